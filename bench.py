@@ -6,6 +6,9 @@
     rank 0 prints the line; under the driver's own `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
     it runs as one of the ranks.  --dry-run: the N-rank plumbing over gloo on CPUs (no GPU, no verification, value 0): the CPU
     tier's rehearsal of the launch path.
+    A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the benchmark
+    measures (the stage A / stage B split, the secondary legs, the CPU baseline).  --dump-outputs DIR writes the last
+    timed step's verdicts to DIR/accept.npy (float32, one 0/1 per tuple of the global batch).
 
 A step = one pass of the hot path (stage A + stage B kernels, through the C-ABI's
 device-pointer entry) over one batch of 2^20 synthetic tuples already resident in HBM.  With
@@ -1027,6 +1030,8 @@ def dry_run(args, world, rank):
         dist.all_gather_into_tensor(allt, t)
         per_rank = [float(x) for x in allt]
     ok = bool((gathered[rank * nbytes:(rank + 1) * nbytes].numpy() == valid).all())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, np, gathered.numpy(), world, n)
     if rank == 0:
         print(json.dumps({
             "metric": "ECDSA P-256 verifies/sec at batch=1M", "value": 0.0, "unit": "verifies/s", "n_gpus": world, "steps": args.steps,
@@ -1046,7 +1051,7 @@ def shard_of_rank(synth, np, dist, rank, n):
     Generating 2^20 signatures takes ~30 s of every host core, so rank 0 generates (or finds the /tmp cache) and the others load it."""
     if dist is not None and rank != 0:
         dist.barrier()
-    tuples, valid = synth.gen_batch(SEED, n)
+    tuples, valid = synth.gen_batch(SEED, n, threads=_host_cores())     # the CPUs this process may use, not all the host has
     if dist is not None and rank == 0:
         dist.barrier()
     if rank:
@@ -1058,18 +1063,43 @@ def shard_of_rank(synth, np, dist, rank, n):
     return tuples, valid
 
 
+DUMP_MAX_VERDICTS = 1 << 24                 # 64 MB of float32
+
+
+def dump_outputs(out_dir, np, bitmaps, world, n):
+    """--dump-outputs: the accept bitmaps of the last timed step (what a caller of the entry receives; `world` of them, one per rank,
+    back to back) as DIR/accept.npy, one float32 0/1 per tuple of the global batch in rank-then-tuple order.  Past DUMP_MAX_VERDICTS
+    tuples, a fixed seeded sample of them, with their indices in the global batch in DIR/accept_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    bits = np.unpackbits(np.asarray(bitmaps, dtype=np.uint8).reshape(world, -1), axis=1, bitorder="little")
+    verdicts = bits[:, :n].reshape(-1)
+    n = verdicts.size
+    if n > DUMP_MAX_VERDICTS:
+        index = np.sort(np.random.default_rng(SEED).choice(n, DUMP_MAX_VERDICTS, replace=False))
+        verdicts = verdicts[index]
+        np.save(os.path.join(out_dir, "accept_index.npy"), index.astype(np.float64))
+    np.save(os.path.join(out_dir, "accept.npy"), verdicts.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tuples", type=int, default=1 << 20, help="tuples per GPU (default: the headline 2^20)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--primary-only", action="store_true", help="skip the secondary legs (grouping off, registered keys): quick A/B runs")
-    ap.add_argument("--warm-leg", action="store_true", help="with --primary-only: still run the warm-key-cache leg")
-    ap.add_argument("--legs", default="", help="comma-separated names of the secondary legs to run (default: all of them); dev sessions")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary measurements: the stage A / stage B kernel split, every secondary "
+                         "leg (1 GPU) and the CPU baseline; the options below select among them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (and the variant legs' own)")
+    ap.add_argument("--primary-only", action="store_true", help="with --full: skip the secondary legs (grouping off, registered keys): quick A/B runs")
+    ap.add_argument("--warm-leg", action="store_true", help="with --full --primary-only: still run the warm-key-cache leg")
+    ap.add_argument("--legs", default="", help="with --full: comma-separated names of the secondary legs to run (default: all of them); dev sessions")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed to DIR/accept.npy (float32, one 0/1 verdict per tuple)")
     ap.add_argument("--dry-run", action="store_true", help="the N-rank launch path over gloo on CPUs: no GPU, nothing verified (CPU tier)")
     args = ap.parse_args()
+    if (args.legs or args.warm_leg) and not args.full:
+        ap.error("--legs and --warm-leg select among the secondary measurements: add --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
 
@@ -1141,19 +1171,24 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     my_elapsed = elapsed
+    got = d_bitmap.cpu().numpy()            # the last timed step's verdicts (--full runs the same entry again below)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, np, d_all.cpu().numpy() if world > 1 else got, world, n)
     gather_ms = sum(a.elapsed_time(b) for a, b in gather_events) / len(gather_events) if gather_events else 0.0
     dominant_us, dominant_launches = sbv.profile_read_dominant()
     sbv.profile_read()
-    sbv.profile_enable(True)
-    for _ in range(2):
-        step()
-    fence()
-    d2_us, d2_launches = sbv.profile_read_dominant()
     dom_steps = args.steps
-    if dominant_launches == 0:              # SBV_BENCH_PROFILE=0: the dominant kernel's duration comes from the untimed pass
-        dominant_us, dominant_launches, dom_steps = d2_us, d2_launches, 2
-    prep_us, verify_us, split_launches = sbv.profile_read()
-    prep_us, verify_us = prep_us / max(1, split_launches), verify_us / max(1, split_launches)
+    split = None
+    if args.full:
+        sbv.profile_enable(True)
+        for _ in range(2):
+            step()
+        fence()
+        d2_us, d2_launches = sbv.profile_read_dominant()
+        if dominant_launches == 0:          # SBV_BENCH_PROFILE=0: the dominant kernel's duration comes from the untimed pass
+            dominant_us, dominant_launches, dom_steps = d2_us, d2_launches, 2
+        prep_us, verify_us, split_launches = sbv.profile_read()
+        split = {"k_p256_prep": prep_us / max(1, split_launches), "stage_b_all_kernels": verify_us / max(1, split_launches)}
     launches = args.steps * ((n + (1 << 21) - 1) >> 21)          # calls x chunks of 2^21 tuples
     sbv.profile_enable(False)
     groups, n_grouped, n_ungrouped, n_key_rejected = sbv.last_group_stats()
@@ -1170,13 +1205,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
 
-    got = d_bitmap.cpu().numpy()
     ok = bool((got == valid).all())
 
     # Secondary measurement (NOT part of `value`): the same batch with in-step key grouping switched off,
     # i.e. what a batch of 2^20 all-distinct keys costs (every tuple through the generic doubling kernel).
     ungrouped = None
-    if world == 1 and not args.primary_only:
+    if world == 1 and args.full and not args.primary_only:
         try:
             sbv.set_grouping(False)
             sbv.verify_batch_dev(d_tuples.data_ptr(), n, d_bitmap.data_ptr(), stream.cuda_stream)
@@ -1201,7 +1235,7 @@ def main():
     # Secondary measurement (NOT part of `value`): the same signatures through the registered-key entry
     # (key slots instead of inline public keys: what VerifyConsenterSig / decision replay use).
     keyed = None
-    if world == 1 and not args.primary_only:
+    if world == 1 and args.full and not args.primary_only:
         try:
             t2 = tuples.reshape(n, 160)
             keys, counts = np.unique(t2[:, 96:160], axis=0, return_counts=True)
@@ -1232,7 +1266,7 @@ def main():
         except Exception as e:  # the headline number must not depend on the secondary leg
             keyed = {"error": repr(e)}
     extra = {}
-    if world == 1 and not args.primary_only:
+    if world == 1 and args.full and not args.primary_only:
         for name, fn in (("warm_key_cache", lambda: leg_warm_cache(sbv, torch, d_tuples, d_bitmap, valid, n, max(2, args.steps // 2), stream)),
                          ("all_valid", lambda: leg_all_valid(sbv, synth, torch, n, max(2, args.steps // 2), stream)),
                          ("key_count_sweep", lambda: leg_key_count_sweep(sbv, synth, torch, n, stream)),
@@ -1254,7 +1288,7 @@ def main():
                 extra[name] = fn()
             except Exception as e:      # noqa: BLE001 - the headline number must not depend on a secondary leg
                 extra[name] = {"error": repr(e)}
-    if world == 1 and args.primary_only and args.warm_leg:
+    if world == 1 and args.full and args.primary_only and args.warm_leg:
         extra["warm_key_cache"] = leg_warm_cache(sbv, torch, d_tuples, d_bitmap, valid, n, max(2, args.steps // 2), stream)
     if world > 1:
         flag = torch.tensor([1 if ok else 0], device="cuda")
@@ -1277,7 +1311,8 @@ def main():
             share = (Q_ADDS_PER_TUPLE / dom_launches_per_step) / (G_ADDS_PER_TUPLE + Q_ADDS_PER_TUPLE)
         else:
             dom_name, dom_units, share = "k_p256_verify", n, 1.0
-        achieved = ALGO_BYTES_PER_VERIFY * dom_units * share / kern_s / 1e9
+        # SBV_BENCH_PROFILE=0 without --full: no launch of the dominant kernel was timed, so no roofline
+        achieved = ALGO_BYTES_PER_VERIFY * dom_units * share / kern_s / 1e9 if kern_s else None
         traffic, traffic_source = None, None
         tpath = os.path.join(ROOT, "profiles", "traffic.json")      # per-launch HBM bytes from a rocprofv3 --pmc run
         if os.path.exists(tpath):
@@ -1302,7 +1337,7 @@ def main():
             "per_rank_ms_per_step": per_rank_ms, "per_rank_dominant_kernel_us": per_rank_dom_us,
             "all_gather_ms": gather_ms if world > 1 else None,
             "self_launched": os.environ.get("SBV_BENCH_SELF_LAUNCHED") == "1",
-            "kernel_us": {"k_p256_prep": prep_us, "stage_b_all_kernels": verify_us,
+            "kernel_us": {**(split or {}),
                           dom_name: dominant_us / max(1, dominant_launches), dom_name + "_launches_per_step": dom_launches_per_step,
                           "launches": launches},
             "key_grouping": {"enabled": was_grouped, "groups": groups, "tuples_registered_key_kernel": n_grouped,
@@ -1310,14 +1345,14 @@ def main():
                              "key_sorted_list": os.environ.get("SBV_GROUP_SORT", "1") != "0",
                              "note": "in-step grouping by public key and counting sort of the grouped tuples by key (consensus_amd/csrc/p256_group.h); all of it is inside the timed region"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
+                         "frac": achieved / HBM_PEAK_GBPS if kern_s else None, "traffic": traffic, "traffic_source": traffic_source,
                          "kernel": dom_name, "units_per_launch": dom_units, "share_of_a_tuples_stage_b_per_launch": share,
                          "note": "algorithmic bytes = 160.125 B/verify x tuples that launch processed x the share of their "
                                  "stage B it executes / its avg duration (HIP events on the launch stream); the path is "
                                  "integer-ALU bound, see DESIGN.md"},
         }
         # share of the integer-multiply pipe's measured peak that the dominant kernel sustains
-        if was_grouped:
+        if was_grouped and kern_s:
             # 32 windows for every tuple + the carry window in the wavefronts that need it: 1 - (1 - 0.0039)^64 = 22 % for
             # uniform scalars (p256_comb29.h: qphase29_point)
             adds_per_launch = Q_ADDS_PER_TUPLE / dom_launches_per_step
@@ -1331,7 +1366,7 @@ def main():
             line["without_key_grouping"] = ungrouped
         if keyed is not None:
             line["registered_key_path"] = keyed
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(tuples, n, got)
         print(json.dumps(line), flush=True)
         if not ok:

@@ -9,6 +9,7 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -68,3 +69,56 @@ def test_rank_shards_are_rotations_with_matching_verdicts(oracle):
         oracle.sbvo_p256_verify_batch(t.ctypes.data, n, got, os.cpu_count() or 1)
         assert got.raw == v.tobytes()
     assert 0 < int(np.unpackbits(base_v).sum()) < n
+
+
+def test_dump_outputs_dry_run_writes_the_verdicts(tmp_path):
+    """--dump-outputs DIR: one float32 0/1 per tuple of the global batch in DIR/accept.npy (a dry run dumps the generator's own bitmap,
+    the only bitmap it has); a size that is not a multiple of 8 must not shift the verdicts."""
+    import synth
+    n = 4100
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run", "--tuples", str(n), "--steps", "2",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert _last_json(p.stdout)["steps"] == 2
+    got = np.load(tmp_path / "accept.npy")
+    _, valid = synth.gen_batch(0x5B7F2026, n)
+    assert got.dtype == np.float32 and got.shape == (n,)
+    assert (got == np.unpackbits(valid, bitorder="little")[:n]).all()
+    assert not (tmp_path / "accept_index.npy").exists()
+
+
+def test_dump_outputs_samples_past_64_mb(tmp_path):
+    import bench
+    n = bench.DUMP_MAX_VERDICTS // 2 + 3
+    rng = np.random.default_rng(1)
+    bits = rng.integers(0, 2, size=(3, n), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path), np, np.packbits(bits, axis=1, bitorder="little"), 3, n)
+    got, index = np.load(tmp_path / "accept.npy"), np.load(tmp_path / "accept_index.npy")
+    assert got.dtype == np.float32 and got.nbytes <= 64 << 20 and got.shape == index.shape == (bench.DUMP_MAX_VERDICTS,)
+    assert (got == bits.reshape(-1)[index.astype(np.int64)]).all()
+
+
+def test_secondary_options_need_full():
+    for extra in (["--legs", "replay_550k"], ["--primary-only", "--warm-leg"]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run"] + extra,
+                           capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert p.returncode != 0 and "--full" in p.stderr
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_bitmap(tmp_path):
+    """A plain run (no --full) on the GPU: the headline fields, exactly --steps timed steps, none of the secondary legs, and the last
+    timed step's verdicts in DIR/accept.npy equal to the generator's expected bitmap."""
+    import synth
+    n = 1 << 16
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--tuples", str(n), "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = _last_json(p.stdout)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["bitmap_correct"] is True
+    assert line["unit"] == "verifies/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert abs(line["value"] - n * 1e3 / line["ms_per_step"]) <= 1e-6 * line["value"]
+    assert not {"cpu_baseline", "warm_key_cache", "without_key_grouping", "registered_key_path"} & set(line)
+    got = np.load(tmp_path / "accept.npy")
+    _, valid = synth.gen_batch(0x5B7F2026, n)
+    assert got.dtype == np.float32 and (got == np.unpackbits(valid, bitorder="little")[:n]).all()

@@ -3,6 +3,7 @@ mechanically is: every cgo call site against include/sbv.h (tools/check_cgo.py: 
 element types), that the checker really catches a wrong call, the method set of api.Verifier / api.Signer /
 api.RequestInspector (pkg/api/dependencies.go:46-83 of the reference) signature for signature, and that every file is at
 least lexically sound (balanced brackets outside strings and comments, one package clause)."""
+import json
 import os
 import re
 import shutil
@@ -77,21 +78,15 @@ def test_api_method_sets_match_the_reference_interfaces():
             n, p, r = _shape(want)
             assert n in have, (recv, n)
             assert have[n] == (p, r), (recv, n, have[n], (p, r))
-    ref = "/root/reference/pkg/api/dependencies.go"             # present in the build container only
-    if os.path.exists(ref):
-        rsrc = open(ref).read()
-        for iface, methods in (("Verifier", API["Verifier"][:7]), ("Signer", API["Signer"]), ("RequestInspector", API["Verifier"][7:])):
-            body = re.search(r"type " + iface + r" interface \{(.*?)\n\}", rsrc, flags=re.S).group(1)
-            rmethods = {}
-            for line in body.split("\n"):
-                line = line.split("//")[0].strip()
-                if re.match(r"\w+\(", line):
-                    n, p, r = _shape(line)
-                    rmethods[n] = ([t.replace("types.", "bft.") for t in p], [t.replace("types.", "bft.") for t in r])
-            assert set(rmethods) == {_shape(m)[0] for m in methods}, (iface, sorted(rmethods))
-            for m in methods:
-                n, p, r = _shape(m)
-                assert rmethods[n] == (p, r), (iface, n, rmethods[n], (p, r))
+    # the reference's interfaces, method by method (tests/golden/reference_api_interfaces.json, taken from pkg/api/dependencies.go)
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_api_interfaces.json")))["interfaces"]
+    for iface, methods in (("Verifier", API["Verifier"][:7]), ("Signer", API["Signer"]), ("RequestInspector", API["Verifier"][7:])):
+        rmethods = {n: ([t.replace("types.", "bft.") for t in m["params"]], [t.replace("types.", "bft.") for t in m["results"]])
+                    for n, m in ref[iface].items()}
+        assert set(rmethods) == {_shape(m)[0] for m in methods}, (iface, sorted(rmethods))
+        for m in methods:
+            n, p, r = _shape(m)
+            assert rmethods[n] == (p, r), (iface, n, rmethods[n], (p, r))
 
 
 def _strip(src):

@@ -1,8 +1,8 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}; OUT=gpurun_out/r05r; mkdir -p $OUT
-python bench.py --steps 6 --warmup 2 --no-cpu-baseline --legs replay_550k > /dev/null 2>&1
+python bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --legs replay_550k > /dev/null 2>&1
 for rep in 1 2; do
-SBV_HOT_KEYS=0 timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --legs replay_550k,end_to_end > $OUT/bench_hot_off_$rep.json 2> $OUT/bench_hot_off_$rep.err
-timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --legs replay_550k,end_to_end > $OUT/bench_hot_on_$rep.json 2> $OUT/bench_hot_on_$rep.err
+SBV_HOT_KEYS=0 timeout 300 python bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --legs replay_550k,end_to_end > $OUT/bench_hot_off_$rep.json 2> $OUT/bench_hot_off_$rep.err
+timeout 300 python bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --legs replay_550k,end_to_end > $OUT/bench_hot_on_$rep.json 2> $OUT/bench_hot_on_$rep.err
 done
 timeout 300 python tools/key_sweep.py 20 1024,4096,16384 > $OUT/key_sweep.json 2> $OUT/key_sweep.err; cat $OUT/key_sweep.err | grep -v amdgpu
 python3 - <<'PY'

@@ -3,7 +3,7 @@
 # every artefact under gpurun_out/<tag>/ (copy what is to be judged into profiles/rNN/).  Steps (arguments after ':' are
 # comma-separated; spaces inside a step need quoting by the caller):
 #   pytest[:<-k expression>]      python -m pytest tests -m gpu -q  (whole tier, or the selection)
-#   bench[:<name>[:<extra flags>]] bench.py with the driver's flags (--gpus 1 --steps 20 --warmup 5) -> bench_<name>.json
+#   bench[:<name>[:<extra flags>]] bench.py with the driver's flags and every leg (--gpus 1 --steps 20 --warmup 5 --full) -> bench_<name>.json
 #   stats                         rocprofv3 --kernel-trace --stats of bench.py (primary leg) -> kernel_stats.csv, timeline.txt
 #   pmc                           separate --pmc passes: FETCH_SIZE, WRITE_SIZE, SQ counters -> pmc_summary.json
 #   sweep:<log2,log2,...>         tools/sweep_sizes.py (cold / warm / one-lane per batch size)
@@ -28,7 +28,7 @@ for step in "$@"; do
       else run pytest_gpu 2400 python -m pytest tests -m gpu -q -rs --durations=25; tail -6 "$OUT/pytest_gpu.log"; fi ;;
     bench)
       name=${a1:-driver_flags}
-      ( timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 ${a2:-} > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"; echo "rc=$?" >> "$OUT/bench_$name.err" )
+      ( timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full ${a2:-} > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"; echo "rc=$?" >> "$OUT/bench_$name.err" )
       python3 - "$OUT/bench_$name.json" <<'PY'
 import json, sys
 try:
@@ -65,7 +65,7 @@ PY
       for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" "sq SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_SALU SQ_ACTIVE_INST_VALU"; do
         set -- $pass; pname=$1; shift
         # the primary leg AND the Ed25519 / secp256k1 legs (round 5: their roofline.traffic used to be null: no PMC pass covered them)
-        ( cd /tmp; SBV_BENCH_ED_HOT=0 timeout 600 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/pmc_$pname" -o p -- python "$ROOT/bench.py" --steps 4 --warmup 2 --no-cpu-baseline --legs ed25519,secp256k1 > "$OUT/pmc_$pname.log" 2>&1; echo "rc=$?" >> "$OUT/pmc_$pname.log" )
+        ( cd /tmp; SBV_BENCH_ED_HOT=0 timeout 600 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/pmc_$pname" -o p -- python "$ROOT/bench.py" --steps 4 --warmup 2 --full --no-cpu-baseline --legs ed25519,secp256k1 > "$OUT/pmc_$pname.log" 2>&1; echo "rc=$?" >> "$OUT/pmc_$pname.log" )
       done
       python3 - "$OUT" <<'PY'
 import csv, collections, json, os, sys

@@ -12,7 +12,7 @@ summary = json.load(open(sys.argv[1]))
 tag = sys.argv[2]
 out = {
     "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, counters only: no tracing in the same run) over "
-              f"`python bench.py --steps 4 --warmup 2 --no-cpu-baseline --legs ed25519,secp256k1`, session {tag} (tools/gpu_session.sh pmc); "
+              f"`python bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --legs ed25519,secp256k1`, session {tag} (tools/gpu_session.sh pmc); "
               f"summary: profiles/{tag[:3]}/pmc_summary_{tag}.json",
     "method": "FETCH_SIZE and WRITE_SIZE are KiB; FETCH_SIZE doubled per /opt/skills/guides/MI355X_MICROARCH.md (gfx950 tallies 128-B "
               "requests as 64 B); the guide calibrates that factor on wide coalesced reads only - the comb phases read 64-byte (96-byte: "
