@@ -255,6 +255,102 @@ def ed25519_verify_batch_dev(d_tuples_ptr: int, n: int, d_bitmap_ptr: int, strea
     _check(load().sbv_ed25519_verify_batch_dev(d_tuples_ptr, n, d_bitmap_ptr, stream))
 
 
+def ed25519_register_keys(pks) -> list:
+    """pks: iterable of 32-byte encoded Ed25519 keys -> list of slots (equal encodings share a slot; see include/sbv.h)."""
+    pks = list(pks)
+    blob = b"".join(pks)
+    if len(blob) != 32 * len(pks):
+        raise ValueError("every key must be 32 bytes")
+    out = (ctypes.c_uint32 * max(1, len(pks)))()
+    lib = load()
+    lib.sbv_ed25519_register_keys.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
+    _check(lib.sbv_ed25519_register_keys(blob, len(pks), out))
+    return list(out[:len(pks)])
+
+
+def ed25519_key_count() -> int:
+    rc = load().sbv_ed25519_key_count()
+    if rc < 0:
+        _check(rc)
+    return rc
+
+
+def ed25519_clear_keys() -> None:
+    _check(load().sbv_ed25519_clear_keys())
+
+
+def ed25519_wide_keys(max_keys: int = 64) -> None:
+    """sbv_ed25519_wide_keys: cap on the registered Ed25519 slots with a 16-bit comb (0 = none)."""
+    lib = load()
+    lib.sbv_ed25519_wide_keys.argtypes = [ctypes.c_uint32]
+    _check(lib.sbv_ed25519_wide_keys(max_keys))
+
+
+def ed25519_widen_keys(slots) -> None:
+    """sbv_ed25519_widen_keys: a 16-bit comb of -A for each of these registered slots (the consenters')."""
+    slots = list(slots)
+    arr = (ctypes.c_uint32 * max(1, len(slots)))(*slots)
+    lib = load()
+    lib.sbv_ed25519_widen_keys.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+    _check(lib.sbv_ed25519_widen_keys(arr, len(slots)))
+
+
+def ed25519_wide_key_stats():
+    """(slots holding a 16-bit comb, 16, cap, KiB per comb)"""
+    out = (ctypes.c_uint32 * 4)()
+    lib = load()
+    lib.sbv_ed25519_wide_key_stats.argtypes = [ctypes.c_void_p]
+    _check(lib.sbv_ed25519_wide_key_stats(out))
+    return out[0], out[1], out[2], out[3]
+
+
+def ed25519_wide_selfcheck(slot: int) -> bool:
+    """sbv_ed25519_wide_selfcheck: the device-built 16-bit comb of `slot` equals the host builder's output byte for byte."""
+    lib = load()
+    lib.sbv_ed25519_wide_selfcheck.argtypes = [ctypes.c_uint32]
+    rc = lib.sbv_ed25519_wide_selfcheck(slot)
+    if rc < 0:
+        _check(rc)
+    return rc == 1
+
+
+def ed25519_verify_batch_keyed(rsk: bytes, slots, n: Optional[int] = None) -> bytes:
+    """Registered-key form: rsk = n x 96 bytes (R | S | k), slots = n key slots -> accept bitmap."""
+    if n is None:
+        n = len(rsk) // 96
+    arr = (ctypes.c_uint32 * max(1, n))(*slots)
+    out = ctypes.create_string_buffer(max(1, (n + 7) // 8))
+    buf = (ctypes.c_char * len(rsk)).from_buffer_copy(rsk) if n else None
+    lib = load()
+    lib.sbv_ed25519_verify_batch_keyed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    _check(lib.sbv_ed25519_verify_batch_keyed(buf, arr, n, out))
+    return out.raw[:(n + 7) // 8]
+
+
+def ed25519_verify_batch_keyed_dev(d_rsk_ptr: int, d_slots_ptr: int, n: int, d_bitmap_ptr: int, stream: int = 0) -> None:
+    lib = load()
+    lib.sbv_ed25519_verify_batch_keyed_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib.sbv_ed25519_verify_batch_keyed_dev(d_rsk_ptr, d_slots_ptr, n, d_bitmap_ptr, stream))
+
+
+def ed25519_verify_msgs_keyed(sigs, msgs, slots) -> bytes:
+    """(64-byte sig, message, slot) triples -> accept bitmap; k = SHA-512(R | A | M) mod L on the device, A from the registry."""
+    n = len(sigs)
+    offs = (ctypes.c_uint64 * (n + 1))()
+    acc = 0
+    for i, m in enumerate(msgs):
+        offs[i] = acc
+        acc += len(m)
+    offs[n] = acc
+    arr = (ctypes.c_uint32 * max(1, n))(*slots)
+    out = ctypes.create_string_buffer(max(1, (n + 7) // 8))
+    lib = load()
+    lib.sbv_ed25519_verify_msgs_keyed.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
+                                                  ctypes.c_size_t, ctypes.c_void_p]
+    _check(lib.sbv_ed25519_verify_msgs_keyed(b"".join(sigs), b"".join(msgs), offs, arr, n, out))
+    return out.raw[:(n + 7) // 8]
+
+
 def secp256k1_verify_batch(tuples: bytes, n: Optional[int] = None) -> bytes:
     """ECDSA over secp256k1 on 160-byte tuples r | s | hash | Qx | Qy (include/sbv.h); returns the accept bitmap."""
     if n is None:

@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "ed25519_group.h"
+#include "ed25519_keyed.h"
 #include "ed25519_kernels.h"
 #include "group_kernels_common.h"
 #include "p256_kernels.h"
@@ -398,6 +399,84 @@ hipError_t launch_ed25519_verify_grouped(const uint8_t* d_tuples, size_t n, cons
     hipLaunchKernelGGL(k_pack_bitmap, dim3((unsigned)(((n + 7) / 8 + 255) / 256)), dim3(256), 0, stream, b.acc, n, d_bitmap);
 #undef SBV_TRY
     if (prof && prof_pairs) *prof_pairs = chunks;
+    return hipGetLastError();
+}
+
+// ---- registered keys (ed25519_keyed.h): expand | G phase | keyed Q phase | finish ------------------------------------------------------
+// records R | S | k + slots -> 128-byte tuples, A from the registry
+__global__ __launch_bounds__(256) void k_ed_keyed_expand(const uint8_t* __restrict__ recs, const u32* __restrict__ slots, size_t n, u32 nkeys,
+                                                         const uint8_t* __restrict__ kenc, uint8_t* __restrict__ tuples) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) ed_keyed_expand_lane(recs, slots, i, nkeys, kenc, tuples);
+}
+// the keyed twin of k_ed_msg_frontend (ed25519_kernels.hip): signatures n x 64, messages msgs[moff[i] .. moff[i+1]), A from the registry
+__global__ __launch_bounds__(256) void k_ed_keyed_msg_frontend(const uint8_t* __restrict__ sigs, const u32* __restrict__ slots, u32 nkeys,
+                                                               const uint8_t* __restrict__ kenc, const uint8_t* __restrict__ msgs,
+                                                               const u64* __restrict__ moff, size_t n, u32* __restrict__ tuples) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const u64 m0 = moff[i], m1 = moff[i + 1];
+    u32 rec[32];
+    ed_keyed_msg_frontend_lane(sigs + i * 64, slots[i], nkeys, kenc, msgs + m0, (size_t)(m1 - m0), rec);
+    ed_q4* t = reinterpret_cast<ed_q4*>(tuples + i * 32);
+    SBV_UNROLL
+    for (int q = 0; q < 8; ++q) { const ed_q4 v = {rec[4 * q], rec[4 * q + 1], rec[4 * q + 2], rec[4 * q + 3]}; t[q] = v; }
+}
+// [k](-A) for every tuple from its slot's registry comb, one launch: a wavefront whose lanes all own a 16-bit comb walks those (16
+// additions), any other the 8-bit combs (32).  Leaves the survivors pending for k_ed_finish.
+#ifndef SBV_ED_KEYED_WAVES
+#define SBV_ED_KEYED_WAVES SBV_ED_GROUP_WAVES
+#endif
+__global__ __launch_bounds__(SBV_VERIFY_BLOCK, SBV_ED_KEYED_WAVES) void k_ed_keyed_qphase(const uint8_t* __restrict__ tuples, const u32* __restrict__ slots, size_t n,
+                                                                  EdKeyedRegistry r, u32* __restrict__ gacc, const uint8_t* __restrict__ okb,
+                                                                  uint8_t* __restrict__ acc) {
+    const size_t i = (size_t)blockIdx.x * SBV_VERIFY_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const u32 slot = slots[i];
+    const bool w = ed_keyed_slot_wide(slot, r.nkeys, r.kwidx);
+    const bool wide = __ballot(w) == __ballot(true);
+    const bool v = ed_keyed_qphase_lane(tuples, i, slot, r.nkeys, r.ktab, r.kvalid, r.wtab, r.kwidx, wide, gacc, okb);
+    acc[i] = v ? SBV_ED_PENDING : 0;
+}
+// the 16-bit combs of `count` widened slots: plist = (slot, comb) pairs; lane (key, window, part) writes 32 entries (ed_widetab_lane),
+// a bounded grid walks the 16 x 1024 items per key; tmp = SBV_ED_HOT_TMP_WORDS per lane of the grid
+__global__ __launch_bounds__(64) void k_ed_keyed_widen(const u32* __restrict__ plist, u32 count, const aniels* __restrict__ ktab,
+                                                       u32* __restrict__ tmp, uint8_t* __restrict__ wtab) {
+    const u32 total = count * (SBV_ED_HOT_WINDOWS * SBV_ED_HOT_PARTS);
+    const u32 gid = blockIdx.x * 64 + threadIdx.x;
+    u32* mine = tmp + (size_t)gid * SBV_ED_HOT_TMP_WORDS;
+    for (u32 item = gid; item < total; item += gridDim.x * 64) {
+        const u32 part = item % SBV_ED_HOT_PARTS, j = (item / SBV_ED_HOT_PARTS) % SBV_ED_HOT_WINDOWS, k = item / (SBV_ED_HOT_PARTS * SBV_ED_HOT_WINDOWS);
+        ed_widetab_lane(ktab + (size_t)plist[2 * k] * SBV_ED_KEYTAB_ENTRIES, j, part, mine, wtab + (size_t)plist[2 * k + 1] * SBV_ED_HOT_COMB_BYTES);
+    }
+}
+
+hipError_t launch_ed_keyed_expand(const uint8_t* d_recs, const u32* d_slots, size_t n, const EdKeyedRegistry& r, uint8_t* d_tuples, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ed_keyed_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_recs, d_slots, n, r.nkeys, r.kenc, d_tuples);
+    return hipGetLastError();
+}
+hipError_t launch_ed_keyed_msg_frontend(const uint8_t* d_sigs, const u32* d_slots, const EdKeyedRegistry& r, const uint8_t* d_msgs, const u64* d_moff,
+                                        size_t n, uint8_t* d_tuples, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ed_keyed_msg_frontend, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_sigs, d_slots, r.nkeys, r.kenc, d_msgs, d_moff, n,
+                       reinterpret_cast<u32*>(d_tuples));
+    return hipGetLastError();
+}
+hipError_t launch_ed25519_verify_keyed(const uint8_t* d_tuples, const u32* d_slots, size_t n, const EdKeyedRegistry& r, const edcomb& bcomb,
+                                       u32* d_gacc, uint8_t* d_okb, uint8_t* d_acc, uint8_t* d_bitmap, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const unsigned gv = (unsigned)((n + SBV_VERIFY_BLOCK - 1) / SBV_VERIFY_BLOCK);
+    hipLaunchKernelGGL(k_ed_gphase, dim3(gv), dim3(SBV_VERIFY_BLOCK), 0, stream, d_tuples, n, bcomb, d_gacc, n, d_okb, 1);
+    hipLaunchKernelGGL(k_ed_keyed_qphase, dim3(gv), dim3(SBV_VERIFY_BLOCK), 0, stream, d_tuples, d_slots, n, r, d_gacc, d_okb, d_acc);
+    const size_t fl = (n + SBV_ED_FINISH_T - 1) / SBV_ED_FINISH_T;
+    hipLaunchKernelGGL(k_ed_finish, dim3((unsigned)((fl + 255) / 256)), dim3(256), 0, stream, d_tuples, n, d_gacc, n, d_acc, 1);
+    hipLaunchKernelGGL(k_pack_bitmap, dim3((unsigned)(((n + 7) / 8 + 255) / 256)), dim3(256), 0, stream, d_acc, n, d_bitmap);
+    return hipGetLastError();
+}
+hipError_t launch_ed_keyed_widen(const u32* d_plist, u32 count, const aniels* d_ktab, u32* d_tmp, u32 blocks, uint8_t* d_wtab, hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ed_keyed_widen, dim3(blocks), dim3(64), 0, stream, d_plist, count, d_ktab, d_tmp, d_wtab);
     return hipGetLastError();
 }
 

@@ -39,6 +39,24 @@ hipError_t launch_ed25519_verify_grouped(const uint8_t* d_tuples, size_t n, cons
 // message front end: raw signatures / keys / messages -> 128-byte tuples on the device (sha512_dev.h)
 hipError_t launch_ed_msg_frontend(const uint8_t* d_sigs, const uint8_t* d_pks, const uint8_t* d_msgs, const u64* d_moff, size_t n,
                                   u32* d_tuples, hipStream_t stream);
+// Registered keys (ed25519_keyed.h): the device view of the registry of the default context
+struct EdKeyedRegistry {
+    const aniels* ktab;           // [key_cap][32 x 128] 8-bit combs of -A
+    const uint8_t* kvalid;        // [key_cap] 1 = the encoding is a point
+    const uint8_t* kenc;          // [key_cap][32] the registered encodings
+    const uint8_t* wtab;          // 16-bit combs of the widened slots (SBV_ED_HOT_COMB_BYTES each), or nullptr
+    const u32* kwidx;             // [key_cap] comb of each slot or SBV_ED_WIDE_NONE; nullptr = no slot is wide
+    u32 nkeys;
+};
+// records (n x 96: R | S | k) + slots -> 128-byte tuples; or signatures + messages + slots -> tuples (k hashed on the device)
+hipError_t launch_ed_keyed_expand(const uint8_t* d_recs, const u32* d_slots, size_t n, const EdKeyedRegistry& r, uint8_t* d_tuples, hipStream_t stream);
+hipError_t launch_ed_keyed_msg_frontend(const uint8_t* d_sigs, const u32* d_slots, const EdKeyedRegistry& r, const uint8_t* d_msgs, const u64* d_moff,
+                                        size_t n, uint8_t* d_tuples, hipStream_t stream);
+// G phase | keyed Q phase | finish | pack on `stream`; gacc: n x 160 bytes (16-byte aligned), okb / acc: n bytes
+hipError_t launch_ed25519_verify_keyed(const uint8_t* d_tuples, const u32* d_slots, size_t n, const EdKeyedRegistry& r, const edcomb& bcomb,
+                                       u32* d_gacc, uint8_t* d_okb, uint8_t* d_acc, uint8_t* d_bitmap, hipStream_t stream);
+// 16-bit combs of `count` slots from their 8-bit combs: plist = (slot, comb index) pairs; tmp = blocks x 64 x SBV_ED_HOT_TMP_WORDS words
+hipError_t launch_ed_keyed_widen(const u32* d_plist, u32 count, const aniels* d_ktab, u32* d_tmp, u32 blocks, uint8_t* d_wtab, hipStream_t stream);
 #define SBV_ED_KEYTAB_ENTRIES_PER_KEY 4096   // 32 windows x 128 entries (ed25519_group.h)
 void host_build_ed_b16(aniels* out);      // 16 x 32768 affine-Niels multiples of B: the comb of the one-lane kernel
 void host_build_ed_bcomb(int bits, aniels* out);   // edcomb_entries(bits) entries: the grouped step's comb (SBV_ED_B_BITS, default 20), one host thread per window

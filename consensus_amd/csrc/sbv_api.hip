@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/sbv.h"
+#include "ed25519_keyed.h"
 #include "ed25519_kernels.h"
 #include "p256_kernels.h"
 #include "k256_core.h"
@@ -135,6 +136,16 @@ struct Context {
     size_t wide_nofit_at = (size_t)-1;
     bool kwide_auto = true;             // width by the number of widened keys: 20 bits up to kWideAutoSplit keys, 16 beyond (sbv_p256_wide_keys)
     u32 kwide_max = 64;
+    // registered Ed25519 keys (ed25519_keyed.h; sbv_ed25519_register_keys): the default context's half of g_edreg, allocated on the
+    // first registration.  Slot s: 8-bit comb of -A, valid byte, encoding, index of its 16-bit comb in d_ed_wtab (or SBV_ED_WIDE_NONE)
+    sbv::aniels* d_ed_ktab = nullptr;
+    uint8_t* d_ed_kvalid = nullptr;
+    uint8_t* d_ed_kenc = nullptr;
+    u32* d_ed_kwidx = nullptr;
+    size_t ed_key_cap = 0, ed_nkeys = 0;
+    uint8_t* d_ed_wtab = nullptr;          // comb w (SBV_ED_HOT_COMB_BYTES) belongs to slot ed_wide_slots[w]
+    size_t ed_wtab_cap = 0;
+    std::vector<u32> ed_wide_slots;
     int profiling = 0;                     // 0 off, 1 = step triples + dominant-kernel pairs, 2 = dominant-kernel pairs only
     std::vector<hipEvent_t> prof_events;   // triples: before prep, after prep, after verify
     std::vector<hipEvent_t> prof_dom;      // pairs around the dominant kernel of grouped batches (nullptr pair = ungrouped)
@@ -991,6 +1002,9 @@ int shutdown_context(Context& c) {
     if (c.d_kwidx) (void)hipFree(c.d_kwidx);
     c.d_kwide = nullptr; c.d_kwidx = nullptr; c.kwide_cap = 0; c.wide_slots.clear();
     c.key_index.clear();
+    for (void* p : {(void*)c.d_ed_ktab, (void*)c.d_ed_kvalid, (void*)c.d_ed_kenc, (void*)c.d_ed_kwidx, (void*)c.d_ed_wtab}) if (p) (void)hipFree(p);
+    c.d_ed_ktab = nullptr; c.d_ed_kvalid = nullptr; c.d_ed_kenc = nullptr; c.d_ed_kwidx = nullptr; c.d_ed_wtab = nullptr;
+    c.ed_key_cap = c.ed_nkeys = 0; c.ed_wtab_cap = 0; c.ed_wide_slots.clear();
     if (c.h_small_in) (void)hipHostFree(c.h_small_in);
     if (c.h_small_out) (void)hipHostFree(c.h_small_out);
     c.h_small_in = c.h_small_out = nullptr; c.d_small_in = c.d_small_out = nullptr;
@@ -1021,9 +1035,11 @@ int shutdown_context(Context& c) {
 }
 }  // namespace
 
+static void ed_registry_forget();
 extern "C" int sbv_shutdown(void) {
     std::unique_lock<std::shared_mutex> rl(g_reg_mu);
     g_reg = Registry();
+    ed_registry_forget();           // takes g_edreg_mu: g_reg_mu -> g_edreg_mu -> g_mu
     std::lock_guard<std::mutex> lk(g_mu);
     rccl_teardown();
     for (auto& up : g_ctxs) {
@@ -2055,6 +2071,418 @@ extern "C" int sbv_ed25519_verify_msgs(const uint8_t* sigs, const uint8_t* pks, 
                                                      reinterpret_cast<u32*>(c.d_tuples), c.stream));
     HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[2], c.stream));
     if ((rc = enqueue_ed25519(c, c.d_tuples, n, c.d_bitmap, c.stream)) != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[3], c.stream));
+    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.h_bitmap, c.d_bitmap, (n + 7) / 8, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[4], c.stream));
+    HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(c.stream));
+    memcpy(accept_bitmap, c.h_bitmap, (n + 7) / 8);
+    tm.h2d_us = 1e3 * ms_between(c.ev[0], c.ev[1]);
+    tm.prep_us = 1e3 * ms_between(c.ev[1], c.ev[2]);       // the front end
+    tm.verify_us = 1e3 * ms_between(c.ev[2], c.ev[3]);
+    tm.d2h_us = 1e3 * ms_between(c.ev[3], c.ev[4]);
+    c.busy_valid = false;
+    tm.total_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    c.timing = tm;
+    return SBV_OK;
+}
+
+// ---- registered Ed25519 keys (ed25519_keyed.h; include/sbv.h: sbv_ed25519_register_keys) ---------------------------------------
+// The registry is process-wide on the host — the slot index (encoding bytes -> slot), every registered encoding and its valid flag, the
+// widening cap — and lives on the default context's device: per slot the 8-bit comb of -A (384 KiB), the valid byte, the encoding for
+// the device front end, and for widened slots a 16-bit comb (64 MiB).  The host copy is what a replication to other contexts would be
+// built from.  Lock order: g_reg_mu -> g_edreg_mu -> g_mu -> Context::mu (registration, widening and clearing take g_edreg_mu and then
+// the default context; the verify entries take the context alone and read its half, which only changes under its lock).
+namespace {
+struct EdRegistry {
+    std::vector<std::string> keys;                    // slot -> the 32 encoding bytes
+    std::unordered_map<std::string, u32> index;       // encoding bytes -> slot (bytes, not points: k hashes the bytes)
+    std::vector<uint8_t> valid;                       // slot -> the encoding is a point
+    u32 wide_max = 64;                                // sbv_ed25519_wide_keys
+} g_edreg;
+std::mutex g_edreg_mu;
+constexpr u32 kEdWideBuildBlocks = 256;              // the wide-comb builder's grid: 16 384 lanes, 84 MB of scratch while it runs
+
+sbv::EdKeyedRegistry ed_reg_view(const Context& c) {
+    sbv::EdKeyedRegistry r;
+    r.ktab = c.d_ed_ktab; r.kvalid = c.d_ed_kvalid; r.kenc = c.d_ed_kenc;
+    r.wtab = c.d_ed_wtab; r.kwidx = c.ed_wide_slots.empty() ? nullptr : c.d_ed_kwidx;
+    r.nkeys = (u32)c.ed_nkeys;
+    return r;
+}
+
+// c.mu held, the device current: room for `want` slots.  Doubles from 64 slots, copies the live slots on the device; a failure leaves the
+// old arrays (and so the registry) as they were.
+int ed_reg_reserve(Context& c, size_t want) {
+    if (want <= c.ed_key_cap) return SBV_OK;
+    size_t cap = c.ed_key_cap ? c.ed_key_cap : 64;
+    while (cap < want) cap *= 2;
+    if (cap > SBV_ED_REG_MAX_KEYS) cap = SBV_ED_REG_MAX_KEYS;
+    sbv::aniels* kt = nullptr; uint8_t* kv = nullptr; uint8_t* ke = nullptr; u32* kw = nullptr;
+    auto drop = [&] { for (void* p : {(void*)kt, (void*)kv, (void*)ke, (void*)kw}) if (p) (void)hipFree(p); (void)hipGetLastError(); };
+    if (hipMalloc(&kt, cap * (size_t)SBV_ED_KEYTAB_ENTRIES * sizeof(sbv::aniels)) != hipSuccess || hipMalloc(&kv, cap) != hipSuccess ||
+        hipMalloc(&ke, cap * 32) != hipSuccess || hipMalloc(&kw, cap * sizeof(u32)) != hipSuccess) {
+        drop();
+        g_err = "sbv_ed25519_register_keys: no device memory for the registry";
+        return SBV_ENOMEM;
+    }
+    const size_t n = c.ed_nkeys;
+    hipError_t e = hipDeviceSynchronize();          // nothing in flight reads the old arrays any more
+    if (e == hipSuccess && n) e = hipMemcpy(kt, c.d_ed_ktab, n * (size_t)SBV_ED_KEYTAB_ENTRIES * sizeof(sbv::aniels), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(kv, c.d_ed_kvalid, n, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(ke, c.d_ed_kenc, n * 32, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(kw, c.d_ed_kwidx, n * sizeof(u32), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = memset_now(kw + n, 0xFF, (cap - n) * sizeof(u32));
+    if (e != hipSuccess) { drop(); return fail(SBV_EDEVICE, "sbv_ed25519_register_keys: growing the registry", e); }
+    for (void* p : {(void*)c.d_ed_ktab, (void*)c.d_ed_kvalid, (void*)c.d_ed_kenc, (void*)c.d_ed_kwidx}) if (p) (void)hipFree(p);
+    c.d_ed_ktab = kt; c.d_ed_kvalid = kv; c.d_ed_kenc = ke; c.d_ed_kwidx = kw;
+    c.ed_key_cap = cap;
+    return SBV_OK;
+}
+
+// c.mu held, the device current: room for `want` 16-bit combs (doubling, at most the cap), the combs there copied on the device
+int ed_wide_reserve(Context& c, size_t want, size_t cap_max) {
+    if (want <= c.ed_wtab_cap) return SBV_OK;
+    size_t cap = c.ed_wtab_cap ? c.ed_wtab_cap : 1;
+    while (cap < want) cap *= 2;
+    if (cap > cap_max) cap = cap_max;
+    uint8_t* w = nullptr;
+    if (hipMalloc(&w, cap * SBV_ED_HOT_COMB_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        g_err = "sbv_ed25519_widen_keys: no device memory for the 16-bit combs";
+        return SBV_ENOMEM;
+    }
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess && !c.ed_wide_slots.empty())
+        e = hipMemcpy(w, c.d_ed_wtab, c.ed_wide_slots.size() * SBV_ED_HOT_COMB_BYTES, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) { (void)hipFree(w); return fail(SBV_EDEVICE, "sbv_ed25519_widen_keys: growing the comb pool", e); }
+    if (c.d_ed_wtab) (void)hipFree(c.d_ed_wtab);
+    c.d_ed_wtab = w;
+    c.ed_wtab_cap = cap;
+    return SBV_OK;
+}
+
+// `count` slots' 8-bit combs, built on the host in parallel (one-time setup, the kernels' field code)
+void ed_build_reg_combs(const std::string* keys, size_t count, std::vector<sbv::aniels>& tabs, std::vector<uint8_t>& valid) {
+    tabs.resize(count * (size_t)SBV_ED_KEYTAB_ENTRIES);
+    valid.assign(count, 0);
+    size_t nt = std::thread::hardware_concurrency();
+    if (nt == 0) nt = 1;
+    if (nt > 64) nt = 64;
+    if (nt > count) nt = count;
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < nt; ++t)
+        th.emplace_back([&, t] {
+            for (size_t j = t; j < count; j += nt)
+                valid[j] = sbv::ed_keyed_host_comb((const uint8_t*)keys[j].data(), &tabs[j * (size_t)SBV_ED_KEYTAB_ENTRIES]) ? 1 : 0;
+        });
+    for (auto& x : th) x.join();
+}
+
+// one chunk (m <= c.cap) of keyed records on `stream`: expand into the qtab planes (128 of their 1792 bytes per tuple), the accumulator,
+// range flags and verdict bytes in the scratch planes (162 of 193 bytes per tuple), then G | keyed Q | finish | pack
+int enqueue_ed_keyed(Context& c, const uint8_t* d_recs, const u32* d_slots, size_t m, uint8_t* d_bitmap, hipStream_t stream, bool expanded = false) {
+    uint8_t* tup = reinterpret_cast<uint8_t*>(c.d_qtab);
+    u32* gacc = reinterpret_cast<u32*>(c.d_scratch);
+    uint8_t* okb = c.d_scratch + c.cap * (size_t)SBV_ED_GACC_WORDS * sizeof(u32);
+    uint8_t* acc = okb + c.cap;
+    const sbv::EdKeyedRegistry r = ed_reg_view(c);
+    if (!expanded) HIP_TRY(SBV_EDEVICE, sbv::launch_ed_keyed_expand(d_recs, d_slots, m, r, tup, stream));
+    HIP_TRY(SBV_EDEVICE, sbv::launch_ed25519_verify_keyed(tup, d_slots, m, r, sbv::edcomb_make(c.d_ed_bcomb, c.ed_bbits, c.ed_bpitch), gacc, okb, acc,
+                                                          d_bitmap, stream));
+    return SBV_OK;
+}
+// the tables every keyed call needs: the comb of B of the grouped step (ensure_ed_bcomb falls back to the one-lane kernel's at 16 bits)
+int ensure_ed_keyed(Context& c, size_t n) {
+    int rc = ensure_capacity(c, n < kMaxChunk ? n : kMaxChunk);
+    if (rc == SBV_OK) rc = ensure_ed_table(c);
+    if (rc == SBV_OK) rc = ensure_ed_bcomb(c);
+    return rc;
+}
+}  // namespace
+
+static void ed_registry_forget() {
+    std::lock_guard<std::mutex> lk(g_edreg_mu);
+    const u32 wm = g_edreg.wide_max;
+    g_edreg = EdRegistry();
+    g_edreg.wide_max = wm;
+}
+
+extern "C" int sbv_ed25519_register_keys(const uint8_t* pks, size_t m, uint32_t* slots_out) {
+    std::lock_guard<std::mutex> rl(g_edreg_mu);
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!pks || !slots_out) { g_err = "null pointer"; return SBV_EINVAL; }
+    std::vector<u32> out(m);
+    std::vector<std::string> fresh;                 // encodings that need a slot, in slot order
+    std::unordered_map<std::string, u32> pending;
+    for (size_t i = 0; i < m; ++i) {
+        const std::string k((const char*)pks + 32 * i, 32);
+        auto it = g_edreg.index.find(k);
+        if (it != g_edreg.index.end()) { out[i] = it->second; continue; }
+        auto pt = pending.find(k);
+        if (pt != pending.end()) { out[i] = pt->second; continue; }
+        const u32 slot = (u32)(g_edreg.keys.size() + fresh.size());
+        pending.emplace(k, slot);
+        fresh.push_back(k);
+        out[i] = slot;
+    }
+    if (g_edreg.keys.size() + fresh.size() > SBV_ED_REG_MAX_KEYS) { g_err = "sbv_ed25519_register_keys: more than 65536 keys"; return SBV_EINVAL; }
+    if (!fresh.empty()) {
+        HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+        std::vector<sbv::aniels> tabs;
+        std::vector<uint8_t> valid;
+        ed_build_reg_combs(fresh.data(), fresh.size(), tabs, valid);
+        std::string enc;
+        for (const std::string& k : fresh) enc += k;
+        const int rc = ed_reg_reserve(c, c.ed_nkeys + fresh.size());
+        if (rc != SBV_OK) return rc;
+        // the new slots lie beyond ed_nkeys: no batch reads them until the count below is raised
+        const size_t s0 = c.ed_nkeys;
+        HIP_TRY(SBV_EDEVICE, hipMemcpy(c.d_ed_ktab + s0 * (size_t)SBV_ED_KEYTAB_ENTRIES, tabs.data(), tabs.size() * sizeof(sbv::aniels), hipMemcpyHostToDevice));
+        HIP_TRY(SBV_EDEVICE, hipMemcpy(c.d_ed_kvalid + s0, valid.data(), valid.size(), hipMemcpyHostToDevice));
+        HIP_TRY(SBV_EDEVICE, hipMemcpy(c.d_ed_kenc + s0 * 32, enc.data(), enc.size(), hipMemcpyHostToDevice));
+        c.ed_nkeys += fresh.size();
+        for (size_t i = 0; i < fresh.size(); ++i) {
+            g_edreg.index.emplace(fresh[i], (u32)g_edreg.keys.size());
+            g_edreg.keys.push_back(fresh[i]);
+            g_edreg.valid.push_back(valid[i]);
+        }
+    }
+    memcpy(slots_out, out.data(), m * sizeof(u32));
+    return SBV_OK;
+}
+
+extern "C" int sbv_ed25519_key_count(void) {
+    SBV_ENTER(c);
+    return c.ready ? (int)c.ed_nkeys : SBV_ENOTINIT;
+}
+
+extern "C" int sbv_ed25519_clear_keys(void) {
+    std::lock_guard<std::mutex> rl(g_edreg_mu);
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+    if (c.d_ed_kwidx && c.ed_key_cap) HIP_TRY(SBV_EDEVICE, memset_now(c.d_ed_kwidx, 0xFF, c.ed_key_cap * sizeof(u32)));
+    c.ed_nkeys = 0;                  // the allocations stay for the next registry
+    c.ed_wide_slots.clear();
+    const u32 wm = g_edreg.wide_max;
+    g_edreg = EdRegistry();
+    g_edreg.wide_max = wm;
+    return SBV_OK;
+}
+
+extern "C" int sbv_ed25519_wide_keys(uint32_t max_keys) {
+    std::lock_guard<std::mutex> rl(g_edreg_mu);
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (max_keys > 4096) { g_err = "sbv_ed25519_wide_keys: at most 4096 keys"; return SBV_EINVAL; }
+    g_edreg.wide_max = max_keys;
+    if (c.ed_wide_slots.size() <= max_keys) return SBV_OK;
+    // fewer than are wide: the first max_keys slots keep their combs (combs 0 .. max_keys - 1), the others go back to their 8-bit combs
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+    const u32 none = SBV_ED_WIDE_NONE;
+    for (size_t w = max_keys; w < c.ed_wide_slots.size(); ++w)
+        HIP_TRY(SBV_EDEVICE, hipMemcpy(c.d_ed_kwidx + c.ed_wide_slots[w], &none, sizeof(u32), hipMemcpyHostToDevice));
+    c.ed_wide_slots.resize(max_keys);
+    if (max_keys == 0 && c.d_ed_wtab) { (void)hipFree(c.d_ed_wtab); c.d_ed_wtab = nullptr; c.ed_wtab_cap = 0; }
+    return SBV_OK;
+}
+
+extern "C" int sbv_ed25519_widen_keys(const uint32_t* slots, size_t m) {
+    std::lock_guard<std::mutex> rl(g_edreg_mu);
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!slots) { g_err = "null pointer"; return SBV_EINVAL; }
+    for (size_t i = 0; i < m; ++i)
+        if (slots[i] >= c.ed_nkeys) { g_err = "sbv_ed25519_widen_keys: unregistered slot"; return SBV_EINVAL; }
+    // the slots that get a comb now: registered, a point, not wide yet, within the cap (the others stay narrow: no error)
+    std::vector<u32> todo;
+    for (size_t i = 0; i < m; ++i) {
+        const u32 s = slots[i];
+        if (!g_edreg.valid[s]) continue;
+        if (std::find(c.ed_wide_slots.begin(), c.ed_wide_slots.end(), s) != c.ed_wide_slots.end()) continue;
+        if (std::find(todo.begin(), todo.end(), s) != todo.end()) continue;
+        if (c.ed_wide_slots.size() + todo.size() >= g_edreg.wide_max) break;
+        todo.push_back(s);
+    }
+    if (todo.empty()) return SBV_OK;
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const size_t w0 = c.ed_wide_slots.size();
+    int rc = ed_wide_reserve(c, w0 + todo.size(), g_edreg.wide_max);
+    if (rc != SBV_OK) return rc;
+    std::vector<u32> plist(2 * todo.size());
+    for (size_t i = 0; i < todo.size(); ++i) { plist[2 * i] = todo[i]; plist[2 * i + 1] = (u32)(w0 + i); }
+    u32* d_plist = nullptr;
+    u32* d_tmp = nullptr;
+    const size_t tmp_bytes = (size_t)kEdWideBuildBlocks * 64 * SBV_ED_HOT_TMP_WORDS * sizeof(u32);
+    auto drop = [&] { if (d_plist) (void)hipFree(d_plist); if (d_tmp) (void)hipFree(d_tmp); };
+    if (hipMalloc(&d_plist, plist.size() * sizeof(u32)) != hipSuccess || hipMalloc(&d_tmp, tmp_bytes) != hipSuccess) {
+        drop();
+        (void)hipGetLastError();
+        g_err = "sbv_ed25519_widen_keys: no device memory for the builder";
+        return SBV_ENOMEM;
+    }
+    hipError_t e = hipMemcpy(d_plist, plist.data(), plist.size() * sizeof(u32), hipMemcpyHostToDevice);
+    if (e == hipSuccess && c.busy_valid) e = hipStreamWaitEvent(c.stream, c.busy, 0);
+    if (e == hipSuccess) e = sbv::launch_ed_keyed_widen(d_plist, (u32)todo.size(), c.d_ed_ktab, d_tmp, kEdWideBuildBlocks, c.d_ed_wtab, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    drop();
+    if (e != hipSuccess) return fail(SBV_EDEVICE, "sbv_ed25519_widen_keys: building the combs", e);
+    // publish: a comb is used only once it is complete
+    for (size_t i = 0; i < todo.size(); ++i) {
+        const u32 w = (u32)(w0 + i);
+        e = hipMemcpy(c.d_ed_kwidx + todo[i], &w, sizeof(u32), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            const u32 none = SBV_ED_WIDE_NONE;
+            for (size_t j = 0; j < i; ++j) (void)hipMemcpy(c.d_ed_kwidx + todo[j], &none, sizeof(u32), hipMemcpyHostToDevice);
+            return fail(SBV_EDEVICE, "sbv_ed25519_widen_keys: publish", e);
+        }
+    }
+    c.ed_wide_slots.insert(c.ed_wide_slots.end(), todo.begin(), todo.end());
+    return SBV_OK;
+}
+
+extern "C" int sbv_ed25519_wide_key_stats(uint32_t out[4]) {
+    std::lock_guard<std::mutex> rl(g_edreg_mu);
+    SBV_ENTER(c);
+    if (!c.ready) return SBV_ENOTINIT;
+    if (!out) return SBV_EINVAL;
+    out[0] = (u32)c.ed_wide_slots.size(); out[1] = SBV_ED_HOT_BITS; out[2] = g_edreg.wide_max;
+    out[3] = (u32)(SBV_ED_HOT_COMB_BYTES >> 10);
+    return SBV_OK;
+}
+
+// 1 = the device-resident 16-bit comb of `slot` equals the host builder's comb of -A (build_ed_window_of) entry by entry
+extern "C" int sbv_ed25519_wide_selfcheck(uint32_t slot) {
+    std::lock_guard<std::mutex> rl(g_edreg_mu);
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    size_t w = c.ed_wide_slots.size();
+    for (size_t i = 0; i < c.ed_wide_slots.size(); ++i) if (c.ed_wide_slots[i] == slot) w = i;
+    if (w == c.ed_wide_slots.size()) { g_err = "sbv_ed25519_wide_selfcheck: the slot has no wide comb"; return SBV_EINVAL; }
+    u32 key[8];
+    memcpy(key, g_edreg.keys[slot].data(), 32);
+    sbv::ept A;
+    if (!sbv::ed_decompress(A, key)) return 0;                          // only points are widened
+    sbv::fe25_neg(A.X, A.X);
+    sbv::fe25_neg(A.T, A.T);
+    std::vector<sbv::aniels> want((size_t)SBV_ED_HOT_WINDOWS * SBV_ED_HOT_PER_WINDOW);
+    {
+        std::vector<std::thread> th;
+        for (int j = 0; j < SBV_ED_HOT_WINDOWS; ++j)
+            th.emplace_back([&, j] { sbv::build_ed_window_of(A, SBV_ED_HOT_BITS, j, want.data() + (size_t)j * SBV_ED_HOT_PER_WINDOW); });
+        for (auto& t : th) t.join();
+    }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+    std::vector<uint8_t> got(SBV_ED_HOT_COMB_BYTES);
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), c.d_ed_wtab + w * SBV_ED_HOT_COMB_BYTES, got.size(), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < want.size(); ++e)
+        if (memcmp(got.data() + e * SBV_ED_HOT_PITCH, &want[e], sizeof(sbv::aniels)) != 0) return 0;
+    return 1;
+}
+
+extern "C" int sbv_ed25519_verify_batch_keyed_dev(const void* d_rsk, const void* d_slots, size_t n, void* d_bitmap, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!d_rsk || !d_slots || !d_bitmap || (reinterpret_cast<uintptr_t>(d_rsk) & 15)) { g_err = "null or misaligned device pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (c.ed_nkeys == 0) {           // every slot is out of range: every record is a reject
+        HIP_TRY(SBV_EDEVICE, hipMemsetAsync(d_bitmap, 0, (n + 7) / 8, stream));
+        return SBV_OK;
+    }
+    int rc = ensure_ed_keyed(c, n);
+    if (rc != SBV_OK) return rc;
+    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(stream, c.busy, 0));
+    const uint8_t* src = static_cast<const uint8_t*>(d_rsk);
+    const u32* sl = static_cast<const u32*>(d_slots);
+    uint8_t* dst = static_cast<uint8_t*>(d_bitmap);
+    for (size_t off = 0; off < n; off += kMaxChunk) {
+        const size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
+        if ((rc = enqueue_ed_keyed(c, src + off * SBV_ED_REC_BYTES, sl + off, m, dst + off / 8, stream)) != SBV_OK) {
+            if (hipEventRecord(c.busy, stream) == hipSuccess) c.busy_valid = true;
+            return rc;
+        }
+    }
+    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.busy, stream));
+    c.busy_valid = true;
+    return SBV_OK;
+}
+
+extern "C" int sbv_ed25519_verify_batch_keyed(const uint8_t* rsk, const uint32_t* slots, size_t n, uint8_t* accept_bitmap) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!rsk || !slots || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (c.ed_nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_ed_keyed(c, n);
+    if (rc != SBV_OK) return rc;
+    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(c.stream, c.busy, 0));
+    sbv_timing tm{};
+    tm.n = n;
+    for (size_t off = 0; off < n; off += kMaxChunk) {
+        const size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
+        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[0], c.stream));
+        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, rsk + off * SBV_ED_REC_BYTES, m * SBV_ED_REC_BYTES, hipMemcpyHostToDevice, c.stream));
+        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots + off, m * sizeof(u32), hipMemcpyHostToDevice, c.stream));
+        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[1], c.stream));
+        if ((rc = enqueue_ed_keyed(c, c.d_tuples, c.d_slots, m, c.d_bitmap, c.stream)) != SBV_OK) return rc;
+        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[3], c.stream));
+        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.h_bitmap, c.d_bitmap, (m + 7) / 8, hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[4], c.stream));
+        HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(c.stream));
+        memcpy(accept_bitmap + off / 8, c.h_bitmap, (m + 7) / 8);
+        tm.h2d_us += 1e3 * ms_between(c.ev[0], c.ev[1]);
+        tm.verify_us += 1e3 * ms_between(c.ev[1], c.ev[3]);
+        tm.d2h_us += 1e3 * ms_between(c.ev[3], c.ev[4]);
+    }
+    c.busy_valid = false;
+    tm.total_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    c.timing = tm;
+    return SBV_OK;
+}
+
+extern "C" int sbv_ed25519_verify_msgs_keyed(const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                             const uint32_t* slots, size_t n, uint8_t* accept_bitmap) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!sigs || !slots || !msg_offsets || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
+    if (msg_offsets[0] != 0) { g_err = "offset tables must start at 0"; return SBV_EINVAL; }
+    for (size_t i = 0; i < n; ++i)
+        if (msg_offsets[i + 1] < msg_offsets[i]) { g_err = "offset table is not monotone"; return SBV_EINVAL; }
+    const size_t mbytes = (size_t)msg_offsets[n];
+    if (mbytes && !msgs) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (c.ed_nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_ed_keyed(c, n);
+    if (rc != SBV_OK) return rc;
+    if ((rc = grow(c.d_msgs, c.msgs_cap, mbytes + 16)) != SBV_OK) return rc;
+    if ((rc = grow(c.d_sigs, c.sigs_cap, n * 64 + 16)) != SBV_OK) return rc;
+    if ((rc = grow(c.d_moff, c.moff_cap, n + 1)) != SBV_OK) return rc;
+    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(c.stream, c.busy, 0));
+    sbv_timing tm{};
+    tm.n = n;
+    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[0], c.stream));
+    if (mbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_msgs, msgs, mbytes, hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs, sigs, n * 64, hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_moff, msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots, n * sizeof(u32), hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[1], c.stream));
+    HIP_TRY(SBV_EDEVICE, sbv::launch_ed_keyed_msg_frontend(c.d_sigs, c.d_slots, ed_reg_view(c), c.d_msgs, c.d_moff, n,
+                                                           reinterpret_cast<uint8_t*>(c.d_qtab), c.stream));
+    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[2], c.stream));
+    if ((rc = enqueue_ed_keyed(c, nullptr, c.d_slots, n, c.d_bitmap, c.stream, true)) != SBV_OK) return rc;
     HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[3], c.stream));
     HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.h_bitmap, c.d_bitmap, (n + 7) / 8, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[4], c.stream));

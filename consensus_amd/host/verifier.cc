@@ -152,6 +152,26 @@ class SbvBackend : public Backend {
         if (rc_ != SBV_OK) return rc_;
         return sbv_ed25519_verify_batch(tuples128, n, bitmap);
     }
+    long register_key_ed25519(const uint8_t a[32]) override {
+        if (rc_ != SBV_OK) return -1;
+        uint32_t slot = 0;
+        return sbv_ed25519_register_keys(a, 1, &slot) == SBV_OK ? (long)slot : -1;
+    }
+    void widen_key_ed25519(long slot) override {
+        if (rc_ != SBV_OK || slot < 0) return;
+        const uint32_t s = (uint32_t)slot;
+        (void)sbv_ed25519_widen_keys(&s, 1);           // best effort: without its 16-bit comb the key keeps the 8-bit one
+    }
+    int verify_ed25519_keyed(const uint8_t* rsk, const uint32_t* slots, size_t n, uint8_t* bitmap) override {
+        if (rc_ != SBV_OK) return rc_;
+        return sbv_ed25519_verify_batch_keyed(rsk, slots, n, bitmap);
+    }
+    int verify_ed25519_msgs_keyed(const uint8_t* sigs, const uint8_t* msgs, const uint64_t* moff, const uint32_t* slots, size_t n,
+                                  uint8_t* bitmap) override {
+        if (rc_ != SBV_OK) return rc_;
+        if (n > ((size_t)1 << 21)) return -2;          // beyond the entry's limit: the caller takes the tuple path
+        return sbv_ed25519_verify_msgs_keyed(sigs, msgs, moff, slots, n, bitmap);
+    }
     int verify_k256(const uint8_t* tuples, size_t n, uint8_t* bitmap) override {
         if (rc_ != SBV_OK) return rc_;
         return sbv_secp256k1_verify_batch(tuples, n, bitmap);
@@ -222,9 +242,58 @@ class CallbackBackend : public Backend {
         std::lock_guard<std::mutex> lk(mu_);
         if ((size_t)slot < keys_.size() && std::find(widened_.begin(), widened_.end(), slot) == widened_.end()) widened_.push_back(slot);
     }
-    uint64_t widened_keys() override { std::lock_guard<std::mutex> lk(mu_); return widened_.size(); }
+    uint64_t widened_keys() override { std::lock_guard<std::mutex> lk(mu_); return widened_.size() + ed_widened_.size(); }
     // the stand-in knows which scheme its test runs: the same callback receives the 128-byte tuples
     int verify_ed25519(const uint8_t* tuples128, size_t n, uint8_t* bitmap) override { return fn_(tuples128, n, bitmap, user_); }
+    // stand-in for the Ed25519 registry: slots index a host-side list of encodings (keyed by the bytes, like the library); the keyed
+    // forms rebuild the 128-byte tuples and go through the same callback, an out-of-range slot is a reject
+    long register_key_ed25519(const uint8_t a[32]) override {
+        if (!registry_) return -1;
+        std::lock_guard<std::mutex> lk(mu_);
+        const std::string k((const char*)a, 32);
+        for (size_t i = 0; i < ed_keys_.size(); ++i) if (ed_keys_[i] == k) return (long)i;
+        ed_keys_.push_back(k);
+        return (long)ed_keys_.size() - 1;
+    }
+    void widen_key_ed25519(long slot) override {
+        if (!registry_ || slot < 0) return;
+        std::lock_guard<std::mutex> lk(mu_);
+        if ((size_t)slot < ed_keys_.size() && std::find(ed_widened_.begin(), ed_widened_.end(), slot) == ed_widened_.end()) ed_widened_.push_back(slot);
+    }
+    int verify_ed25519_keyed(const uint8_t* rsk, const uint32_t* slots, size_t n, uint8_t* bitmap) override {
+        if (!registry_) return -2;
+        std::vector<uint8_t> tuples(n * 128, 0);
+        std::vector<uint8_t> known(n, 0);
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            ++keyed_batches_;
+            for (size_t i = 0; i < n; ++i) {
+                memcpy(&tuples[i * 128], rsk + i * 96, 64);
+                memcpy(&tuples[i * 128 + 96], rsk + i * 96 + 64, 32);
+                if (slots[i] < ed_keys_.size()) { memcpy(&tuples[i * 128 + 64], ed_keys_[slots[i]].data(), 32); known[i] = 1; }
+            }
+        }
+        const int rc = fn_(tuples.data(), n, bitmap, user_);
+        for (size_t i = 0; i < n; ++i) if (!known[i]) bitmap[i >> 3] &= (uint8_t)~(1u << (i & 7));
+        return rc;
+    }
+    int verify_ed25519_msgs_keyed(const uint8_t* sigs, const uint8_t* msgs, const uint64_t* moff, const uint32_t* slots, size_t n,
+                                  uint8_t* bitmap) override {
+        if (!registry_) return -2;
+        std::vector<uint8_t> rsk(n * 96, 0);
+        std::vector<std::string> keys(n);
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            for (size_t i = 0; i < n; ++i) if (slots[i] < ed_keys_.size()) keys[i] = ed_keys_[slots[i]];
+        }
+        parallel_chunks(n, [&](size_t lo, size_t hi) {
+            for (size_t i = lo; i < hi; ++i) {
+                memcpy(&rsk[i * 96], sigs + i * 64, 64);
+                if (!keys[i].empty()) ed25519_hram(sigs + i * 64, (const uint8_t*)keys[i].data(), (const char*)msgs + moff[i], (size_t)(moff[i + 1] - moff[i]), &rsk[i * 96 + 64]);
+            }
+        });
+        return verify_ed25519_keyed(rsk.data(), slots, n, bitmap);
+    }
     int verify_k256(const uint8_t* tuples, size_t n, uint8_t* bitmap) override { return fn_(tuples, n, bitmap, user_); }
  private:
     backend_fn fn_;
@@ -233,6 +302,8 @@ class CallbackBackend : public Backend {
     std::vector<long> widened_;
     std::mutex mu_;
     std::vector<std::string> keys_;
+    std::vector<std::string> ed_keys_;
+    std::vector<long> ed_widened_;
     uint64_t keyed_batches_ = 0;
 };
 }  // namespace
@@ -324,6 +395,17 @@ int Coalescer::submit_many_ed25519(const uint8_t* tuples128, size_t n, uint8_t* 
         if (n > st_.max_batch) st_.max_batch = n;
     }
     return be_->verify_ed25519(tuples128, n, bitmap);
+}
+
+int Coalescer::submit_many_ed25519_msgs_keyed(const uint8_t* sigs, const uint8_t* msgs, const uint64_t* moff, const uint32_t* slots, size_t n,
+                                              uint8_t* bitmap) {
+    const int rc = be_->verify_ed25519_msgs_keyed(sigs, msgs, moff, slots, n, bitmap);
+    if (rc != -2) {
+        std::lock_guard<SpinLock> lk(mu_);
+        ++st_.batches;
+        if (n > st_.max_batch) st_.max_batch = n;
+    }
+    return rc;
 }
 
 int Coalescer::submit_many_k256(const uint8_t* tuples, size_t n, uint8_t* bitmap) {
@@ -435,9 +517,22 @@ void Coalescer::serve_as_leader(const std::atomic<bool>* own_done) {
         for (size_t i = 0; i < n; ++i) all_keyed = all_keyed && batch[i]->slot >= 0;
         int rc;
         if (batch[0]->ed25519) {         // Ed25519 Verifier: 128-byte tuples
-            tuples.resize(n * 128);
-            for (size_t i = 0; i < n; ++i) memcpy(&tuples[i * 128], batch[i]->tuple, 128);
-            rc = be_->verify_ed25519(tuples.data(), n, bitmap.data());
+            rc = -2;
+            if (all_keyed) {             // a commit burst of registered consenters: records R|S|k + slots, A from the device registry
+                tuples.resize(n * 96);
+                std::vector<uint32_t> slots(n);
+                for (size_t i = 0; i < n; ++i) {
+                    memcpy(&tuples[i * 96], batch[i]->tuple, 64);
+                    memcpy(&tuples[i * 96 + 64], batch[i]->tuple + 96, 32);
+                    slots[i] = (uint32_t)batch[i]->slot;
+                }
+                rc = be_->verify_ed25519_keyed(tuples.data(), slots.data(), n, bitmap.data());
+            }
+            if (rc == -2) {
+                tuples.resize(n * 128);
+                for (size_t i = 0; i < n; ++i) memcpy(&tuples[i * 128], batch[i]->tuple, 128);
+                rc = be_->verify_ed25519(tuples.data(), n, bitmap.data());
+            }
         } else if (batch[0]->k256) {     // secp256k1 Verifier: the same 160-byte tuples, the other curve
             tuples.resize(n * 160);
             for (size_t i = 0; i < n; ++i) memcpy(&tuples[i * 160], batch[i]->tuple, 160);
@@ -517,8 +612,10 @@ void* Verifier::staging(Staging& s, size_t bytes) {
 }
 
 void Verifier::RegisterConsenter(uint64_t id, const uint8_t* q) {
-    const long slot = ed() || k256() ? -1 : co_.backend().register_key(q);     // -1: no key registry (Ed25519: grouped per batch; secp256k1: no combs yet)
-    if (slot >= 0) co_.backend().widen_key(slot);      // consenters sign every vote of the epoch: 16 comb additions per u2 * Q instead of 32
+    // -1: no key registry (secp256k1: no combs yet; a backend without one).  Ed25519 keys take the scheme's own registry.
+    const long slot = k256() ? -1 : ed() ? co_.backend().register_key_ed25519(q) : co_.backend().register_key(q);
+    if (slot >= 0 && ed()) co_.backend().widen_key_ed25519(slot);     // 16 comb additions per [k](-A) instead of 32
+    else if (slot >= 0) co_.backend().widen_key(slot);      // consenters sign every vote of the epoch: 16 comb additions per u2 * Q instead of 32
     bytes key((const char*)q, key_bytes());
     key.resize(64, '\0');
     std::lock_guard<SpinLock> lk(mu_);
@@ -535,7 +632,7 @@ void Verifier::RegisterConsenter(uint64_t id, const uint8_t* q) {
 void Verifier::RegisterClient(const std::string& client_id, const uint8_t* q) {
     bool on_device;
     { std::lock_guard<SpinLock> lk(mu_); on_device = opt_.device_client_keys; }
-    const long slot = ed() || k256() || !on_device ? -1 : co_.backend().register_key(q);     // -1: no key registry (Ed25519: grouped per batch; secp256k1: no combs yet)
+    const long slot = k256() || !on_device ? -1 : ed() ? co_.backend().register_key_ed25519(q) : co_.backend().register_key(q);     // -1: no key registry
     bytes key((const char*)q, key_bytes());
     key.resize(64, '\0');
     std::lock_guard<SpinLock> lk(mu_);
@@ -619,7 +716,7 @@ Status Verifier::verify_one(const uint8_t q[64], const bytes& msg, const bytes& 
     if (ed()) make_tuple_ed25519(q, msg, sig, t);
     else make_tuple(q, msg, sig, t);
     std::string err;
-    const int r = co_.submit(t, ed() || k256() ? -1 : slot, ed(), k256(), &err);
+    const int r = co_.submit(t, k256() ? -1 : slot, ed(), k256(), &err);
     if (r < 0) return Status::Unavailable("backend error: " + err);
     if (opt_.cache_verified) {
         std::lock_guard<SpinLock> lk(cache_mu_);
@@ -828,6 +925,24 @@ Status Verifier::VerifyProposal(const Proposal& p, std::vector<RequestInfo>* req
                 }
             });
             rc = co_.submit_many_msgs_keyed(mbuf, moff, sbuf, soff, dslots, n, bitmap.data());
+        }
+        if (ed() && !unkeyed.load()) {
+            // Ed25519, every client registered: 64-byte signatures + signed bytes + slots; SHA-512(R | A | M) runs on the device with A
+            // from the registry.  A signature that is not 64 bytes is the caller's reject: S = 2^256 - 1.
+            std::vector<uint8_t> sbuf(n * 64);
+            std::vector<uint64_t> moff(n + 1);
+            uint64_t a = 0;
+            for (size_t i = 0; i < n; ++i) { moff[i] = a; a += views[i].signed_len; }
+            moff[n] = a;
+            std::vector<uint8_t> mbuf(a + 1);
+            parallel_chunks(n, [&](size_t lo, size_t hi) {
+                for (size_t i = lo; i < hi; ++i) {
+                    memcpy(&mbuf[moff[i]], pl.data() + views[i].signed_off, views[i].signed_len);
+                    if (views[i].sig_len == 64) memcpy(&sbuf[i * 64], pl.data() + views[i].sig_off, 64);
+                    else { memset(&sbuf[i * 64], 0, 32); memset(&sbuf[i * 64 + 32], 0xFF, 32); }
+                }
+            });
+            rc = co_.submit_many_ed25519_msgs_keyed(sbuf.data(), mbuf.data(), moff.data(), slots.data(), n, bitmap.data());
         }
         if (rc == -2) {
             // no front end, unregistered clients or another scheme: tuples built by the host workers (SHA-256, strict DER)

@@ -56,6 +56,19 @@ class Backend {
     virtual void host_free(void* p) { (void)p; }
     // Ed25519 variant (include/sbv.h: sbv_ed25519_verify_batch): n tuples of 128 bytes R|S|A|k.  -2 when unsupported.
     virtual int verify_ed25519(const uint8_t* tuples128, size_t n, uint8_t* bitmap) { (void)tuples128; (void)n; (void)bitmap; return -2; }
+    // Registered Ed25519 keys (include/sbv.h: sbv_ed25519_register_keys): a slot >= 0 for the 32-byte encoding, or -1 when the backend
+    // has no Ed25519 registry (callers then keep A in the 128-byte tuple).  widen_key_ed25519: a 16-bit comb for a consenter's slot.
+    virtual long register_key_ed25519(const uint8_t a[32]) { (void)a; return -1; }
+    virtual void widen_key_ed25519(long slot) { (void)slot; }
+    // n records of 96 bytes R|S|k + slots (sbv_ed25519_verify_batch_keyed); -2 when unsupported
+    virtual int verify_ed25519_keyed(const uint8_t* rsk, const uint32_t* slots, size_t n, uint8_t* bitmap) {
+        (void)rsk; (void)slots; (void)n; (void)bitmap; return -2;
+    }
+    // n signatures of 64 bytes + raw messages + slots, k hashed by the backend (sbv_ed25519_verify_msgs_keyed); -2 when unsupported
+    virtual int verify_ed25519_msgs_keyed(const uint8_t* sigs, const uint8_t* msgs, const uint64_t* moff, const uint32_t* slots, size_t n,
+                                          uint8_t* bitmap) {
+        (void)sigs; (void)msgs; (void)moff; (void)slots; (void)n; (void)bitmap; return -2;
+    }
     // secp256k1 variant (include/sbv.h: sbv_secp256k1_verify_batch): n tuples of 160 bytes, same layout as verify().  -2 when unsupported.
     virtual int verify_k256(const uint8_t* tuples, size_t n, uint8_t* bitmap) { (void)tuples; (void)n; (void)bitmap; return -2; }
     virtual int verify_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* bitmap) {
@@ -116,6 +129,7 @@ class Coalescer {
     // thread, and the failing call ran there, not on the submitter)
     int submit(const uint8_t tuple[160], long slot = -1, bool ed25519 = false, bool k256 = false, std::string* err = nullptr);
     int submit_many_ed25519(const uint8_t* tuples128, size_t n, uint8_t* bitmap);
+    int submit_many_ed25519_msgs_keyed(const uint8_t* sigs, const uint8_t* msgs, const uint64_t* moff, const uint32_t* slots, size_t n, uint8_t* bitmap);
     int submit_many_k256(const uint8_t* tuples, size_t n, uint8_t* bitmap);
     int submit_many(const uint8_t* tuples, size_t n, uint8_t* bitmap);
     int submit_many_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* bitmap);

@@ -27,7 +27,8 @@ const (
 //
 //	Pub   the P-256 key (SchemeP256)
 //	Key   the raw key bytes of the other schemes: 32-byte Ed25519 key, or 64 bytes Qx|Qy big-endian for secp256k1
-//	Slot  >= 0 when the key is registered with the device (sbv_p256_register_keys); -1 otherwise
+//	Slot  >= 0 when the key is registered with the device (sbv_p256_register_keys, or sbv_ed25519_register_keys under
+//	      SchemeEd25519); -1 otherwise
 type Item struct {
 	Pub  *ecdsa.PublicKey
 	Key  []byte
@@ -59,6 +60,15 @@ type Backend interface {
 	// A backend without batch signing returns ErrNoBatchSigner and the Signer signs one by one with crypto/ecdsa.
 	SignBatch(keys [][32]byte, keyIndex []uint32, digests [][32]byte) (sigs [][64]byte, ok []bool, err error)
 	Close()
+}
+
+// EdKeyRegistry is the optional Ed25519 key registry of a backend (sbv_ed25519_register_keys): RegisterKeyEd25519 gives the
+// device a 32-byte key it will see again and returns its slot (-1 when there is no registry: the key then travels inline);
+// WidenKeyEd25519 gives a consenter's slot a 16-bit comb (sbv_ed25519_widen_keys: [k](-A) in 16 additions instead of 32).
+// Slots are keyed by the encoding's bytes.  An optional interface, so that backends without it need no change.
+type EdKeyRegistry interface {
+	RegisterKeyEd25519(key []byte) int32
+	WidenKeyEd25519(slot int32)
 }
 
 // ErrNoBatchSigner: the backend has no batch signing entry (the pure-Go backend).

@@ -36,11 +36,13 @@ const (
 //	every item has a slot, n >= frontEndFrom   sbv_p256_verify_msgs_keyed   raw messages + DER + slots (SHA-256 and DER on the device)
 //	every item has a slot                      sbv_p256_verify_batch_keyed  96-byte r|s|hash records + slots
 //	otherwise                                  sbv_p256_verify_batch_sharded generic tuples, all GPUs of the node
+//	SchemeEd25519, every item has a slot       sbv_ed25519_verify_msgs_keyed  signatures + raw messages + slots (SHA-512 on the device)
 //	SchemeEd25519 / SchemeSecp256k1            sbv_ed25519_verify_msgs / sbv_secp256k1_verify_batch
 type gpuBackend struct {
-	jobs chan *gpuJob
-	mu   sync.Mutex
-	regs map[[64]byte]int32
+	jobs   chan *gpuJob
+	mu     sync.Mutex
+	regs   map[[64]byte]int32
+	edRegs map[[32]byte]int32 // the Ed25519 registry's slots (sbv_ed25519_register_keys), by encoding
 }
 
 type gpuJob struct {
@@ -50,7 +52,7 @@ type gpuJob struct {
 
 // NewDeviceBackend initialises every visible MI355X (sbv_init_all).
 func NewDeviceBackend() (Backend, error) {
-	b := &gpuBackend{jobs: make(chan *gpuJob, 64), regs: map[[64]byte]int32{}}
+	b := &gpuBackend{jobs: make(chan *gpuJob, 64), regs: map[[64]byte]int32{}, edRegs: map[[32]byte]int32{}}
 	ready := make(chan error, 1)
 	go b.loop(ready)
 	if err := <-ready; err != nil {
@@ -205,9 +207,52 @@ func (b *gpuBackend) verifyP256(items []Item) ([]bool, error) {
 	return bitmapToBools(bitmap, n), nil
 }
 
+// verifyEd25519Keyed: every item's key is registered (sbv_ed25519_verify_msgs_keyed): signatures n x 64, messages packed and
+// slots; k = SHA-512(R | A | M) mod L runs on the device with A from the registry.  A signature of the wrong length is this
+// layer's reject: it travels as S = 2^256 - 1, which the device rejects.
+func (b *gpuBackend) verifyEd25519Keyed(items []Item) ([]bool, error) {
+	n := len(items)
+	ok := make([]bool, n)
+	for lo := 0; lo < n; lo += frontEndMax {
+		hi := lo + frontEndMax
+		if hi > n {
+			hi = n
+		}
+		m := hi - lo
+		sigs := make([]byte, 64*m)
+		slots := make([]uint32, m)
+		for k := 0; k < m; k++ {
+			it := &items[lo+k]
+			if len(it.Sig) == 64 {
+				copy(sigs[64*k:], it.Sig)
+			} else {
+				for j := 32; j < 64; j++ {
+					sigs[64*k+j] = 0xFF
+				}
+			}
+			slots[k] = uint32(it.Slot)
+		}
+		msgs, moff := packMsgs(func(k int) []byte { return items[lo+k].Msg }, m)
+		bitmap := make([]byte, (m+7)/8)
+		rc := C.sbv_ed25519_verify_msgs_keyed(u8(sigs), u8(msgs), (*C.uint64_t)(unsafe.Pointer(&moff[0])),
+			(*C.uint32_t)(unsafe.Pointer(&slots[0])), C.size_t(m), u8(bitmap))
+		if rc != 0 {
+			return nil, lastError()
+		}
+		for k := 0; k < m; k++ {
+			ok[lo+k] = len(items[lo+k].Sig) == 64 && bitmap[k>>3]>>(uint(k)&7)&1 == 1
+		}
+	}
+	return ok, nil
+}
+
 // verifyEd25519: signatures n x 64, keys n x 32, messages packed; SHA-512 and the reduction mod L run on the device.
 // A signature or key of the wrong length is this layer's reject (crypto/ed25519.Verify returns false / panics on them).
+// When every item's key has a registry slot the keyed entry takes the batch (verifyEd25519Keyed).
 func (b *gpuBackend) verifyEd25519(items []Item) ([]bool, error) {
+	if allSlotted(items) {
+		return b.verifyEd25519Keyed(items)
+	}
 	n := len(items)
 	ok := make([]bool, n)
 	idx := make([]int, 0, n)
@@ -313,6 +358,48 @@ func (b *gpuBackend) WidenKey(slot int32) {
 		var s C.uint32_t
 		s = C.uint32_t(slot)
 		C.sbv_p256_widen_keys(&s, C.size_t(1))
+	})
+}
+
+// RegisterKeyEd25519 builds the key's 8-bit comb of -A on the device once (sbv_ed25519_register_keys: 384 KiB of HBM per key)
+// and remembers the slot; registering the same bytes again returns the same slot.  -1 when the device refuses (the key then
+// travels inline).
+func (b *gpuBackend) RegisterKeyEd25519(key []byte) int32 {
+	if len(key) != 32 {
+		return -1
+	}
+	var k [32]byte
+	copy(k[:], key)
+	b.mu.Lock()
+	if s, hit := b.edRegs[k]; hit {
+		b.mu.Unlock()
+		return s
+	}
+	b.mu.Unlock()
+	slot := int32(-1)
+	b.on(func() {
+		var out C.uint32_t
+		if rc := C.sbv_ed25519_register_keys(u8(key), 1, &out); rc == 0 {
+			slot = int32(out)
+		}
+	})
+	if slot >= 0 {
+		b.mu.Lock()
+		b.edRegs[k] = slot
+		b.mu.Unlock()
+	}
+	return slot
+}
+
+// WidenKeyEd25519: sbv_ed25519_widen_keys for one slot (best effort: a slot without a 16-bit comb keeps its 8-bit one).
+func (b *gpuBackend) WidenKeyEd25519(slot int32) {
+	if slot < 0 {
+		return
+	}
+	b.on(func() {
+		var s C.uint32_t
+		s = C.uint32_t(slot)
+		C.sbv_ed25519_widen_keys(&s, C.size_t(1))
 	})
 }
 

@@ -141,10 +141,25 @@ func (v *Verifier) RegisterClient(clientID string, pub *ecdsa.PublicKey) {
 }
 
 // RegisterConsenterRaw / RegisterClientRaw: the registry for SchemeEd25519 (32-byte keys) and SchemeSecp256k1 (64 bytes
-// Qx|Qy big-endian); no device slots for these schemes (the device groups by key inside each batch).
+// Qx|Qy big-endian).  Under SchemeEd25519 a backend with an Ed25519 registry (EdKeyRegistry: sbv_ed25519_register_keys) gives
+// the key a device slot — consenters' slots also a 16-bit comb — and batches whose signers all have slots take the keyed
+// entry; secp256k1 keys have no device slots (the device groups by key inside each batch).
+func (v *Verifier) edSlot(key []byte, consenter bool) int32 {
+	reg, has := v.backend.(EdKeyRegistry)
+	if v.opt.Scheme != SchemeEd25519 || !has || len(key) != 32 {
+		return -1
+	}
+	slot := reg.RegisterKeyEd25519(key)
+	if slot >= 0 && consenter {
+		reg.WidenKeyEd25519(slot)
+	}
+	return slot
+}
+
 func (v *Verifier) RegisterConsenterRaw(id uint64, key []byte) {
+	slot := v.edSlot(key, true)
 	v.mu.Lock()
-	v.consenters[id] = regKey{raw: append([]byte(nil), key...), slot: -1}
+	v.consenters[id] = regKey{raw: append([]byte(nil), key...), slot: slot}
 	n := len(v.consenters)
 	v.mu.Unlock()
 	if n > 1 {
@@ -153,8 +168,12 @@ func (v *Verifier) RegisterConsenterRaw(id uint64, key []byte) {
 }
 
 func (v *Verifier) RegisterClientRaw(clientID string, key []byte) {
+	slot := int32(-1)
+	if v.opt.DeviceClientKeys {
+		slot = v.edSlot(key, false)
+	}
 	v.mu.Lock()
-	v.clients[clientID] = regKey{raw: append([]byte(nil), key...), slot: -1}
+	v.clients[clientID] = regKey{raw: append([]byte(nil), key...), slot: slot}
 	v.mu.Unlock()
 }
 

@@ -202,6 +202,41 @@ int sbv_ed25519_make_tuples(const uint8_t* sigs, const uint8_t* pks, const uint8
 int sbv_ed25519_verify_msgs(const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* msg_offsets,
                             size_t n, uint8_t* accept_bitmap);
 
+/* Registered Ed25519 keys: the consenters' (and registered clients') keys get a slot once, after which a verification against
+ * that key needs no doublings and no grouping work: [S]B from the comb of B plus [k](-A) in 32 additions from the slot's 8-bit
+ * comb of -A (384 KiB of HBM per key), or in 16 from a 16-bit comb after sbv_ed25519_widen_keys (64 MiB per key).  Four launches
+ * per call: records -> tuples (A from the registry), [S]B, [k](-A), the encoding check (consensus_amd/csrc/ed25519_keyed.h).
+ *   pks: m x 32 bytes (the encoded A).  slots_out[i] = slot of pks[i].  Slots are keyed by the encoding's BYTES, not by the point:
+ *     k hashes the bytes, so two encodings of one point get two slots; equal encodings share one.  An encoding that Go's
+ *     edwards25519 Point.SetBytes refuses still gets a slot, flagged invalid: every signature against it is rejected.  At most
+ *     65 536 keys (SBV_EINVAL beyond).  Nothing is allocated before the first registration.
+ *   sbv_ed25519_wide_keys: cap on the slots with a 16-bit comb (0 = none; default 64 = 4 GiB; at most 4096); lowering it
+ *     returns the slots beyond the cap to their 8-bit combs.  sbv_ed25519_widen_keys: 16-bit combs for the named slots, built on
+ *     the device from their 8-bit combs; a slot that is wide already, is not a point or lies beyond the cap stays as it is (no
+ *     error); an unregistered slot is SBV_EINVAL.  stats: out[0] = wide slots, out[1] = 16 (bits), out[2] = the cap,
+ *     out[3] = KiB per wide comb.  sbv_ed25519_wide_selfcheck(slot) = 1 when the device comb equals the host builder's byte
+ *     for byte, 0 when it differs, SBV_EINVAL when the slot has no wide comb.
+ *   rsk: n x 96 bytes R | S | k, little-endian: the 128-byte tuple without A, with k = SHA-512(R || A || M) mod L over the
+ *     registered encoding.  slots: n slots.  A wavefront whose signatures all belong to wide slots walks the 16-bit combs, any
+ *     other the 8-bit combs every slot keeps; verdicts are bit-identical to sbv_ed25519_verify_batch on the equivalent tuples.
+ *     An out-of-range slot, S >= L or k >= L is a reject, not an error; len(sig) != 64 is the caller's reject (S = 2^256 - 1).
+ *     _dev: d_rsk 16-byte aligned, on `hip_stream`, the caller synchronises.
+ *   sbv_ed25519_verify_msgs_keyed: sigs n x 64 (R | S), message i = msgs[msg_offsets[i] .. msg_offsets[i+1]), signer slots[i]; k is
+ *     computed on the device from the registry's encoding; n <= 2^21.
+ * A failed registration or widening (SBV_ENOMEM, SBV_EDEVICE) leaves the registry as it was.  These entries run on the default
+ * context (registry replication to other devices is not provided); sbv_shutdown forgets the registry. */
+int sbv_ed25519_register_keys(const uint8_t* pks, size_t m, uint32_t* slots_out);
+int sbv_ed25519_key_count(void);
+int sbv_ed25519_clear_keys(void);
+int sbv_ed25519_wide_keys(uint32_t max_keys);
+int sbv_ed25519_widen_keys(const uint32_t* slots, size_t m);
+int sbv_ed25519_wide_key_stats(uint32_t out[4]);
+int sbv_ed25519_wide_selfcheck(uint32_t slot);
+int sbv_ed25519_verify_batch_keyed(const uint8_t* rsk, const uint32_t* slots, size_t n, uint8_t* accept_bitmap);
+int sbv_ed25519_verify_batch_keyed_dev(const void* d_rsk, const void* d_slots, size_t n, void* d_bitmap, void* hip_stream);
+int sbv_ed25519_verify_msgs_keyed(const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                  const uint32_t* slots, size_t n, uint8_t* accept_bitmap);
+
 /* Strict DER parse of an ECDSA-Sig-Value with Go x/crypto/cryptobyte rules
  * (crypto/ecdsa.parseSignature): out = r | s, 32 bytes each, big-endian, zero padded.
  * Returns SBV_OK or SBV_EPARSE (then out is all zero, which every verify rejects). */
