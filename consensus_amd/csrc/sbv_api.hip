@@ -676,11 +676,10 @@ int enqueue_ed25519(Context& c, const uint8_t* d_tuples, size_t n, uint8_t* d_bi
 // decide_n: the batch size the grouped / one-lane decision is taken on (0 = n).  A key-affine part holds 1 / G of a batch's
 // tuples but each of its keys as often as the whole batch does: it groups whenever the whole batch would.
 int enqueue(Context& c, const uint8_t* d_tuples, size_t n, uint8_t* d_bitmap, hipStream_t stream,
-            hipEvent_t after_prep, hipEvent_t* dom = nullptr, int* dom_pairs = nullptr, bool* was_grouped = nullptr, size_t decide_n = 0) {
+            hipEvent_t after_prep, hipEvent_t* dom = nullptr, int* dom_pairs = nullptr, size_t decide_n = 0) {
     const sbv::Scratch s = scratch_view(c);
     bool grouped = c.group_enabled && (decide_n ? decide_n : n) >= (c.kc_on[0] ? c.group_min_batch : c.group_min_batch_cold);
     if (grouped && !group_buffers_or_fallback(c, n, [&] { return ensure_group_buffers(c, n); }, grouped)) return g_last_rc;
-    if (was_grouped) *was_grouped = grouped;
     if (grouped) {
         // Below 2^18 tuples the step is latency: one straggling tuple in the one-lane doubling kernel (2.3 ms) outlasts the
         // whole table pipeline (1.7 ms at 1024 cold keys).  A threshold of 64 uses, counted on every 8th tuple, loses 3 % of
@@ -783,6 +782,102 @@ double ms_between(hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return 0.0;
     return ms;
+}
+
+// The chunk loop of the device-pointer verify entries: c.mu held, the device current, the scheme's tables ensured.
+// step(off, m, after_prep, dom, dom_pairs) enqueues tuples [off, off + m) on `stream`.  Profiling (include/sbv.h:
+// sbv_profile_enable): at level 1 each chunk is bracketed by an event triple, whose middle event the step records after its
+// stage A (a step without one, stage_a false, has it recorded at its start); at levels 1 and 2 the step may record up to
+// SBV_GROUP_MAX_CHUNKS event pairs around the launches of its dominant kernel and reports how many.
+template <class Step>
+int run_chunks_dev(Context& c, size_t n, hipStream_t stream, bool stage_a, Step&& step) {
+    int rc = ensure_capacity(c, n < kMaxChunk ? n : kMaxChunk);
+    if (rc != SBV_OK) return rc;
+    // the scratch is single-flight: order this call after the previous one even across streams
+    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(stream, c.busy, 0));
+    auto chunk = [&](size_t off, size_t m) -> int {
+        hipEvent_t mid = nullptr, end = nullptr;
+        if (c.profiling == 1) {
+            if (c.prof_used + 3 > c.prof_events.size())
+                for (int k = 0; k < 3; ++k) { hipEvent_t ev; HIP_TRY(SBV_EDEVICE, hipEventCreate(&ev)); c.prof_events.push_back(ev); }
+            HIP_TRY(SBV_EDEVICE, hipEventRecord(c.prof_events[c.prof_used], stream));
+            mid = c.prof_events[c.prof_used + 1];
+            end = c.prof_events[c.prof_used + 2];
+            c.prof_used += 3;
+            if (!stage_a) { HIP_TRY(SBV_EDEVICE, hipEventRecord(mid, stream)); mid = nullptr; }
+        }
+        hipEvent_t* dom = nullptr;
+        int dom_pairs = 0;
+        if (c.profiling) {
+            while (c.prof_dom_used + 2 * SBV_GROUP_MAX_CHUNKS > c.prof_dom.size()) { hipEvent_t ev; HIP_TRY(SBV_EDEVICE, hipEventCreate(&ev)); c.prof_dom.push_back(ev); }
+            dom = c.prof_dom.data() + c.prof_dom_used;
+        }
+        const int r = step(off, m, mid, dom, &dom_pairs);
+        if (r != SBV_OK) return r;
+        if (c.profiling) c.prof_dom_used += 2 * (size_t)dom_pairs;
+        if (end) HIP_TRY(SBV_EDEVICE, hipEventRecord(end, stream));
+        return SBV_OK;
+    };
+    for (size_t off = 0; off < n && rc == SBV_OK; off += kMaxChunk)       // kMaxChunk is a multiple of 8: whole bitmap bytes
+        rc = chunk(off, n - off < kMaxChunk ? n - off : kMaxChunk);
+    // also on failure: part of a chunk may be enqueued, and later users of the scratch must still wait for it
+    const hipError_t e = hipEventRecord(c.busy, stream);
+    if (e == hipSuccess) c.busy_valid = true;
+    else if (rc == SBV_OK) rc = fail(SBV_EDEVICE, "hipEventRecord(c.busy, stream)", e);
+    return rc;
+}
+
+// The chunk loop of the synchronous host-pointer verify entries, on c.stream: c.mu held, the device current, the scheme's tables
+// and the entry's own staging ensured.  Per chunk of tuples [off, off + m), upload(off, m) enqueues the copies into the context's
+// staging and step(off, m, after_prep) the kernels, which leave the verdicts in c.d_bitmap; after_prep is the event between stage A
+// (or a front end) and stage B when stage_a, else null.  The verdicts land in accept_bitmap + off / 8, the summed event spans in
+// c.timing; total_us runs from the entry's t0.
+template <class Upload, class Step>
+int run_chunks_host(Context& c, size_t n, uint8_t* accept_bitmap, std::chrono::steady_clock::time_point t0, bool stage_a, Upload&& upload,
+                    Step&& step) {
+    int rc = ensure_capacity(c, n < kMaxChunk ? n : kMaxChunk);
+    if (rc != SBV_OK) return rc;
+    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(c.stream, c.busy, 0));
+    sbv_timing tm{};
+    tm.n = n;
+    auto chunk = [&](size_t off, size_t m) -> int {
+        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[0], c.stream));
+        int r = upload(off, m);
+        if (r != SBV_OK) return r;
+        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[1], c.stream));
+        if ((r = step(off, m, stage_a ? c.ev[2] : nullptr)) != SBV_OK) return r;
+        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[3], c.stream));
+        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.h_bitmap, c.d_bitmap, (m + 7) / 8, hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[4], c.stream));
+        HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(c.stream));
+        memcpy(accept_bitmap + off / 8, c.h_bitmap, (m + 7) / 8);
+        tm.h2d_us += 1e3 * ms_between(c.ev[0], c.ev[1]);
+        if (stage_a) tm.prep_us += 1e3 * ms_between(c.ev[1], c.ev[2]);
+        tm.verify_us += 1e3 * ms_between(stage_a ? c.ev[2] : c.ev[1], c.ev[3]);
+        tm.d2h_us += 1e3 * ms_between(c.ev[3], c.ev[4]);
+        return SBV_OK;
+    };
+    for (size_t off = 0; off < n && rc == SBV_OK; off += kMaxChunk)
+        rc = chunk(off, n - off < kMaxChunk ? n - off : kMaxChunk);
+    if (rc != SBV_OK) {          // part of a chunk may be enqueued: later users of the scratch must still wait for it
+        if (hipEventRecord(c.busy, c.stream) == hipSuccess) c.busy_valid = true;
+        return rc;
+    }
+    c.busy_valid = false;
+    tm.total_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    c.timing = tm;
+    return SBV_OK;
+}
+
+// An offset table of the message entries, which the device dereferences: it starts at 0 and never decreases, and its payload is
+// null only when empty.  bytes = the payload's size.
+int check_offsets(const uint64_t* offsets, size_t n, const void* payload, size_t& bytes) {
+    if (offsets[0] != 0) { g_err = "offset tables must start at 0"; return SBV_EINVAL; }
+    for (size_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) { g_err = "offset table is not monotone"; return SBV_EINVAL; }
+    bytes = (size_t)offsets[n];
+    if (bytes && !payload) { g_err = "null pointer"; return SBV_EINVAL; }
+    return SBV_OK;
 }
 
 }  // namespace
@@ -1055,58 +1150,14 @@ extern "C" int sbv_p256_verify_batch_dev(const void* d_tuples, size_t n, void* d
     SBV_ENTER(c);
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (n == 0) return SBV_OK;
-    if (!d_tuples || !d_bitmap || (reinterpret_cast<uintptr_t>(d_tuples) & 15)) {
-        g_err = "null or misaligned device pointer";
-        return SBV_EINVAL;
-    }
+    if (!d_tuples || !d_bitmap || (reinterpret_cast<uintptr_t>(d_tuples) & 15)) { g_err = "null or misaligned device pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    int rc = ensure_capacity(c, n < kMaxChunk ? n : kMaxChunk);
-    if (rc != SBV_OK) return rc;
-    // the scratch is single-flight: order this call after the previous one even across streams
-    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(stream, c.busy, 0));
     const uint8_t* src = static_cast<const uint8_t*>(d_tuples);
     uint8_t* dst = static_cast<uint8_t*>(d_bitmap);
-    for (size_t off = 0; off < n; off += kMaxChunk) {       // kMaxChunk is a multiple of 8
-        const size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
-        hipEvent_t mid = nullptr, end = nullptr;
-        if (c.profiling == 1) {
-            if (c.prof_used + 3 > c.prof_events.size()) {
-                for (int k = 0; k < 3; ++k) {
-                    hipEvent_t ev;
-                    HIP_TRY(SBV_EDEVICE, hipEventCreate(&ev));
-                    c.prof_events.push_back(ev);
-                }
-            }
-            HIP_TRY(SBV_EDEVICE, hipEventRecord(c.prof_events[c.prof_used], stream));
-            mid = c.prof_events[c.prof_used + 1];
-            end = c.prof_events[c.prof_used + 2];
-            c.prof_used += 3;
-        }
-        // event pairs around every launch of the dominant kernel (one per chunk of windows when grouped)
-        hipEvent_t* dom = nullptr;
-        int dom_pairs = 0;
-        if (c.profiling) {
-            while (c.prof_dom_used + 2 * SBV_GROUP_MAX_CHUNKS > c.prof_dom.size()) {
-                hipEvent_t ev;
-                HIP_TRY(SBV_EDEVICE, hipEventCreate(&ev));
-                c.prof_dom.push_back(ev);
-            }
-            dom = c.prof_dom.data() + c.prof_dom_used;
-        }
-        bool was_grouped = false;
-        rc = enqueue(c, src + off * SBV_TUPLE_BYTES, m, dst + off / 8, stream, mid, dom, &dom_pairs, &was_grouped);
-        if (rc != SBV_OK) {          // part of the step may be enqueued: later users of the scratch must still wait for it
-            if (hipEventRecord(c.busy, stream) == hipSuccess) c.busy_valid = true;
-            return rc;
-        }
-        (void)was_grouped;
-        if (c.profiling) c.prof_dom_used += 2 * (size_t)dom_pairs;
-        if (end) HIP_TRY(SBV_EDEVICE, hipEventRecord(end, stream));
-    }
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.busy, stream));
-    c.busy_valid = true;
-    return SBV_OK;
+    return run_chunks_dev(c, n, stream, true, [&](size_t off, size_t m, hipEvent_t after_prep, hipEvent_t* dom, int* dom_pairs) {
+        return enqueue(c, src + off * SBV_TUPLE_BYTES, m, dst + off / 8, stream, after_prep, dom, dom_pairs);
+    });
 }
 
 // The host-pointer entry a cgo caller uses, pipelined: two staging slots (device tuples + bitmap + page-locked bitmap) and a
@@ -1636,33 +1687,12 @@ extern "C" int sbv_p256_verify_batch_keyed_dev(const void* d_rsh, const void* d_
     if (c.nkeys == 0) { g_err = "no keys registered"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    int rc = ensure_capacity(c, n < kMaxChunk ? n : kMaxChunk);
-    if (rc != SBV_OK) return rc;
-    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(stream, c.busy, 0));
     const uint8_t* src = static_cast<const uint8_t*>(d_rsh);
     const u32* sl = static_cast<const u32*>(d_slots);
     uint8_t* dst = static_cast<uint8_t*>(d_bitmap);
-    for (size_t off = 0; off < n; off += kMaxChunk) {
-        const size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
-        hipEvent_t mid = nullptr, end = nullptr;
-        if (c.profiling) {
-            if (c.prof_used + 3 > c.prof_events.size())
-                for (int k = 0; k < 3; ++k) { hipEvent_t ev; HIP_TRY(SBV_EDEVICE, hipEventCreate(&ev)); c.prof_events.push_back(ev); }
-            HIP_TRY(SBV_EDEVICE, hipEventRecord(c.prof_events[c.prof_used], stream));
-            mid = c.prof_events[c.prof_used + 1];
-            end = c.prof_events[c.prof_used + 2];
-            c.prof_used += 3;
-        }
-        rc = enqueue_keyed(c, src + off * 96, sl + off, m, dst + off / 8, stream, mid);
-        if (rc != SBV_OK) {
-            if (hipEventRecord(c.busy, stream) == hipSuccess) c.busy_valid = true;
-            return rc;
-        }
-        if (end) HIP_TRY(SBV_EDEVICE, hipEventRecord(end, stream));
-    }
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.busy, stream));
-    c.busy_valid = true;
-    return SBV_OK;
+    return run_chunks_dev(c, n, stream, true, [&](size_t off, size_t m, hipEvent_t after_prep, hipEvent_t*, int*) {
+        return enqueue_keyed(c, src + off * 96, sl + off, m, dst + off / 8, stream, after_prep);
+    });
 }
 
 extern "C" int sbv_p256_verify_batch_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* accept_bitmap) {
@@ -1712,33 +1742,13 @@ extern "C" int sbv_p256_verify_batch_keyed(const uint8_t* rsh, const uint32_t* s
         c.timing = tm;
         return SBV_OK;
     }
-    int rc = ensure_capacity(c, n < kMaxChunk ? n : kMaxChunk);
-    if (rc != SBV_OK) return rc;
-    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(c.stream, c.busy, 0));
-    sbv_timing tm{};
-    tm.n = n;
-    for (size_t off = 0; off < n; off += kMaxChunk) {
-        const size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[0], c.stream));
-        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, rsh + off * 96, m * 96, hipMemcpyHostToDevice, c.stream));
-        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots + off, m * sizeof(u32), hipMemcpyHostToDevice, c.stream));
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[1], c.stream));
-        rc = enqueue_keyed(c, c.d_tuples, c.d_slots, m, c.d_bitmap, c.stream, c.ev[2]);
-        if (rc != SBV_OK) return rc;
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[3], c.stream));
-        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.h_bitmap, c.d_bitmap, (m + 7) / 8, hipMemcpyDeviceToHost, c.stream));
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[4], c.stream));
-        HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(c.stream));
-        memcpy(accept_bitmap + off / 8, c.h_bitmap, (m + 7) / 8);
-        tm.h2d_us += 1e3 * ms_between(c.ev[0], c.ev[1]);
-        tm.prep_us += 1e3 * ms_between(c.ev[1], c.ev[2]);
-        tm.verify_us += 1e3 * ms_between(c.ev[2], c.ev[3]);
-        tm.d2h_us += 1e3 * ms_between(c.ev[3], c.ev[4]);
-    }
-    c.busy_valid = false;
-    tm.total_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    c.timing = tm;
-    return SBV_OK;
+    return run_chunks_host(c, n, accept_bitmap, t0, true,
+        [&](size_t off, size_t m) {
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, rsh + off * 96, m * 96, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots + off, m * sizeof(u32), hipMemcpyHostToDevice, c.stream));
+            return SBV_OK;
+        },
+        [&](size_t, size_t m, hipEvent_t after_prep) { return enqueue_keyed(c, c.d_tuples, c.d_slots, m, c.d_bitmap, c.stream, after_prep); });
 }
 
 namespace {
@@ -1783,40 +1793,14 @@ extern "C" int sbv_ed25519_verify_batch_dev(const void* d_tuples, size_t n, void
     if (n == 0) return SBV_OK;
     if (!d_tuples || !d_bitmap || (reinterpret_cast<uintptr_t>(d_tuples) & 15)) { g_err = "null or misaligned device pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    int rc = ensure_capacity(c, n < kMaxChunk ? n : kMaxChunk);
+    const int rc = ensure_ed_table(c);
     if (rc != SBV_OK) return rc;
-    if ((rc = ensure_ed_table(c)) != SBV_OK) return rc;
-    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(stream, c.busy, 0));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const uint8_t* src = static_cast<const uint8_t*>(d_tuples);
     uint8_t* dst = static_cast<uint8_t*>(d_bitmap);
-    for (size_t off = 0; off < n; off += kMaxChunk) {
-        const size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
-        hipEvent_t end = nullptr;
-        if (c.profiling) {
-            if (c.prof_used + 3 > c.prof_events.size())
-                for (int k = 0; k < 3; ++k) { hipEvent_t ev; HIP_TRY(SBV_EDEVICE, hipEventCreate(&ev)); c.prof_events.push_back(ev); }
-            HIP_TRY(SBV_EDEVICE, hipEventRecord(c.prof_events[c.prof_used], stream));
-            HIP_TRY(SBV_EDEVICE, hipEventRecord(c.prof_events[c.prof_used + 1], stream));     // no stage A
-            end = c.prof_events[c.prof_used + 2];
-            c.prof_used += 3;
-        }
-        hipEvent_t* dom = nullptr;                // event pairs around the dominant kernel (k_ed_qphase, one launch per chunk of windows)
-        int dom_pairs = 0;
-        if (c.profiling) {
-            while (c.prof_dom_used + 2 * SBV_GROUP_MAX_CHUNKS > c.prof_dom.size()) { hipEvent_t ev; HIP_TRY(SBV_EDEVICE, hipEventCreate(&ev)); c.prof_dom.push_back(ev); }
-            dom = c.prof_dom.data() + c.prof_dom_used;
-        }
-        if ((rc = enqueue_ed25519(c, src + off * 128, m, dst + off / 8, stream, dom, &dom_pairs)) != SBV_OK) {
-            if (hipEventRecord(c.busy, stream) == hipSuccess) c.busy_valid = true;
-            return rc;
-        }
-        if (c.profiling) c.prof_dom_used += 2 * (size_t)dom_pairs;
-        if (end) HIP_TRY(SBV_EDEVICE, hipEventRecord(end, stream));
-    }
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.busy, stream));
-    c.busy_valid = true;
-    return SBV_OK;
+    return run_chunks_dev(c, n, stream, false, [&](size_t off, size_t m, hipEvent_t, hipEvent_t* dom, int* dom_pairs) {
+        return enqueue_ed25519(c, src + off * 128, m, dst + off / 8, stream, dom, dom_pairs);
+    });
 }
 
 extern "C" int sbv_ed25519_verify_batch(const uint8_t* tuples, size_t n, uint8_t* accept_bitmap) {
@@ -1826,31 +1810,14 @@ extern "C" int sbv_ed25519_verify_batch(const uint8_t* tuples, size_t n, uint8_t
     if (!tuples || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_capacity(c, n < kMaxChunk ? n : kMaxChunk);
+    const int rc = ensure_ed_table(c);
     if (rc != SBV_OK) return rc;
-    if ((rc = ensure_ed_table(c)) != SBV_OK) return rc;
-    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(c.stream, c.busy, 0));
-    sbv_timing tm{};
-    tm.n = n;
-    for (size_t off = 0; off < n; off += kMaxChunk) {
-        const size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[0], c.stream));
-        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, tuples + off * 128, m * 128, hipMemcpyHostToDevice, c.stream));
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[1], c.stream));
-        if ((rc = enqueue_ed25519(c, c.d_tuples, m, c.d_bitmap, c.stream)) != SBV_OK) return rc;
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[3], c.stream));
-        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.h_bitmap, c.d_bitmap, (m + 7) / 8, hipMemcpyDeviceToHost, c.stream));
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[4], c.stream));
-        HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(c.stream));
-        memcpy(accept_bitmap + off / 8, c.h_bitmap, (m + 7) / 8);
-        tm.h2d_us += 1e3 * ms_between(c.ev[0], c.ev[1]);
-        tm.verify_us += 1e3 * ms_between(c.ev[1], c.ev[3]);
-        tm.d2h_us += 1e3 * ms_between(c.ev[3], c.ev[4]);
-    }
-    c.busy_valid = false;
-    tm.total_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    c.timing = tm;
-    return SBV_OK;
+    return run_chunks_host(c, n, accept_bitmap, t0, false,
+        [&](size_t off, size_t m) {
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, tuples + off * 128, m * 128, hipMemcpyHostToDevice, c.stream));
+            return SBV_OK;
+        },
+        [&](size_t, size_t m, hipEvent_t) { return enqueue_ed25519(c, c.d_tuples, m, c.d_bitmap, c.stream); });
 }
 
 // ---- secp256k1 variant ("other curves") ------------------------------------------------------
@@ -1916,26 +1883,14 @@ extern "C" int sbv_secp256k1_verify_batch_dev(const void* d_tuples, size_t n, vo
     if (n == 0) return SBV_OK;
     if (!d_tuples || !d_bitmap || (reinterpret_cast<uintptr_t>(d_tuples) & 15)) { g_err = "null or misaligned device pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    int rc = ensure_capacity(c, n < kMaxChunk ? n : kMaxChunk);
+    const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
-    if ((rc = ensure_k256_table(c)) != SBV_OK) return rc;
-    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(stream, c.busy, 0));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const uint8_t* src = static_cast<const uint8_t*>(d_tuples);
     uint8_t* dst = static_cast<uint8_t*>(d_bitmap);
-    for (size_t off = 0; off < n && rc == SBV_OK; off += kMaxChunk) {
-        const size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
-        hipEvent_t* dom = nullptr;                // event pairs around the dominant kernel (k_k256_qphase), read by sbv_profile_read_dominant
-        int dom_pairs = 0;
-        if (c.profiling) {
-            while (c.prof_dom_used + 2 * SBV_GROUP_MAX_CHUNKS > c.prof_dom.size()) { hipEvent_t ev; if (hipEventCreate(&ev) != hipSuccess) { g_err = "hipEventCreate failed"; return SBV_EDEVICE; } c.prof_dom.push_back(ev); }
-            dom = c.prof_dom.data() + c.prof_dom_used;
-        }
-        rc = enqueue_k256(c, src + off * 160, m, dst + off / 8, stream, dom, &dom_pairs);
-        if (rc == SBV_OK && c.profiling) c.prof_dom_used += 2 * (size_t)dom_pairs;
-    }
-    if (hipEventRecord(c.busy, stream) == hipSuccess) c.busy_valid = true;       // the scratch stays ordered behind whatever was enqueued
-    return rc;
+    return run_chunks_dev(c, n, stream, false, [&](size_t off, size_t m, hipEvent_t, hipEvent_t* dom, int* dom_pairs) {
+        return enqueue_k256(c, src + off * 160, m, dst + off / 8, stream, dom, dom_pairs);
+    });
 }
 
 extern "C" int sbv_secp256k1_verify_batch(const uint8_t* tuples, size_t n, uint8_t* accept_bitmap) {
@@ -1945,31 +1900,14 @@ extern "C" int sbv_secp256k1_verify_batch(const uint8_t* tuples, size_t n, uint8
     if (!tuples || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_capacity(c, n < kMaxChunk ? n : kMaxChunk);
+    const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
-    if ((rc = ensure_k256_table(c)) != SBV_OK) return rc;
-    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(c.stream, c.busy, 0));
-    sbv_timing tm{};
-    tm.n = n;
-    for (size_t off = 0; off < n; off += kMaxChunk) {
-        const size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[0], c.stream));
-        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, tuples + off * 160, m * 160, hipMemcpyHostToDevice, c.stream));
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[1], c.stream));
-        if ((rc = enqueue_k256(c, c.d_tuples, m, c.d_bitmap, c.stream)) != SBV_OK) return rc;
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[3], c.stream));
-        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.h_bitmap, c.d_bitmap, (m + 7) / 8, hipMemcpyDeviceToHost, c.stream));
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[4], c.stream));
-        HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(c.stream));
-        memcpy(accept_bitmap + off / 8, c.h_bitmap, (m + 7) / 8);
-        tm.h2d_us += 1e3 * ms_between(c.ev[0], c.ev[1]);
-        tm.verify_us += 1e3 * ms_between(c.ev[1], c.ev[3]);
-        tm.d2h_us += 1e3 * ms_between(c.ev[3], c.ev[4]);
-    }
-    c.busy_valid = false;
-    tm.total_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    c.timing = tm;
-    return SBV_OK;
+    return run_chunks_host(c, n, accept_bitmap, t0, false,
+        [&](size_t off, size_t m) {
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, tuples + off * 160, m * 160, hipMemcpyHostToDevice, c.stream));
+            return SBV_OK;
+        },
+        [&](size_t, size_t m, hipEvent_t) { return enqueue_k256(c, c.d_tuples, m, c.d_bitmap, c.stream); });
 }
 
 namespace {
@@ -1995,46 +1933,29 @@ extern "C" int sbv_p256_verify_msgs_keyed(const uint8_t* msgs, const uint64_t* m
     if (!msg_offsets || !sig_offsets || !slots || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
     if (c.nkeys == 0) { g_err = "no keys registered"; return SBV_EINVAL; }
     if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
-    // the device dereferences the offset tables: they must start at 0 and never decrease
-    if (msg_offsets[0] != 0 || sig_offsets[0] != 0) { g_err = "offset tables must start at 0"; return SBV_EINVAL; }
-    for (size_t i = 0; i < n; ++i)
-        if (msg_offsets[i + 1] < msg_offsets[i] || sig_offsets[i + 1] < sig_offsets[i]) { g_err = "offset table is not monotone"; return SBV_EINVAL; }
-    const size_t mbytes = (size_t)msg_offsets[n], sbytes = (size_t)sig_offsets[n];
-    if ((mbytes && !msgs) || (sbytes && !sigs)) { g_err = "null pointer"; return SBV_EINVAL; }
+    size_t mbytes = 0, sbytes = 0;
+    int rc = check_offsets(msg_offsets, n, msgs, mbytes);
+    if (rc == SBV_OK) rc = check_offsets(sig_offsets, n, sigs, sbytes);
+    if (rc != SBV_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_capacity(c, n);
-    if (rc != SBV_OK) return rc;
     if ((rc = grow(c.d_msgs, c.msgs_cap, mbytes + 16)) != SBV_OK) return rc;
     if ((rc = grow(c.d_sigs, c.sigs_cap, sbytes + 16)) != SBV_OK) return rc;
     if ((rc = grow(c.d_moff, c.moff_cap, n + 1)) != SBV_OK) return rc;
     if ((rc = grow(c.d_soff, c.soff_cap, n + 1)) != SBV_OK) return rc;
-    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(c.stream, c.busy, 0));
-    sbv_timing tm{};
-    tm.n = n;
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[0], c.stream));
-    if (mbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_msgs, msgs, mbytes, hipMemcpyHostToDevice, c.stream));
-    if (sbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs, sigs, sbytes, hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_moff, msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_soff, sig_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots, n * sizeof(u32), hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[1], c.stream));
-    HIP_TRY(SBV_EDEVICE, sbv::launch_msg_frontend(c.d_msgs, c.d_moff, c.d_sigs, c.d_soff, n, reinterpret_cast<u32*>(c.d_tuples), c.stream, 0, 0, mbytes, sbytes));
-    rc = enqueue_keyed(c, c.d_tuples, c.d_slots, n, c.d_bitmap, c.stream, c.ev[2]);
-    if (rc != SBV_OK) return rc;
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[3], c.stream));
-    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.h_bitmap, c.d_bitmap, (n + 7) / 8, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[4], c.stream));
-    HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(c.stream));
-    memcpy(accept_bitmap, c.h_bitmap, (n + 7) / 8);
-    tm.h2d_us = 1e3 * ms_between(c.ev[0], c.ev[1]);
-    tm.prep_us = 1e3 * ms_between(c.ev[1], c.ev[2]);       // front end + stage A
-    tm.verify_us = 1e3 * ms_between(c.ev[2], c.ev[3]);
-    tm.d2h_us = 1e3 * ms_between(c.ev[3], c.ev[4]);
-    c.busy_valid = false;
-    tm.total_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    c.timing = tm;
-    return SBV_OK;
+    return run_chunks_host(c, n, accept_bitmap, t0, true,
+        [&](size_t, size_t) {
+            if (mbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_msgs, msgs, mbytes, hipMemcpyHostToDevice, c.stream));
+            if (sbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs, sigs, sbytes, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_moff, msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_soff, sig_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots, n * sizeof(u32), hipMemcpyHostToDevice, c.stream));
+            return SBV_OK;
+        },
+        [&](size_t, size_t, hipEvent_t after_prep) {          // prep_us: front end + stage A
+            HIP_TRY(SBV_EDEVICE, sbv::launch_msg_frontend(c.d_msgs, c.d_moff, c.d_sigs, c.d_soff, n, reinterpret_cast<u32*>(c.d_tuples), c.stream, 0, 0, mbytes, sbytes));
+            return enqueue_keyed(c, c.d_tuples, c.d_slots, n, c.d_bitmap, c.stream, after_prep);
+        });
 }
 
 extern "C" int sbv_ed25519_verify_msgs(const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* msg_offsets,
@@ -2044,46 +1965,30 @@ extern "C" int sbv_ed25519_verify_msgs(const uint8_t* sigs, const uint8_t* pks, 
     if (n == 0) return SBV_OK;
     if (!sigs || !pks || !msg_offsets || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
     if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
-    if (msg_offsets[0] != 0) { g_err = "offset tables must start at 0"; return SBV_EINVAL; }
-    for (size_t i = 0; i < n; ++i)
-        if (msg_offsets[i + 1] < msg_offsets[i]) { g_err = "offset table is not monotone"; return SBV_EINVAL; }
-    const size_t mbytes = (size_t)msg_offsets[n];
-    if (mbytes && !msgs) { g_err = "null pointer"; return SBV_EINVAL; }
+    size_t mbytes = 0;
+    int rc = check_offsets(msg_offsets, n, msgs, mbytes);
+    if (rc != SBV_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_capacity(c, n);
-    if (rc != SBV_OK) return rc;
     if ((rc = ensure_ed_table(c)) != SBV_OK) return rc;
     // staging: messages in d_msgs, signatures (64 B each) followed by keys (32 B each) in d_sigs, offsets in d_moff
     if ((rc = grow(c.d_msgs, c.msgs_cap, mbytes + 16)) != SBV_OK) return rc;
     if ((rc = grow(c.d_sigs, c.sigs_cap, n * 96 + 16)) != SBV_OK) return rc;
     if ((rc = grow(c.d_moff, c.moff_cap, n + 1)) != SBV_OK) return rc;
-    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(c.stream, c.busy, 0));
-    sbv_timing tm{};
-    tm.n = n;
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[0], c.stream));
-    if (mbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_msgs, msgs, mbytes, hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs, sigs, n * 64, hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs + n * 64, pks, n * 32, hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_moff, msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[1], c.stream));
-    HIP_TRY(SBV_EDEVICE, sbv::launch_ed_msg_frontend(c.d_sigs, c.d_sigs + n * 64, c.d_msgs, c.d_moff, n,
-                                                     reinterpret_cast<u32*>(c.d_tuples), c.stream));
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[2], c.stream));
-    if ((rc = enqueue_ed25519(c, c.d_tuples, n, c.d_bitmap, c.stream)) != SBV_OK) return rc;
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[3], c.stream));
-    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.h_bitmap, c.d_bitmap, (n + 7) / 8, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[4], c.stream));
-    HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(c.stream));
-    memcpy(accept_bitmap, c.h_bitmap, (n + 7) / 8);
-    tm.h2d_us = 1e3 * ms_between(c.ev[0], c.ev[1]);
-    tm.prep_us = 1e3 * ms_between(c.ev[1], c.ev[2]);       // the front end
-    tm.verify_us = 1e3 * ms_between(c.ev[2], c.ev[3]);
-    tm.d2h_us = 1e3 * ms_between(c.ev[3], c.ev[4]);
-    c.busy_valid = false;
-    tm.total_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    c.timing = tm;
-    return SBV_OK;
+    return run_chunks_host(c, n, accept_bitmap, t0, true,
+        [&](size_t, size_t) {
+            if (mbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_msgs, msgs, mbytes, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs, sigs, n * 64, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs + n * 64, pks, n * 32, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_moff, msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+            return SBV_OK;
+        },
+        [&](size_t, size_t, hipEvent_t after_prep) {          // prep_us: the front end
+            HIP_TRY(SBV_EDEVICE, sbv::launch_ed_msg_frontend(c.d_sigs, c.d_sigs + n * 64, c.d_msgs, c.d_moff, n,
+                                                             reinterpret_cast<u32*>(c.d_tuples), c.stream));
+            HIP_TRY(SBV_EDEVICE, hipEventRecord(after_prep, c.stream));
+            return enqueue_ed25519(c, c.d_tuples, n, c.d_bitmap, c.stream);
+        });
 }
 
 // ---- registered Ed25519 keys (ed25519_keyed.h; include/sbv.h: sbv_ed25519_register_keys) ---------------------------------------
@@ -2192,11 +2097,9 @@ int enqueue_ed_keyed(Context& c, const uint8_t* d_recs, const u32* d_slots, size
     return SBV_OK;
 }
 // the tables every keyed call needs: the comb of B of the grouped step (ensure_ed_bcomb falls back to the one-lane kernel's at 16 bits)
-int ensure_ed_keyed(Context& c, size_t n) {
-    int rc = ensure_capacity(c, n < kMaxChunk ? n : kMaxChunk);
-    if (rc == SBV_OK) rc = ensure_ed_table(c);
-    if (rc == SBV_OK) rc = ensure_ed_bcomb(c);
-    return rc;
+int ensure_ed_keyed(Context& c) {
+    const int rc = ensure_ed_table(c);
+    return rc == SBV_OK ? ensure_ed_bcomb(c) : rc;
 }
 }  // namespace
 
@@ -2397,22 +2300,14 @@ extern "C" int sbv_ed25519_verify_batch_keyed_dev(const void* d_rsk, const void*
         HIP_TRY(SBV_EDEVICE, hipMemsetAsync(d_bitmap, 0, (n + 7) / 8, stream));
         return SBV_OK;
     }
-    int rc = ensure_ed_keyed(c, n);
+    const int rc = ensure_ed_keyed(c);
     if (rc != SBV_OK) return rc;
-    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(stream, c.busy, 0));
     const uint8_t* src = static_cast<const uint8_t*>(d_rsk);
     const u32* sl = static_cast<const u32*>(d_slots);
     uint8_t* dst = static_cast<uint8_t*>(d_bitmap);
-    for (size_t off = 0; off < n; off += kMaxChunk) {
-        const size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
-        if ((rc = enqueue_ed_keyed(c, src + off * SBV_ED_REC_BYTES, sl + off, m, dst + off / 8, stream)) != SBV_OK) {
-            if (hipEventRecord(c.busy, stream) == hipSuccess) c.busy_valid = true;
-            return rc;
-        }
-    }
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.busy, stream));
-    c.busy_valid = true;
-    return SBV_OK;
+    return run_chunks_dev(c, n, stream, false, [&](size_t off, size_t m, hipEvent_t, hipEvent_t*, int*) {
+        return enqueue_ed_keyed(c, src + off * SBV_ED_REC_BYTES, sl + off, m, dst + off / 8, stream);
+    });
 }
 
 extern "C" int sbv_ed25519_verify_batch_keyed(const uint8_t* rsk, const uint32_t* slots, size_t n, uint8_t* accept_bitmap) {
@@ -2423,31 +2318,15 @@ extern "C" int sbv_ed25519_verify_batch_keyed(const uint8_t* rsk, const uint32_t
     if (c.ed_nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_ed_keyed(c, n);
+    const int rc = ensure_ed_keyed(c);
     if (rc != SBV_OK) return rc;
-    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(c.stream, c.busy, 0));
-    sbv_timing tm{};
-    tm.n = n;
-    for (size_t off = 0; off < n; off += kMaxChunk) {
-        const size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[0], c.stream));
-        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, rsk + off * SBV_ED_REC_BYTES, m * SBV_ED_REC_BYTES, hipMemcpyHostToDevice, c.stream));
-        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots + off, m * sizeof(u32), hipMemcpyHostToDevice, c.stream));
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[1], c.stream));
-        if ((rc = enqueue_ed_keyed(c, c.d_tuples, c.d_slots, m, c.d_bitmap, c.stream)) != SBV_OK) return rc;
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[3], c.stream));
-        HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.h_bitmap, c.d_bitmap, (m + 7) / 8, hipMemcpyDeviceToHost, c.stream));
-        HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[4], c.stream));
-        HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(c.stream));
-        memcpy(accept_bitmap + off / 8, c.h_bitmap, (m + 7) / 8);
-        tm.h2d_us += 1e3 * ms_between(c.ev[0], c.ev[1]);
-        tm.verify_us += 1e3 * ms_between(c.ev[1], c.ev[3]);
-        tm.d2h_us += 1e3 * ms_between(c.ev[3], c.ev[4]);
-    }
-    c.busy_valid = false;
-    tm.total_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    c.timing = tm;
-    return SBV_OK;
+    return run_chunks_host(c, n, accept_bitmap, t0, false,
+        [&](size_t off, size_t m) {
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, rsk + off * SBV_ED_REC_BYTES, m * SBV_ED_REC_BYTES, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots + off, m * sizeof(u32), hipMemcpyHostToDevice, c.stream));
+            return SBV_OK;
+        },
+        [&](size_t, size_t m, hipEvent_t) { return enqueue_ed_keyed(c, c.d_tuples, c.d_slots, m, c.d_bitmap, c.stream); });
 }
 
 extern "C" int sbv_ed25519_verify_msgs_keyed(const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
@@ -2457,45 +2336,30 @@ extern "C" int sbv_ed25519_verify_msgs_keyed(const uint8_t* sigs, const uint8_t*
     if (n == 0) return SBV_OK;
     if (!sigs || !slots || !msg_offsets || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
     if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
-    if (msg_offsets[0] != 0) { g_err = "offset tables must start at 0"; return SBV_EINVAL; }
-    for (size_t i = 0; i < n; ++i)
-        if (msg_offsets[i + 1] < msg_offsets[i]) { g_err = "offset table is not monotone"; return SBV_EINVAL; }
-    const size_t mbytes = (size_t)msg_offsets[n];
-    if (mbytes && !msgs) { g_err = "null pointer"; return SBV_EINVAL; }
+    size_t mbytes = 0;
+    int rc = check_offsets(msg_offsets, n, msgs, mbytes);
+    if (rc != SBV_OK) return rc;
     if (c.ed_nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_ed_keyed(c, n);
-    if (rc != SBV_OK) return rc;
+    if ((rc = ensure_ed_keyed(c)) != SBV_OK) return rc;
     if ((rc = grow(c.d_msgs, c.msgs_cap, mbytes + 16)) != SBV_OK) return rc;
     if ((rc = grow(c.d_sigs, c.sigs_cap, n * 64 + 16)) != SBV_OK) return rc;
     if ((rc = grow(c.d_moff, c.moff_cap, n + 1)) != SBV_OK) return rc;
-    if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(c.stream, c.busy, 0));
-    sbv_timing tm{};
-    tm.n = n;
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[0], c.stream));
-    if (mbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_msgs, msgs, mbytes, hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs, sigs, n * 64, hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_moff, msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots, n * sizeof(u32), hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[1], c.stream));
-    HIP_TRY(SBV_EDEVICE, sbv::launch_ed_keyed_msg_frontend(c.d_sigs, c.d_slots, ed_reg_view(c), c.d_msgs, c.d_moff, n,
-                                                           reinterpret_cast<uint8_t*>(c.d_qtab), c.stream));
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[2], c.stream));
-    if ((rc = enqueue_ed_keyed(c, nullptr, c.d_slots, n, c.d_bitmap, c.stream, true)) != SBV_OK) return rc;
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[3], c.stream));
-    HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.h_bitmap, c.d_bitmap, (n + 7) / 8, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(SBV_EDEVICE, hipEventRecord(c.ev[4], c.stream));
-    HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(c.stream));
-    memcpy(accept_bitmap, c.h_bitmap, (n + 7) / 8);
-    tm.h2d_us = 1e3 * ms_between(c.ev[0], c.ev[1]);
-    tm.prep_us = 1e3 * ms_between(c.ev[1], c.ev[2]);       // the front end
-    tm.verify_us = 1e3 * ms_between(c.ev[2], c.ev[3]);
-    tm.d2h_us = 1e3 * ms_between(c.ev[3], c.ev[4]);
-    c.busy_valid = false;
-    tm.total_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    c.timing = tm;
-    return SBV_OK;
+    return run_chunks_host(c, n, accept_bitmap, t0, true,
+        [&](size_t, size_t) {
+            if (mbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_msgs, msgs, mbytes, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs, sigs, n * 64, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_moff, msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots, n * sizeof(u32), hipMemcpyHostToDevice, c.stream));
+            return SBV_OK;
+        },
+        [&](size_t, size_t, hipEvent_t after_prep) {          // prep_us: the front end
+            HIP_TRY(SBV_EDEVICE, sbv::launch_ed_keyed_msg_frontend(c.d_sigs, c.d_slots, ed_reg_view(c), c.d_msgs, c.d_moff, n,
+                                                                   reinterpret_cast<uint8_t*>(c.d_qtab), c.stream));
+            HIP_TRY(SBV_EDEVICE, hipEventRecord(after_prep, c.stream));
+            return enqueue_ed_keyed(c, nullptr, c.d_slots, n, c.d_bitmap, c.stream, true);
+        });
 }
 
 // ---- batch signing (p256_sign.h) ----------------------------------------------------------------------
@@ -3173,7 +3037,7 @@ int part_enqueue(Context& c, const uint8_t* d_tuples, size_t n, u32 part, u32 pa
         hipLaunchKernelGGL(k_part_gather, dim3((unsigned)((members * 10 + 255) / 256)), dim3(256), 0, stream, src, pb.d_idx, members, pb.d_dense);
         if ((rc = ensure_capacity(c, members)) != SBV_OK) return rc;
         if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(stream, c.busy, 0));
-        rc = enqueue(c, pb.d_dense, members, pb.d_bits, stream, nullptr, nullptr, nullptr, nullptr, n);
+        rc = enqueue(c, pb.d_dense, members, pb.d_bits, stream, nullptr, nullptr, nullptr, n);
         if (hipEventRecord(c.busy, stream) == hipSuccess) c.busy_valid = true;
         if (rc != SBV_OK) return rc;
         hipLaunchKernelGGL(k_part_scatter, dim3((unsigned)((members + 255) / 256)), dim3(256), 0, stream, pb.d_bits, pb.d_idx, members, d_out_words + off / 32);

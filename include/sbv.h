@@ -260,11 +260,12 @@ typedef struct sbv_timing {
 /* Timing of the most recent sbv_p256_verify_batch call made by any thread. */
 int sbv_last_timing(sbv_timing* out);
 
-/* Per-kernel timing of the device-pointer entry (bench.py's roofline leg).  While enabled,
- * every sbv_p256_verify_batch_dev call records HIP events around its two kernels ON THE
- * CALLER'S STREAM; sbv_profile_read waits for them and returns the sums (microseconds) and the
- * number of stage-B launches since the previous read.
- * on = 1: an event triple per call (before stage A, after stage A, after stage B) AND a pair around every launch of the
+/* Per-kernel timing of the device-pointer entries (bench.py's roofline leg).  While enabled,
+ * every call of a device-pointer verify entry (sbv_p256_verify_batch_dev, sbv_p256_verify_batch_keyed_dev,
+ * sbv_ed25519_verify_batch_dev, sbv_ed25519_verify_batch_keyed_dev, sbv_secp256k1_verify_batch_dev) records HIP events
+ * around its kernels ON THE CALLER'S STREAM; sbv_profile_read waits for them and returns the sums (microseconds) and the
+ * number of stage-B launches since the previous read (a step without stage A records its middle event at its start).
+ * on = 1: an event triple per launch (before stage A, after stage A, after stage B) AND a pair around every launch of the
  * dominant kernel; on = 2: the dominant-kernel pairs only (what bench.py keeps inside its timed region: every recorded event
  * is a packet between two kernels of the step); on = 0: off.  Process-wide: applies to every initialised device and to
  * devices initialised later. */

@@ -214,3 +214,99 @@ def test_ed25519_batches_leave_the_p256_key_cache_alone(gpu, oracle):
         assert hits >= 300 and misses == 0
     finally:
         gpu.set_grouping(True, sbv.GROUP_MIN_BATCH_DEFAULT, 0, 0)
+
+
+CHUNKED_N = (1 << 21) + (1 << 19) + 37        # two launches of kMaxChunk = 2^21 tuples and a ragged tail
+
+
+@pytest.fixture(scope="module")
+def chunked(gpu, oracle):
+    """A generated batch of 2^16 (64 signers, every 8th signature corrupted) per scheme, tiled up to CHUNKED_N records; the keyed forms
+    over its registered keys -> {scheme: (host-pointer entry, device-pointer entry, dominant kernel reported, inputs, expected bitmap)}."""
+    base = 1 << 16
+    reps = -(-CHUNKED_N // base)
+
+    def gen(fn, rec_bytes, seed):
+        fn.argtypes = [ctypes.c_uint32, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        tup = np.zeros(rec_bytes * base, dtype=np.uint8)
+        exp = np.zeros(base // 8, dtype=np.uint8)
+        fn(seed, base, 64, 8, tup.ctypes.data, exp.ctypes.data, THREADS)
+        want = np.packbits(np.tile(_bits(exp.tobytes(), base), reps)[:CHUNKED_N], bitorder="little")
+        return np.tile(tup.reshape(base, rec_bytes), (reps, 1))[:CHUNKED_N], want
+
+    def slots(keys, register):
+        uniq, inv = np.unique(keys, axis=0, return_inverse=True)
+        return np.array(register([k.tobytes() for k in uniq]), dtype=np.uint32)[inv.reshape(-1)]
+
+    lib = sbv.load()
+    p256, p256_want = gen(oracle.sbvo_gen_batch, 160, 0xC4A7)
+    ed, ed_want = gen(oracle.sbvo_ed25519_gen_batch, 128, 0xC4A8)
+    k256, k256_want = gen(oracle.sbvo_k256_gen_batch, 160, 0xC4A9)
+    gpu.clear_keys()
+    gpu.ed25519_clear_keys()
+    try:
+        yield {
+            "p256": (lib.sbv_p256_verify_batch, lib.sbv_p256_verify_batch_dev, True, [p256], p256_want),
+            "ed25519": (lib.sbv_ed25519_verify_batch, lib.sbv_ed25519_verify_batch_dev, True, [ed], ed_want),
+            "secp256k1": (lib.sbv_secp256k1_verify_batch, lib.sbv_secp256k1_verify_batch_dev, True, [k256], k256_want),
+            "p256 keyed": (lib.sbv_p256_verify_batch_keyed, lib.sbv_p256_verify_batch_keyed_dev, False,
+                           [p256[:, :96], slots(p256[:, 96:], gpu.register_keys)], p256_want),
+            "ed25519 keyed": (lib.sbv_ed25519_verify_batch_keyed, lib.sbv_ed25519_verify_batch_keyed_dev, False,
+                              [np.concatenate([ed[:, :64], ed[:, 96:]], axis=1), slots(ed[:, 64:96], gpu.ed25519_register_keys)], ed_want),
+        }
+    finally:
+        gpu.clear_keys()
+        gpu.ed25519_clear_keys()
+
+
+def _on_device(arrays):
+    import torch
+    return [torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8)).cuda() for a in arrays]
+
+
+def _dev_call(entry, d_inputs, n):
+    import torch
+    entry.argtypes = [ctypes.c_void_p] * len(d_inputs) + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    d_b = torch.zeros((n + 7) // 8, dtype=torch.uint8, device="cuda")
+    sbv._check(entry(*[ctypes.c_void_p(x.data_ptr()) for x in d_inputs], ctypes.c_size_t(n), ctypes.c_void_p(d_b.data_ptr()),
+                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    torch.cuda.synchronize()
+    return d_b.cpu().numpy()
+
+
+@pytest.mark.parametrize("scheme", ["ed25519", "secp256k1", "p256 keyed", "ed25519 keyed"])
+def test_chunked_batches_through_the_host_and_device_entries(chunked, scheme):
+    """More records than one launch holds (kMaxChunk = 2^21) through the host-pointer and the device-pointer entry: both walk the
+    batch in chunks, and the bitmap equals the tiled batch's verdicts, ragged tail included."""
+    host, dev, _, inputs, want = chunked[scheme]
+    inputs = [np.ascontiguousarray(a) for a in inputs]
+    host.argtypes = [ctypes.c_void_p] * len(inputs) + [ctypes.c_size_t, ctypes.c_void_p]
+    got = np.zeros((CHUNKED_N + 7) // 8, dtype=np.uint8)
+    sbv._check(host(*[ctypes.c_void_p(a.ctypes.data) for a in inputs], ctypes.c_size_t(CHUNKED_N), ctypes.c_void_p(got.ctypes.data)))
+    assert (got == want).all(), (scheme, "host", np.nonzero(got != want)[0][:8])
+    got = _dev_call(dev, _on_device(inputs), CHUNKED_N)
+    assert (got == want).all(), (scheme, "device", np.nonzero(got != want)[0][:8])
+
+
+@pytest.mark.parametrize("scheme", ["p256", "p256 keyed", "ed25519", "ed25519 keyed", "secp256k1"])
+def test_profiling_levels_of_the_device_entries(gpu, chunked, scheme):
+    """include/sbv.h, sbv_profile_enable: level 2 records only the pairs around the dominant kernel's launches (what bench.py keeps in
+    its timed region), level 1 also an event triple per launch of the step.  At both levels every launch of the dominant kernel of the
+    grouped P-256, Ed25519 and secp256k1 steps counts (one per chunk of windows: 1 to SBV_GROUP_MAX_CHUNKS = 4 per launch of the step)."""
+    _, dev, dominant, inputs, _ = chunked[scheme]
+    d_inputs = _on_device(inputs)
+    launches = -(-CHUNKED_N // (1 << 21))
+    _dev_call(dev, d_inputs, CHUNKED_N)            # tables and buffers set up outside the profiled calls
+    gpu.profile_read_dominant()
+    gpu.profile_read()
+    seen = {}
+    try:
+        for level in (2, 1):
+            gpu.profile_enable(level)
+            _dev_call(dev, d_inputs, CHUNKED_N)
+            seen[level] = (gpu.profile_read_dominant()[1], gpu.profile_read()[2])
+    finally:
+        gpu.profile_enable(False)
+    assert seen[2][1] == 0 and seen[1][1] == launches, (scheme, seen)
+    for dom, _ in seen.values():
+        assert (launches <= dom <= 4 * launches) if dominant else dom == 0, (scheme, seen)
