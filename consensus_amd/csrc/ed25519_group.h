@@ -128,6 +128,26 @@ struct edchain_quad_host {
     int role(int i) const { return i; }
     void bcast(fe25 out[4], const fe25 in[4], int src) const { for (int i = 0; i < 4; ++i) out[i] = in[src]; }
 };
+#if defined(__HIPCC__)
+// The device policy: one lane of a quad, DPP quad_perm broadcasts (k_ed_keytab_bases and the quad form of the one-lane kernel in
+// ed25519_group_kernels.hip; the device unit tier, tools/devunit.hip).
+struct edchain_quad_dev {
+    static const int N = 1;
+    ept s[1];
+    int r;
+    __device__ __forceinline__ int role(int) const { return r; }
+    __device__ __forceinline__ void bcast(fe25 out[1], const fe25 in[1], int src) const {
+        SBV_UNROLL
+        for (int l = 0; l < 10; ++l) {
+            const int v = in[0].v[l];
+            out[0].v[l] = src == 0 ? __builtin_amdgcn_mov_dpp(v, 0x00, 0xF, 0xF, true)
+                        : src == 1 ? __builtin_amdgcn_mov_dpp(v, 0x55, 0xF, 0xF, true)
+                        : src == 2 ? __builtin_amdgcn_mov_dpp(v, 0xAA, 0xF, 0xF, true)
+                                   : __builtin_amdgcn_mov_dpp(v, 0xFF, 0xF, 0xF, true);
+        }
+    }
+};
+#endif
 SBV_HD void edchain_l1(fe25& P, const ept& s, int role) {
     fe25 xy, in;
     fe25_add(xy, s.X, s.Y);

@@ -55,23 +55,7 @@ __global__ __launch_bounds__(256) void k_ed_group_split(size_t n, GroupState g) 
 }
 
 // only the groups whose tables are built in this batch (cold: not found in the key-table cache).  Four lanes per key (ed25519_group.h:
-// edchain_run); a quad lives or exits as a whole.
-struct edchain_quad_dev {
-    static const int N = 1;
-    ept s[1];
-    int r;
-    __device__ __forceinline__ int role(int) const { return r; }
-    __device__ __forceinline__ void bcast(fe25 out[1], const fe25 in[1], int src) const {
-        SBV_UNROLL
-        for (int l = 0; l < 10; ++l) {
-            const int v = in[0].v[l];
-            out[0].v[l] = src == 0 ? __builtin_amdgcn_mov_dpp(v, 0x00, 0xF, 0xF, true)
-                        : src == 1 ? __builtin_amdgcn_mov_dpp(v, 0x55, 0xF, 0xF, true)
-                        : src == 2 ? __builtin_amdgcn_mov_dpp(v, 0xAA, 0xF, 0xF, true)
-                                   : __builtin_amdgcn_mov_dpp(v, 0xFF, 0xF, 0xF, true);
-        }
-    }
-};
+// edchain_run, exchange policy edchain_quad_dev); a quad lives or exits as a whole.
 __global__ __launch_bounds__(64) void k_ed_keytab_bases(const uint8_t* __restrict__ tuples, GroupState g, u32* __restrict__ jbases,
                                                         uint8_t* __restrict__ valid, const u32* __restrict__ tslot, const uint8_t* __restrict__ cold,
                                                         int j_first, int j_last) {

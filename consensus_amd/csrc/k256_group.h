@@ -83,6 +83,24 @@ struct k256_quad_host {
     int role(int i) const { return i; }
     void bcast(kfe out[4], const kfe in[4], int src) const { for (int i = 0; i < 4; ++i) out[i] = in[src]; }
 };
+#if defined(__HIPCC__)
+// The device policy: one lane of a quad, DPP quad_perm broadcasts (k_k256_chain in k256_group_kernels.hip; tools/devunit.hip).
+struct k256_quad_dev {
+    static const int N = 1;
+    kchain3 s[1];
+    int r;
+    __device__ __forceinline__ int role(int) const { return r; }
+    __device__ __forceinline__ void bcast(kfe out[1], const kfe in[1], int src) const {
+        SBV_UNROLL
+        for (int l = 0; l < 9; ++l) {
+            const int v = in[0].v[l];
+            out[0].v[l] = src == 0 ? __builtin_amdgcn_mov_dpp(v, 0x00, 0xF, 0xF, true)
+                        : src == 1 ? __builtin_amdgcn_mov_dpp(v, 0x55, 0xF, 0xF, true)
+                                   : __builtin_amdgcn_mov_dpp(v, 0xAA, 0xF, 0xF, true);
+        }
+    }
+};
+#endif
 template <class QX>
 SBV_HD void k256_chain_dbl(QX& q) {
     kfe P[QX::N], A[QX::N], B[QX::N], YZ[QX::N], E[QX::N], Z3[QX::N];

@@ -54,21 +54,7 @@ __global__ __launch_bounds__(256) void k_k256_keycheck(const uint8_t* __restrict
     if (active && ok) g.ung_idx[pos] = i;
 }
 
-struct k256_quad_dev {
-    static const int N = 1;
-    kchain3 s[1];
-    int r;
-    __device__ __forceinline__ int role(int) const { return r; }
-    __device__ __forceinline__ void bcast(kfe out[1], const kfe in[1], int src) const {
-        SBV_UNROLL
-        for (int l = 0; l < 9; ++l) {
-            const int v = in[0].v[l];
-            out[0].v[l] = src == 0 ? __builtin_amdgcn_mov_dpp(v, 0x00, 0xF, 0xF, true)
-                        : src == 1 ? __builtin_amdgcn_mov_dpp(v, 0x55, 0xF, 0xF, true)
-                                   : __builtin_amdgcn_mov_dpp(v, 0xAA, 0xF, 0xF, true);
-        }
-    }
-};
+// (exchange policy of the chain on the device: k256_quad_dev, k256_group.h)
 // lanes = groups x 4; only the groups whose tables are built in this batch (cold); table slot of group k = tslot[k]
 __global__ __launch_bounds__(64) void k_k256_chain(const uint8_t* __restrict__ tuples, GroupState g, u32* __restrict__ jstate, u32* __restrict__ bases,
                                                    uint8_t* __restrict__ valid, const u32* __restrict__ tslot, const uint8_t* __restrict__ cold,

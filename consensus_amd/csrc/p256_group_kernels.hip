@@ -92,23 +92,7 @@ static __device__ __forceinline__ void table_prio() {
 #endif
 }
 
-// Exchange policy of the chain on the device: one lane of a quad; a value of lane `src` of the quad reaches all four lanes
-// by DPP quad_perm (v_mov_b32_dpp, a full-rate register move; control = the source lane in all four 2-bit fields).
-struct keychain_quad_dev {
-    static const int N = 1;
-    kchain s[1];
-    int r;
-    __device__ __forceinline__ int role(int) const { return r; }
-    __device__ __forceinline__ void bcast(fe29 out[1], const fe29 in[1], int src) const {
-        SBV_UNROLL
-        for (int l = 0; l < 9; ++l) {
-            const int v = in[0].v[l];
-            out[0].v[l] = src == 0 ? __builtin_amdgcn_mov_dpp(v, 0x00, 0xF, 0xF, true)
-                        : src == 1 ? __builtin_amdgcn_mov_dpp(v, 0x55, 0xF, 0xF, true)
-                                   : __builtin_amdgcn_mov_dpp(v, 0xAA, 0xF, 0xF, true);
-        }
-    }
-};
+// (the chain's exchange policy on the device, keychain_quad_dev, sits next to its host twin in p256_keytab29.h)
 // The table kernels run on BOUNDED grids (round 5): a launch holds at most SBV_TABLE_GRID_BLOCKS workgroups of 64 lanes and every
 // lane walks its share of the work items in a grid-stride loop.  The number of groups is known on the device only, and a batch may
 // now hold up to 65 536 of them (sbv_p256_set_grouping): a grid sized for the capacity would dispatch ~140 000 empty workgroups per

@@ -139,6 +139,26 @@ struct keychain_quad_host {
     int role(int i) const { return i; }
     void bcast(fe29 out[4], const fe29 in[4], int src) const { for (int i = 0; i < 4; ++i) out[i] = in[src]; }
 };
+#if defined(__HIPCC__)
+// Exchange policy of the chain on the device: one lane of a quad; a value of lane `src` of the quad reaches all four lanes
+// by DPP quad_perm (v_mov_b32_dpp, a full-rate register move; control = the source lane in all four 2-bit fields).
+// Used by k_keytab29_chain (p256_group_kernels.hip) and by the device unit tier (tools/devunit.hip).
+struct keychain_quad_dev {
+    static const int N = 1;
+    kchain s[1];
+    int r;
+    __device__ __forceinline__ int role(int) const { return r; }
+    __device__ __forceinline__ void bcast(fe29 out[1], const fe29 in[1], int src) const {
+        SBV_UNROLL
+        for (int l = 0; l < 9; ++l) {
+            const int v = in[0].v[l];
+            out[0].v[l] = src == 0 ? __builtin_amdgcn_mov_dpp(v, 0x00, 0xF, 0xF, true)
+                        : src == 1 ? __builtin_amdgcn_mov_dpp(v, 0x55, 0xF, 0xF, true)
+                                   : __builtin_amdgcn_mov_dpp(v, 0xAA, 0xF, 0xF, true);
+        }
+    }
+};
+#endif
 // One doubling of the quad's point.  QX: N lanes in q.s[0..N), role(i) in 0..3, bcast(out, in, src) = every lane's copy of
 // lane src's value.
 template <class QX>
