@@ -365,6 +365,103 @@ def secp256k1_verify_batch_dev(d_tuples_ptr: int, n: int, d_bitmap_ptr: int, str
     _check(load().sbv_secp256k1_verify_batch_dev(d_tuples_ptr, n, d_bitmap_ptr, stream))
 
 
+def secp256k1_register_keys(keys) -> list:
+    """keys: iterable of 64-byte Qx | Qy -> list of slots of the secp256k1 registry (equal keys share a slot; see include/sbv.h)."""
+    keys = list(keys)
+    blob = b"".join(keys)
+    if len(blob) != 64 * len(keys):
+        raise ValueError("every key must be 64 bytes")
+    out = (ctypes.c_uint32 * max(1, len(keys)))()
+    lib = load()
+    lib.sbv_secp256k1_register_keys.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_register_keys(blob, len(keys), out))
+    return list(out[:len(keys)])
+
+
+def secp256k1_key_count() -> int:
+    rc = load().sbv_secp256k1_key_count()
+    if rc < 0:
+        _check(rc)
+    return rc
+
+
+def secp256k1_clear_keys() -> None:
+    _check(load().sbv_secp256k1_clear_keys())
+
+
+def secp256k1_wide_keys(max_keys: int = 64) -> None:
+    """sbv_secp256k1_wide_keys: cap on the registered secp256k1 slots with a 16-bit comb (0 = none)."""
+    lib = load()
+    lib.sbv_secp256k1_wide_keys.argtypes = [ctypes.c_uint32]
+    _check(lib.sbv_secp256k1_wide_keys(max_keys))
+
+
+def secp256k1_widen_keys(slots) -> None:
+    """sbv_secp256k1_widen_keys: a 16-bit comb of Q for each of these registered slots (the consenters')."""
+    slots = list(slots)
+    arr = (ctypes.c_uint32 * max(1, len(slots)))(*slots)
+    lib = load()
+    lib.sbv_secp256k1_widen_keys.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+    _check(lib.sbv_secp256k1_widen_keys(arr, len(slots)))
+
+
+def secp256k1_wide_key_stats():
+    """(slots holding a 16-bit comb, 16, cap, KiB per comb)"""
+    out = (ctypes.c_uint32 * 4)()
+    lib = load()
+    lib.sbv_secp256k1_wide_key_stats.argtypes = [ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_wide_key_stats(out))
+    return out[0], out[1], out[2], out[3]
+
+
+def secp256k1_wide_selfcheck(slot: int) -> bool:
+    """sbv_secp256k1_wide_selfcheck: the device-built 16-bit comb of `slot` equals the host builder's output byte for byte."""
+    lib = load()
+    lib.sbv_secp256k1_wide_selfcheck.argtypes = [ctypes.c_uint32]
+    rc = lib.sbv_secp256k1_wide_selfcheck(slot)
+    if rc < 0:
+        _check(rc)
+    return rc == 1
+
+
+def secp256k1_verify_batch_keyed(rsh: bytes, slots, n: Optional[int] = None) -> bytes:
+    """Registered-key form: rsh = n x 96 bytes (r | s | hash), slots = n key slots -> accept bitmap."""
+    if n is None:
+        n = len(rsh) // 96
+    arr = (ctypes.c_uint32 * max(1, n))(*slots)
+    out = ctypes.create_string_buffer(max(1, (n + 7) // 8))
+    buf = (ctypes.c_char * len(rsh)).from_buffer_copy(rsh) if n else None
+    lib = load()
+    lib.sbv_secp256k1_verify_batch_keyed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_verify_batch_keyed(buf, arr, n, out))
+    return out.raw[:(n + 7) // 8]
+
+
+def secp256k1_verify_batch_keyed_dev(d_rsh_ptr: int, d_slots_ptr: int, n: int, d_bitmap_ptr: int, stream: int = 0) -> None:
+    lib = load()
+    lib.sbv_secp256k1_verify_batch_keyed_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_verify_batch_keyed_dev(d_rsh_ptr, d_slots_ptr, n, d_bitmap_ptr, stream))
+
+
+def secp256k1_verify_msgs_keyed(msgs, sigs_der, slots) -> bytes:
+    """Device front end: SHA-256(msg) + strict DER parse on the GPU, then registered-key verification over secp256k1."""
+    n = len(msgs)
+    mo = (ctypes.c_uint64 * (n + 1))()
+    so = (ctypes.c_uint64 * (n + 1))()
+    a = b = 0
+    for i in range(n):
+        mo[i], so[i] = a, b
+        a += len(msgs[i]); b += len(sigs_der[i])
+    mo[n], so[n] = a, b
+    arr = (ctypes.c_uint32 * max(1, n))(*slots)
+    out = ctypes.create_string_buffer(max(1, (n + 7) // 8))
+    lib = load()
+    lib.sbv_secp256k1_verify_msgs_keyed.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p,
+                                                    ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_verify_msgs_keyed(b"".join(msgs), mo, b"".join(sigs_der), so, arr, n, out))
+    return out.raw[:(n + 7) // 8]
+
+
 def verify_msgs_keyed(msgs, sigs_der, slots) -> bytes:
     """Device front end: SHA-256(msg) + strict DER parse on the GPU, then registered-key verification."""
     n = len(msgs)

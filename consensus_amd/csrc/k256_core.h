@@ -351,13 +351,14 @@ SBV_HD bool k256_verify_lane(const Scratch& s, size_t i, u32* qtab, const kapt* 
     return ok && match;
 }
 
-// ---- the comb of G, built on the host (or by the emulator): one call per window ------------------------------------------------
-// row[m - 1] = m * 2^(16 j) * G, m = 1..count: a Jacobian chain normalised in chunks with Montgomery's trick
-// (bits = window width: 16 for the device comb; the host signer uses an 8-bit comb of the same shape)
-SBV_HD void k256_build_g_window_bits(int bits, int j, kapt* row, int count) {
+// ---- combs built on the host (or by the emulator): one call per window -------------------------------------------------------
+// row[m - 1] = m * 2^(bits j) * (px, py), m = 1..count, for any affine point of the curve: a Jacobian chain normalised in chunks with
+// Montgomery's trick (the shape of P-256's build_comb_window_of).  The comb of G (bits = 16 for the one-lane kernel, wider for the
+// grouped step, 8 for the host signer) and the reference combs of registered keys (k256_keyed.h) are built by this.
+SBV_HD void k256_build_window_of(const kfe& px, const kfe& py, int bits, int j, kapt* row, int count) {
     kjpt B;
-    kfe_from_words(B.X, k256_gx_words());
-    kfe_from_words(B.Y, k256_gy_words());
+    B.X = px;
+    B.Y = py;
     B.Z = kfe_one();
     B.inf = false;
     for (int d = 0; d < bits * j; ++d) kpt_dbl(B, B);
@@ -397,6 +398,13 @@ SBV_HD void k256_build_g_window_bits(int bits, int j, kapt* row, int count) {
             kapt_store(row + m, X, Y);
         }
     }
+}
+// the comb of G: window j row m - 1 holds m * 2^(bits j) * G
+SBV_HD void k256_build_g_window_bits(int bits, int j, kapt* row, int count) {
+    kfe gx, gy;
+    kfe_from_words(gx, k256_gx_words());
+    kfe_from_words(gy, k256_gy_words());
+    k256_build_window_of(gx, gy, bits, j, row, count);
 }
 SBV_HD void k256_build_g_window(int j, kapt* row, int count) { k256_build_g_window_bits(16, j, row, count); }
 

@@ -37,8 +37,8 @@ struct kchain3 { kfe X, Y, Z; };
 SBV_HD void kfe_pick(kfe& r, bool c, const kfe& a, const kfe& b) { kfe_select(r, c, a, b); }
 
 // pointFromAffine on this curve: coordinates < p, y^2 = x^3 + 7
-SBV_HD bool k256_key_load(const uint8_t* tuples, size_t idx, kfe& x, kfe& y) {
-    const u32* k = tuple_key_words(tuples, idx);
+// (k: the key's 16 dwords, Qx | Qy big-endian)
+SBV_HD bool k256_key_load_words(const u32* k, kfe& x, kfe& y) {
     u256 qx, qy;
     SBV_UNROLL
     for (int l = 0; l < 8; ++l) { qx.v[l] = bswap32(k[7 - l]); qy.v[l] = bswap32(k[8 + 7 - l]); }
@@ -47,6 +47,7 @@ SBV_HD bool k256_key_load(const uint8_t* tuples, size_t idx, kfe& x, kfe& y) {
     kfe_from_words(y, qy);
     return lt256(qx, p_) && lt256(qy, p_) && k256_on_curve(x, y);
 }
+SBV_HD bool k256_key_load(const uint8_t* tuples, size_t idx, kfe& x, kfe& y) { return k256_key_load_words(tuple_key_words(tuples, idx), x, y); }
 
 // ---- chain: one doubling on a quad ------------------------------------------------------------------------------------------
 // level 1: role 0 -> X X, role 1 -> Y Y, roles 2, 3 -> Y Z
@@ -121,14 +122,15 @@ SBV_HD void kchain3_store_part(u32* dst, const kchain3& s, int role) {
 }
 SBV_HD void kchain3_load(kchain3& s, const u32* src) { kfe_load_raw(s.X, src); kfe_load_raw(s.Y, src + 9); kfe_load_raw(s.Z, src + 18); }
 
-// the chain of one chunk of windows for one quad: records B_j and 16 B_j of windows j_first..j_last
-template <class QX>
-SBV_HD void k256_chain_run(QX& q, const uint8_t* tuples, u32 gidx, const GroupState& g, u32* jstate, u32* bases, uint8_t* valid,
-                           int j_first, int j_last) {
+// the chain of one chunk of windows for one quad: records B_j and 16 B_j of windows j_first..j_last.  key(x, y) loads the key of
+// chain `gidx` and gives pointFromAffine's verdict: from the batch's tuples for the grouped step (k256_chain_run), from the
+// registry's key array for a registered slot (k256_keyed.h)
+template <class QX, class KeyFn>
+SBV_HD void k256_chain_run_key(QX& q, KeyFn key, u32 gidx, u32* jstate, u32* bases, uint8_t* valid, int j_first, int j_last) {
     u32* st = jstate + (size_t)gidx * SBV_K256_STATE_WORDS;
     if (j_first == 0) {
         kfe x, y;
-        const bool ok = k256_key_load(tuples, g.group_rep[gidx], x, y);
+        const bool ok = key(x, y);
         SBV_UNROLL
         for (int i = 0; i < QX::N; ++i) {
             if (q.role(i) == 0) *valid = ok ? 1 : 0;
@@ -154,6 +156,11 @@ SBV_HD void k256_chain_run(QX& q, const uint8_t* tuples, u32 gidx, const GroupSt
     }
     SBV_UNROLL
     for (int i = 0; i < QX::N; ++i) kchain3_store_part(st, q.s[i], q.role(i));
+}
+template <class QX>
+SBV_HD void k256_chain_run(QX& q, const uint8_t* tuples, u32 gidx, const GroupState& g, u32* jstate, u32* bases, uint8_t* valid,
+                           int j_first, int j_last) {
+    k256_chain_run_key(q, [&](kfe& x, kfe& y) { return k256_key_load(tuples, g.group_rep[gidx], x, y); }, gidx, jstate, bases, valid, j_first, j_last);
 }
 
 // ---- rows ----------------------------------------------------------------------------------------------------------------

@@ -34,6 +34,7 @@
 #include "ed25519_kernels.h"
 #include "p256_kernels.h"
 #include "k256_core.h"
+#include "k256_keyed_kernels.h"
 
 namespace {
 
@@ -146,6 +147,16 @@ struct Context {
     uint8_t* d_ed_wtab = nullptr;          // comb w (SBV_ED_HOT_COMB_BYTES) belongs to slot ed_wide_slots[w]
     size_t ed_wtab_cap = 0;
     std::vector<u32> ed_wide_slots;
+    // registered secp256k1 keys (k256_keyed.h; sbv_secp256k1_register_keys): the default context's half of g_k256reg, allocated on the
+    // first registration.  Slot s: the 64 key bytes, valid byte, 8-bit comb of Q, index of its 16-bit comb in d_k256_wtab (or SBV_K256_WIDE_NONE)
+    sbv::kapt* d_k256_ktab = nullptr;
+    uint8_t* d_k256_kvalid = nullptr;
+    uint8_t* d_k256_kkeys = nullptr;
+    u32* d_k256_kwidx = nullptr;
+    size_t k256_key_cap = 0, k256_nkeys = 0;
+    sbv::kapt* d_k256_wtab = nullptr;      // comb w (SBV_K256_WIDE_ENTRIES) belongs to slot k256_wide_slots[w]
+    size_t k256_wtab_cap = 0;
+    std::vector<u32> k256_wide_slots;
     int profiling = 0;                     // 0 off, 1 = step triples + dominant-kernel pairs, 2 = dominant-kernel pairs only
     std::vector<hipEvent_t> prof_events;   // triples: before prep, after prep, after verify
     std::vector<hipEvent_t> prof_dom;      // pairs around the dominant kernel of grouped batches (nullptr pair = ungrouped)
@@ -1100,6 +1111,9 @@ int shutdown_context(Context& c) {
     for (void* p : {(void*)c.d_ed_ktab, (void*)c.d_ed_kvalid, (void*)c.d_ed_kenc, (void*)c.d_ed_kwidx, (void*)c.d_ed_wtab}) if (p) (void)hipFree(p);
     c.d_ed_ktab = nullptr; c.d_ed_kvalid = nullptr; c.d_ed_kenc = nullptr; c.d_ed_kwidx = nullptr; c.d_ed_wtab = nullptr;
     c.ed_key_cap = c.ed_nkeys = 0; c.ed_wtab_cap = 0; c.ed_wide_slots.clear();
+    for (void* p : {(void*)c.d_k256_ktab, (void*)c.d_k256_kvalid, (void*)c.d_k256_kkeys, (void*)c.d_k256_kwidx, (void*)c.d_k256_wtab}) if (p) (void)hipFree(p);
+    c.d_k256_ktab = nullptr; c.d_k256_kvalid = nullptr; c.d_k256_kkeys = nullptr; c.d_k256_kwidx = nullptr; c.d_k256_wtab = nullptr;
+    c.k256_key_cap = c.k256_nkeys = 0; c.k256_wtab_cap = 0; c.k256_wide_slots.clear();
     if (c.h_small_in) (void)hipHostFree(c.h_small_in);
     if (c.h_small_out) (void)hipHostFree(c.h_small_out);
     c.h_small_in = c.h_small_out = nullptr; c.d_small_in = c.d_small_out = nullptr;
@@ -1131,10 +1145,12 @@ int shutdown_context(Context& c) {
 }  // namespace
 
 static void ed_registry_forget();
+static void k256_registry_forget();
 extern "C" int sbv_shutdown(void) {
     std::unique_lock<std::shared_mutex> rl(g_reg_mu);
     g_reg = Registry();
     ed_registry_forget();           // takes g_edreg_mu: g_reg_mu -> g_edreg_mu -> g_mu
+    k256_registry_forget();         // takes g_k256reg_mu alone
     std::lock_guard<std::mutex> lk(g_mu);
     rccl_teardown();
     for (auto& up : g_ctxs) {
@@ -2359,6 +2375,349 @@ extern "C" int sbv_ed25519_verify_msgs_keyed(const uint8_t* sigs, const uint8_t*
                                                                    reinterpret_cast<uint8_t*>(c.d_qtab), c.stream));
             HIP_TRY(SBV_EDEVICE, hipEventRecord(after_prep, c.stream));
             return enqueue_ed_keyed(c, nullptr, c.d_slots, n, c.d_bitmap, c.stream, true);
+        });
+}
+
+// ---- registered secp256k1 keys (k256_keyed.h; include/sbv.h: sbv_secp256k1_register_keys) -------------------------------------
+// The Ed25519 registry's shape on this curve.  Process-wide on the host: the slot index (64 key bytes -> slot), every registered key,
+// its valid flag and the widening cap.  On the default context's device, per slot: the key bytes (the chain's input), the valid byte,
+// the 8-bit comb of Q (270 KiB, built on the device by the grouped step's chain / rows / fill lanes) and for widened slots a 16-bit
+// comb (35.7 MB, built on the device from the 8-bit comb).  The registry shares nothing with the P-256 registry (Context::key_index,
+// d_ktab) or with either key-table cache (grp.kc, k256pool.kc): a byte string can be a point of both curves.
+// Lock order: g_k256reg_mu -> g_mu -> Context::mu; the verify entries take the context alone and read its half.
+namespace {
+struct K256Registry {
+    std::vector<std::string> keys;                    // slot -> the 64 key bytes
+    std::unordered_map<std::string, u32> index;       // key bytes -> slot
+    std::vector<uint8_t> valid;                       // slot -> the key is a point of the curve
+    u32 wide_max = 64;                                // sbv_secp256k1_wide_keys
+} g_k256reg;
+std::mutex g_k256reg_mu;
+constexpr u32 kK256RegBuildKeys = 512;               // slots per pass of the comb builder: 78 MB of scratch while it runs
+
+sbv::K256KeyedRegistry k256_reg_view(const Context& c) {
+    sbv::K256KeyedRegistry r;
+    r.ktab = c.d_k256_ktab; r.kvalid = c.d_k256_kvalid;
+    r.wtab = c.d_k256_wtab; r.kwidx = c.k256_wide_slots.empty() ? nullptr : c.d_k256_kwidx;
+    r.nkeys = (u32)c.k256_nkeys;
+    return r;
+}
+
+// c.mu held, the device current: room for `want` slots.  Doubles from 64 slots, copies the live slots on the device; a failure leaves
+// the old arrays (and so the registry) as they were.
+int k256_reg_reserve(Context& c, size_t want) {
+    if (want <= c.k256_key_cap) return SBV_OK;
+    size_t cap = c.k256_key_cap ? c.k256_key_cap : 64;
+    while (cap < want) cap *= 2;
+    if (cap > SBV_K256_REG_MAX_KEYS) cap = SBV_K256_REG_MAX_KEYS;
+    sbv::kapt* kt = nullptr; uint8_t* kv = nullptr; uint8_t* kk = nullptr; u32* kw = nullptr;
+    auto drop = [&] { for (void* p : {(void*)kt, (void*)kv, (void*)kk, (void*)kw}) if (p) (void)hipFree(p); (void)hipGetLastError(); };
+    if (hipMalloc(&kt, cap * (size_t)SBV_K256_KEYTAB_ENTRIES * sizeof(sbv::kapt)) != hipSuccess || hipMalloc(&kv, cap) != hipSuccess ||
+        hipMalloc(&kk, cap * SBV_K256_KEY_BYTES) != hipSuccess || hipMalloc(&kw, cap * sizeof(u32)) != hipSuccess) {
+        drop();
+        g_err = "sbv_secp256k1_register_keys: no device memory for the registry";
+        return SBV_ENOMEM;
+    }
+    const size_t n = c.k256_nkeys;
+    hipError_t e = hipDeviceSynchronize();          // nothing in flight reads the old arrays any more
+    if (e == hipSuccess && n) e = hipMemcpy(kt, c.d_k256_ktab, n * (size_t)SBV_K256_KEYTAB_ENTRIES * sizeof(sbv::kapt), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(kv, c.d_k256_kvalid, n, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(kk, c.d_k256_kkeys, n * SBV_K256_KEY_BYTES, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(kw, c.d_k256_kwidx, n * sizeof(u32), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);     // device-to-device copies are ordered in the null stream only (see memset_now)
+    if (e == hipSuccess) e = memset_now(kw + n, 0xFF, (cap - n) * sizeof(u32));
+    if (e != hipSuccess) { drop(); return fail(SBV_EDEVICE, "sbv_secp256k1_register_keys: growing the registry", e); }
+    for (void* p : {(void*)c.d_k256_ktab, (void*)c.d_k256_kvalid, (void*)c.d_k256_kkeys, (void*)c.d_k256_kwidx}) if (p) (void)hipFree(p);
+    c.d_k256_ktab = kt; c.d_k256_kvalid = kv; c.d_k256_kkeys = kk; c.d_k256_kwidx = kw;
+    c.k256_key_cap = cap;
+    return SBV_OK;
+}
+
+// c.mu held, the device current: room for `want` 16-bit combs (doubling, at most the cap), the combs there copied on the device
+int k256_wide_reserve(Context& c, size_t want, size_t cap_max) {
+    if (want <= c.k256_wtab_cap) return SBV_OK;
+    size_t cap = c.k256_wtab_cap ? c.k256_wtab_cap : 1;
+    while (cap < want) cap *= 2;
+    if (cap > cap_max) cap = cap_max;
+    sbv::kapt* w = nullptr;
+    if (hipMalloc(&w, cap * SBV_K256_WIDE_COMB_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        g_err = "sbv_secp256k1_widen_keys: no device memory for the 16-bit combs";
+        return SBV_ENOMEM;
+    }
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess && !c.k256_wide_slots.empty())
+        e = hipMemcpy(w, c.d_k256_wtab, c.k256_wide_slots.size() * SBV_K256_WIDE_COMB_BYTES, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) { (void)hipFree(w); return fail(SBV_EDEVICE, "sbv_secp256k1_widen_keys: growing the comb pool", e); }
+    if (c.d_k256_wtab) (void)hipFree(c.d_k256_wtab);
+    c.d_k256_wtab = w;
+    c.k256_wtab_cap = cap;
+    return SBV_OK;
+}
+
+// one chunk (m <= c.cap) of keyed records on `stream`: stage A on the records into the scratch planes, then the keyed stage B
+int enqueue_k256_keyed(Context& c, const uint8_t* d_recs, const u32* d_slots, size_t m, uint8_t* d_bitmap, hipStream_t stream, hipEvent_t after_prep = nullptr) {
+    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_verify_keyed(d_recs, d_slots, m, scratch_view(c), k256_reg_view(c), c.d_k256_gcomb, c.k256_gbits, d_bitmap, stream, after_prep));
+    return SBV_OK;
+}
+// the table every keyed call needs: the comb of G of the grouped step (which borrows the one-lane kernel's at 16 bits)
+int ensure_k256_keyed(Context& c) {
+    const int rc = ensure_k256_table(c);
+    return rc == SBV_OK ? ensure_k256_gcomb(c) : rc;
+}
+}  // namespace
+
+static void k256_registry_forget() {
+    std::lock_guard<std::mutex> lk(g_k256reg_mu);
+    const u32 wm = g_k256reg.wide_max;
+    g_k256reg = K256Registry();
+    g_k256reg.wide_max = wm;
+}
+
+extern "C" int sbv_secp256k1_register_keys(const uint8_t* keys, size_t m, uint32_t* slots_out) {
+    std::lock_guard<std::mutex> rl(g_k256reg_mu);
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!keys || !slots_out) { g_err = "null pointer"; return SBV_EINVAL; }
+    std::vector<u32> out(m);
+    std::string fresh;                              // keys that need a slot, in slot order
+    std::unordered_map<std::string, u32> pending;
+    for (size_t i = 0; i < m; ++i) {
+        const std::string k((const char*)keys + SBV_K256_KEY_BYTES * i, SBV_K256_KEY_BYTES);
+        auto it = g_k256reg.index.find(k);
+        if (it != g_k256reg.index.end()) { out[i] = it->second; continue; }
+        auto pt = pending.find(k);
+        if (pt != pending.end()) { out[i] = pt->second; continue; }
+        const u32 slot = (u32)(g_k256reg.keys.size() + pending.size());
+        pending.emplace(k, slot);
+        fresh += k;
+        out[i] = slot;
+    }
+    const size_t nf = pending.size();
+    if (g_k256reg.keys.size() + nf > SBV_K256_REG_MAX_KEYS) { g_err = "sbv_secp256k1_register_keys: more than 65536 keys"; return SBV_EINVAL; }
+    if (nf) {
+        HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+        const int rc = k256_reg_reserve(c, c.k256_nkeys + nf);
+        if (rc != SBV_OK) return rc;
+        // the new slots lie beyond k256_nkeys: no batch reads them until the count below is raised
+        const size_t s0 = c.k256_nkeys;
+        const u32 pass = nf < kK256RegBuildKeys ? (u32)nf : kK256RegBuildKeys;
+        u32* d_work = nullptr;
+        if (hipMalloc(&d_work, sbv::k256_reg_build_words(pass) * sizeof(u32)) != hipSuccess) {
+            (void)hipGetLastError();
+            g_err = "sbv_secp256k1_register_keys: no device memory for the builder";
+            return SBV_ENOMEM;
+        }
+        std::vector<uint8_t> valid(nf);
+        hipError_t e = hipMemcpy(c.d_k256_kkeys + s0 * SBV_K256_KEY_BYTES, fresh.data(), fresh.size(), hipMemcpyHostToDevice);
+        for (size_t off = 0; off < nf && e == hipSuccess; off += pass) {
+            const u32 cnt = (u32)(nf - off < pass ? nf - off : pass);
+            e = sbv::launch_k256_reg_build(c.d_k256_kkeys, (u32)(s0 + off), cnt, d_work, c.d_k256_ktab, c.d_k256_kvalid, c.stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c.stream);        // the next pass reuses the scratch
+        }
+        (void)hipFree(d_work);                      // build scratch lives for the call only
+        if (e == hipSuccess) e = hipMemcpy(valid.data(), c.d_k256_kvalid + s0, nf, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return fail(SBV_EDEVICE, "sbv_secp256k1_register_keys: building the combs", e);
+        c.k256_nkeys += nf;
+        for (size_t i = 0; i < nf; ++i) {
+            const std::string k = fresh.substr(i * SBV_K256_KEY_BYTES, SBV_K256_KEY_BYTES);
+            g_k256reg.index.emplace(k, (u32)g_k256reg.keys.size());
+            g_k256reg.keys.push_back(k);
+            g_k256reg.valid.push_back(valid[i]);
+        }
+    }
+    memcpy(slots_out, out.data(), m * sizeof(u32));
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_key_count(void) {
+    SBV_ENTER(c);
+    return c.ready ? (int)c.k256_nkeys : SBV_ENOTINIT;
+}
+
+extern "C" int sbv_secp256k1_clear_keys(void) {
+    std::lock_guard<std::mutex> rl(g_k256reg_mu);
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+    if (c.d_k256_kwidx && c.k256_key_cap) HIP_TRY(SBV_EDEVICE, memset_now(c.d_k256_kwidx, 0xFF, c.k256_key_cap * sizeof(u32)));
+    c.k256_nkeys = 0;                // the allocations stay for the next registry
+    c.k256_wide_slots.clear();
+    const u32 wm = g_k256reg.wide_max;
+    g_k256reg = K256Registry();
+    g_k256reg.wide_max = wm;
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_wide_keys(uint32_t max_keys) {
+    std::lock_guard<std::mutex> rl(g_k256reg_mu);
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (max_keys > 4096) { g_err = "sbv_secp256k1_wide_keys: at most 4096 keys"; return SBV_EINVAL; }
+    g_k256reg.wide_max = max_keys;
+    if (c.k256_wide_slots.size() <= max_keys) return SBV_OK;
+    // fewer than are wide: the first max_keys widened slots keep their combs, the others go back to their 8-bit combs
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+    const u32 none = SBV_K256_WIDE_NONE;
+    for (size_t w = max_keys; w < c.k256_wide_slots.size(); ++w)
+        HIP_TRY(SBV_EDEVICE, hipMemcpy(c.d_k256_kwidx + c.k256_wide_slots[w], &none, sizeof(u32), hipMemcpyHostToDevice));
+    c.k256_wide_slots.resize(max_keys);
+    if (max_keys == 0 && c.d_k256_wtab) { (void)hipFree(c.d_k256_wtab); c.d_k256_wtab = nullptr; c.k256_wtab_cap = 0; }
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_widen_keys(const uint32_t* slots, size_t m) {
+    std::lock_guard<std::mutex> rl(g_k256reg_mu);
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!slots) { g_err = "null pointer"; return SBV_EINVAL; }
+    for (size_t i = 0; i < m; ++i)
+        if (slots[i] >= c.k256_nkeys) { g_err = "sbv_secp256k1_widen_keys: unregistered slot"; return SBV_EINVAL; }
+    // the slots that get a comb now: registered, a point, not wide yet, within the cap (the others stay narrow: no error)
+    std::vector<u32> todo;
+    for (size_t i = 0; i < m; ++i) {
+        const u32 s = slots[i];
+        if (!g_k256reg.valid[s]) continue;
+        if (std::find(c.k256_wide_slots.begin(), c.k256_wide_slots.end(), s) != c.k256_wide_slots.end()) continue;
+        if (std::find(todo.begin(), todo.end(), s) != todo.end()) continue;
+        if (c.k256_wide_slots.size() + todo.size() >= g_k256reg.wide_max) break;
+        todo.push_back(s);
+    }
+    if (todo.empty()) return SBV_OK;
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const size_t w0 = c.k256_wide_slots.size();
+    const int rc = k256_wide_reserve(c, w0 + todo.size(), g_k256reg.wide_max);
+    if (rc != SBV_OK) return rc;
+    u32* d_tmp = nullptr;
+    if (hipMalloc(&d_tmp, sbv::k256_widetab_tmp_words() * sizeof(u32)) != hipSuccess) {
+        (void)hipGetLastError();
+        g_err = "sbv_secp256k1_widen_keys: no device memory for the builder";
+        return SBV_ENOMEM;
+    }
+    hipError_t e = hipSuccess;
+    if (c.busy_valid) e = hipStreamWaitEvent(c.stream, c.busy, 0);
+    for (size_t i = 0; i < todo.size() && e == hipSuccess; ++i)       // one after the other on the stream: they share the scratch
+        e = sbv::launch_k256_widetab(c.d_k256_ktab, todo[i], d_tmp, c.d_k256_wtab, (u32)(w0 + i), c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    (void)hipFree(d_tmp);                           // build scratch lives for the call only
+    if (e != hipSuccess) return fail(SBV_EDEVICE, "sbv_secp256k1_widen_keys: building the combs", e);
+    // publish: a comb is used only once it is complete
+    for (size_t i = 0; i < todo.size(); ++i) {
+        const u32 w = (u32)(w0 + i);
+        e = hipMemcpy(c.d_k256_kwidx + todo[i], &w, sizeof(u32), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            const u32 none = SBV_K256_WIDE_NONE;
+            for (size_t j = 0; j < i; ++j) (void)hipMemcpy(c.d_k256_kwidx + todo[j], &none, sizeof(u32), hipMemcpyHostToDevice);
+            return fail(SBV_EDEVICE, "sbv_secp256k1_widen_keys: publish", e);
+        }
+    }
+    c.k256_wide_slots.insert(c.k256_wide_slots.end(), todo.begin(), todo.end());
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_wide_key_stats(uint32_t out[4]) {
+    std::lock_guard<std::mutex> rl(g_k256reg_mu);
+    SBV_ENTER(c);
+    if (!c.ready) return SBV_ENOTINIT;
+    if (!out) return SBV_EINVAL;
+    out[0] = (u32)c.k256_wide_slots.size(); out[1] = SBV_K256_WIDE_BITS; out[2] = g_k256reg.wide_max;
+    out[3] = (u32)(SBV_K256_WIDE_COMB_BYTES >> 10);
+    return SBV_OK;
+}
+
+// 1 = the device-resident 16-bit comb of `slot` equals the host builder's comb of Q (k256_build_window_of) byte for byte
+extern "C" int sbv_secp256k1_wide_selfcheck(uint32_t slot) {
+    std::lock_guard<std::mutex> rl(g_k256reg_mu);
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    size_t w = c.k256_wide_slots.size();
+    for (size_t i = 0; i < c.k256_wide_slots.size(); ++i) if (c.k256_wide_slots[i] == slot) w = i;
+    if (w == c.k256_wide_slots.size()) { g_err = "sbv_secp256k1_wide_selfcheck: the slot has no wide comb"; return SBV_EINVAL; }
+    std::vector<sbv::kapt> want(SBV_K256_WIDE_ENTRIES), got(SBV_K256_WIDE_ENTRIES);
+    if (!sbv::host_build_k256_wide_comb((const uint8_t*)g_k256reg.keys[slot].data(), want.data())) return 0;      // only points are widened
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), c.d_k256_wtab + w * SBV_K256_WIDE_ENTRIES, SBV_K256_WIDE_COMB_BYTES, hipMemcpyDeviceToHost));
+    return memcmp(got.data(), want.data(), SBV_K256_WIDE_COMB_BYTES) == 0 ? 1 : 0;
+}
+
+extern "C" int sbv_secp256k1_verify_batch_keyed_dev(const void* d_rsh, const void* d_slots, size_t n, void* d_bitmap, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!d_rsh || !d_slots || !d_bitmap || (reinterpret_cast<uintptr_t>(d_rsh) & 15)) { g_err = "null or misaligned device pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (c.k256_nkeys == 0) {         // every slot is out of range: every record is a reject
+        HIP_TRY(SBV_EDEVICE, hipMemsetAsync(d_bitmap, 0, (n + 7) / 8, stream));
+        return SBV_OK;
+    }
+    const int rc = ensure_k256_keyed(c);
+    if (rc != SBV_OK) return rc;
+    const uint8_t* src = static_cast<const uint8_t*>(d_rsh);
+    const u32* sl = static_cast<const u32*>(d_slots);
+    uint8_t* dst = static_cast<uint8_t*>(d_bitmap);
+    return run_chunks_dev(c, n, stream, true, [&](size_t off, size_t m, hipEvent_t after_prep, hipEvent_t*, int*) {
+        return enqueue_k256_keyed(c, src + off * SBV_K256_REC_BYTES, sl + off, m, dst + off / 8, stream, after_prep);
+    });
+}
+
+extern "C" int sbv_secp256k1_verify_batch_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* accept_bitmap) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!rsh || !slots || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (c.k256_nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const int rc = ensure_k256_keyed(c);
+    if (rc != SBV_OK) return rc;
+    return run_chunks_host(c, n, accept_bitmap, t0, true,
+        [&](size_t off, size_t m) {
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, rsh + off * SBV_K256_REC_BYTES, m * SBV_K256_REC_BYTES, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots + off, m * sizeof(u32), hipMemcpyHostToDevice, c.stream));
+            return SBV_OK;
+        },
+        [&](size_t, size_t m, hipEvent_t after_prep) { return enqueue_k256_keyed(c, c.d_tuples, c.d_slots, m, c.d_bitmap, c.stream, after_prep); });
+}
+
+// the message front end (SHA-256 + strict DER -> r | s | hash records, curve-agnostic) in front of the keyed step
+extern "C" int sbv_secp256k1_verify_msgs_keyed(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs,
+                                               const uint64_t* sig_offsets, const uint32_t* slots, size_t n, uint8_t* accept_bitmap) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!msg_offsets || !sig_offsets || !slots || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
+    size_t mbytes = 0, sbytes = 0;
+    int rc = check_offsets(msg_offsets, n, msgs, mbytes);
+    if (rc == SBV_OK) rc = check_offsets(sig_offsets, n, sigs, sbytes);
+    if (rc != SBV_OK) return rc;
+    if (c.k256_nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    if ((rc = ensure_k256_keyed(c)) != SBV_OK) return rc;
+    if ((rc = grow(c.d_msgs, c.msgs_cap, mbytes + 16)) != SBV_OK) return rc;
+    if ((rc = grow(c.d_sigs, c.sigs_cap, sbytes + 16)) != SBV_OK) return rc;
+    if ((rc = grow(c.d_moff, c.moff_cap, n + 1)) != SBV_OK) return rc;
+    if ((rc = grow(c.d_soff, c.soff_cap, n + 1)) != SBV_OK) return rc;
+    return run_chunks_host(c, n, accept_bitmap, t0, true,
+        [&](size_t, size_t) {
+            if (mbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_msgs, msgs, mbytes, hipMemcpyHostToDevice, c.stream));
+            if (sbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs, sigs, sbytes, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_moff, msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_soff, sig_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots, n * sizeof(u32), hipMemcpyHostToDevice, c.stream));
+            return SBV_OK;
+        },
+        [&](size_t, size_t, hipEvent_t after_prep) {          // prep_us: front end + stage A
+            HIP_TRY(SBV_EDEVICE, sbv::launch_msg_frontend(c.d_msgs, c.d_moff, c.d_sigs, c.d_soff, n, reinterpret_cast<u32*>(c.d_tuples), c.stream, 0, 0, mbytes, sbytes));
+            return enqueue_k256_keyed(c, c.d_tuples, c.d_slots, n, c.d_bitmap, c.stream, after_prep);
         });
 }
 

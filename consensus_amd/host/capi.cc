@@ -77,6 +77,13 @@ uint64_t sbvh_backend_keyed_batches(void* h) { return ((VHandle*)h)->be->keyed_b
 uint64_t sbvh_backend_widened_keys(void* h) { return ((VHandle*)h)->be->widened_keys(); }
 // the backend's Ed25519 registry as the Verifier sees it: slot of a 32-byte encoding (-1 = no registry)
 long sbvh_backend_register_ed25519(void* h, const uint8_t* a32) { return ((VHandle*)h)->be->register_key_ed25519(a32); }
+// the secp256k1 registry of the backend: the slot of a 64-byte key (-1: no registry), and the slots of the last keyed batch
+long sbvh_backend_register_k256(void* h, const uint8_t* q64) { return ((VHandle*)h)->be->register_key_k256(q64); }
+size_t sbvh_backend_last_k256_slots(void* h, uint32_t* out, size_t cap) {
+    const std::vector<uint32_t> s = ((VHandle*)h)->be->last_k256_slots();
+    for (size_t i = 0; i < s.size() && i < cap; ++i) out[i] = s[i];
+    return s.size();
+}
 void sbvh_register_consenter(void* h, uint64_t id, const uint8_t q[64]) { ((VHandle*)h)->v->RegisterConsenter(id, q); }
 void sbvh_register_client(void* h, const char* client, const uint8_t q[64]) { ((VHandle*)h)->v->RegisterClient(client, q); }
 // 0: clients registered from now on get no comb slot on the device (their request signatures go as generic tuples)

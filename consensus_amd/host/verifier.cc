@@ -176,6 +176,26 @@ class SbvBackend : public Backend {
         if (rc_ != SBV_OK) return rc_;
         return sbv_secp256k1_verify_batch(tuples, n, bitmap);
     }
+    long register_key_k256(const uint8_t q[64]) override {
+        if (rc_ != SBV_OK) return -1;
+        uint32_t slot = 0;
+        return sbv_secp256k1_register_keys(q, 1, &slot) == SBV_OK ? (long)slot : -1;
+    }
+    void widen_key_k256(long slot) override {
+        if (rc_ != SBV_OK || slot < 0) return;
+        const uint32_t s = (uint32_t)slot;
+        (void)sbv_secp256k1_widen_keys(&s, 1);         // best effort: without its 16-bit comb the key keeps the 8-bit one
+    }
+    int verify_k256_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* bitmap) override {
+        if (rc_ != SBV_OK) return rc_;
+        return sbv_secp256k1_verify_batch_keyed(rsh, slots, n, bitmap);
+    }
+    int verify_k256_msgs_keyed(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff,
+                               const uint32_t* slots, size_t n, uint8_t* bitmap) override {
+        if (rc_ != SBV_OK) return rc_;
+        if (n > ((size_t)1 << 21)) return -2;          // beyond the entry's limit: the caller takes the record path
+        return sbv_secp256k1_verify_msgs_keyed(msgs, moff, sigs, soff, slots, n, bitmap);
+    }
     void* host_alloc(size_t bytes) override { return rc_ == SBV_OK ? sbv_host_alloc(bytes) : nullptr; }
     void host_free(void* p) override { sbv_host_free(p); }
     int verify_msgs_keyed(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff,
@@ -242,7 +262,7 @@ class CallbackBackend : public Backend {
         std::lock_guard<std::mutex> lk(mu_);
         if ((size_t)slot < keys_.size() && std::find(widened_.begin(), widened_.end(), slot) == widened_.end()) widened_.push_back(slot);
     }
-    uint64_t widened_keys() override { std::lock_guard<std::mutex> lk(mu_); return widened_.size() + ed_widened_.size(); }
+    uint64_t widened_keys() override { std::lock_guard<std::mutex> lk(mu_); return widened_.size() + ed_widened_.size() + k256_widened_.size(); }
     // the stand-in knows which scheme its test runs: the same callback receives the 128-byte tuples
     int verify_ed25519(const uint8_t* tuples128, size_t n, uint8_t* bitmap) override { return fn_(tuples128, n, bitmap, user_); }
     // stand-in for the Ed25519 registry: slots index a host-side list of encodings (keyed by the bytes, like the library); the keyed
@@ -295,7 +315,55 @@ class CallbackBackend : public Backend {
         return verify_ed25519_keyed(rsk.data(), slots, n, bitmap);
     }
     int verify_k256(const uint8_t* tuples, size_t n, uint8_t* bitmap) override { return fn_(tuples, n, bitmap, user_); }
+    // stand-in for the secp256k1 registry: a key list of its own (a slot of it means nothing to verify_keyed, as in the library); the
+    // keyed forms re-attach the keys and go through the same callback, an out-of-range slot is a reject
+    long register_key_k256(const uint8_t q[64]) override {
+        if (!registry_) return -1;
+        std::lock_guard<std::mutex> lk(mu_);
+        const std::string k((const char*)q, 64);
+        for (size_t i = 0; i < k256_keys_.size(); ++i) if (k256_keys_[i] == k) return (long)i;
+        k256_keys_.push_back(k);
+        return (long)k256_keys_.size() - 1;
+    }
+    void widen_key_k256(long slot) override {
+        if (!registry_ || slot < 0) return;
+        std::lock_guard<std::mutex> lk(mu_);
+        if ((size_t)slot < k256_keys_.size() && std::find(k256_widened_.begin(), k256_widened_.end(), slot) == k256_widened_.end()) k256_widened_.push_back(slot);
+    }
+    int verify_k256_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* bitmap) override {
+        if (!registry_) return -2;
+        std::vector<uint8_t> tuples(n * 160, 0);
+        std::vector<uint8_t> known(n, 0);
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            ++keyed_batches_;
+            last_k256_slots_.assign(slots, slots + n);
+            for (size_t i = 0; i < n; ++i) {
+                memcpy(&tuples[i * 160], rsh + i * 96, 96);
+                if (slots[i] < k256_keys_.size()) { memcpy(&tuples[i * 160 + 96], k256_keys_[slots[i]].data(), 64); known[i] = 1; }
+            }
+        }
+        const int rc = fn_(tuples.data(), n, bitmap, user_);
+        for (size_t i = 0; i < n; ++i) if (!known[i]) bitmap[i >> 3] &= (uint8_t)~(1u << (i & 7));
+        return rc;
+    }
+    int verify_k256_msgs_keyed(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff,
+                               const uint32_t* slots, size_t n, uint8_t* bitmap) override {
+        if (!registry_) return -2;
+        std::vector<uint8_t> rsh(n * 96, 0);
+        parallel_chunks(n, [&](size_t lo, size_t hi) {
+            for (size_t i = lo; i < hi; ++i) {
+                sbv_p256_parse_der(sigs + soff[i], (size_t)(soff[i + 1] - soff[i]), &rsh[i * 96]);   // failure leaves r = s = 0
+                sha256(msgs + moff[i], (size_t)(moff[i + 1] - moff[i]), &rsh[i * 96 + 64]);
+            }
+        });
+        return verify_k256_keyed(rsh.data(), slots, n, bitmap);
+    }
+    std::vector<uint32_t> last_k256_slots() override { std::lock_guard<std::mutex> lk(mu_); return last_k256_slots_; }
  private:
+    std::vector<std::string> k256_keys_;
+    std::vector<long> k256_widened_;
+    std::vector<uint32_t> last_k256_slots_;
     backend_fn fn_;
     void* user_;
     bool registry_;
@@ -417,6 +485,27 @@ int Coalescer::submit_many_k256(const uint8_t* tuples, size_t n, uint8_t* bitmap
     return be_->verify_k256(tuples, n, bitmap);
 }
 
+int Coalescer::submit_many_k256_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* bitmap) {
+    const int rc = be_->verify_k256_keyed(rsh, slots, n, bitmap);
+    if (rc != -2) {
+        std::lock_guard<SpinLock> lk(mu_);
+        ++st_.batches;
+        if (n > st_.max_batch) st_.max_batch = n;
+    }
+    return rc;
+}
+
+int Coalescer::submit_many_k256_msgs_keyed(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint32_t* slots,
+                                           size_t n, uint8_t* bitmap) {
+    const int rc = be_->verify_k256_msgs_keyed(msgs, moff, sigs, soff, slots, n, bitmap);
+    if (rc != -2) {
+        std::lock_guard<SpinLock> lk(mu_);
+        ++st_.batches;
+        if (n > st_.max_batch) st_.max_batch = n;
+    }
+    return rc;
+}
+
 int Coalescer::submit_many_msgs_keyed(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint32_t* slots,
                                       size_t n, uint8_t* bitmap) {
     const int rc = be_->verify_msgs_keyed(msgs, moff, sigs, soff, slots, n, bitmap);
@@ -534,9 +623,18 @@ void Coalescer::serve_as_leader(const std::atomic<bool>* own_done) {
                 rc = be_->verify_ed25519(tuples.data(), n, bitmap.data());
             }
         } else if (batch[0]->k256) {     // secp256k1 Verifier: the same 160-byte tuples, the other curve
-            tuples.resize(n * 160);
-            for (size_t i = 0; i < n; ++i) memcpy(&tuples[i * 160], batch[i]->tuple, 160);
-            rc = be_->verify_k256(tuples.data(), n, bitmap.data());
+            rc = -2;
+            if (all_keyed) {             // a commit burst of registered consenters: records r|s|hash + slots of the curve's registry
+                tuples.resize(n * 96);
+                std::vector<uint32_t> slots(n);
+                for (size_t i = 0; i < n; ++i) { memcpy(&tuples[i * 96], batch[i]->tuple, 96); slots[i] = (uint32_t)batch[i]->slot; }
+                rc = be_->verify_k256_keyed(tuples.data(), slots.data(), n, bitmap.data());
+            }
+            if (rc == -2) {
+                tuples.resize(n * 160);
+                for (size_t i = 0; i < n; ++i) memcpy(&tuples[i * 160], batch[i]->tuple, 160);
+                rc = be_->verify_k256(tuples.data(), n, bitmap.data());
+            }
         } else if (all_keyed) {          // the commit-vote burst: every signer is a registered consenter
             tuples.resize(n * 96);
             std::vector<uint32_t> slots(n);
@@ -612,9 +710,10 @@ void* Verifier::staging(Staging& s, size_t bytes) {
 }
 
 void Verifier::RegisterConsenter(uint64_t id, const uint8_t* q) {
-    // -1: no key registry (secp256k1: no combs yet; a backend without one).  Ed25519 keys take the scheme's own registry.
-    const long slot = k256() ? -1 : ed() ? co_.backend().register_key_ed25519(q) : co_.backend().register_key(q);
-    if (slot >= 0 && ed()) co_.backend().widen_key_ed25519(slot);     // 16 comb additions per [k](-A) instead of 32
+    // -1: a backend without a key registry.  Ed25519 and secp256k1 keys take their scheme's own registry.
+    const long slot = k256() ? co_.backend().register_key_k256(q) : ed() ? co_.backend().register_key_ed25519(q) : co_.backend().register_key(q);
+    if (slot >= 0 && k256()) co_.backend().widen_key_k256(slot);      // 16 comb additions per u2 * Q instead of 32
+    else if (slot >= 0 && ed()) co_.backend().widen_key_ed25519(slot);     // 16 comb additions per [k](-A) instead of 32
     else if (slot >= 0) co_.backend().widen_key(slot);      // consenters sign every vote of the epoch: 16 comb additions per u2 * Q instead of 32
     bytes key((const char*)q, key_bytes());
     key.resize(64, '\0');
@@ -632,7 +731,7 @@ void Verifier::RegisterConsenter(uint64_t id, const uint8_t* q) {
 void Verifier::RegisterClient(const std::string& client_id, const uint8_t* q) {
     bool on_device;
     { std::lock_guard<SpinLock> lk(mu_); on_device = opt_.device_client_keys; }
-    const long slot = k256() || !on_device ? -1 : ed() ? co_.backend().register_key_ed25519(q) : co_.backend().register_key(q);     // -1: no key registry
+    const long slot = !on_device ? -1 : k256() ? co_.backend().register_key_k256(q) : ed() ? co_.backend().register_key_ed25519(q) : co_.backend().register_key(q);     // -1: no key registry
     bytes key((const char*)q, key_bytes());
     key.resize(64, '\0');
     std::lock_guard<SpinLock> lk(mu_);
@@ -716,7 +815,7 @@ Status Verifier::verify_one(const uint8_t q[64], const bytes& msg, const bytes& 
     if (ed()) make_tuple_ed25519(q, msg, sig, t);
     else make_tuple(q, msg, sig, t);
     std::string err;
-    const int r = co_.submit(t, k256() ? -1 : slot, ed(), k256(), &err);
+    const int r = co_.submit(t, slot, ed(), k256(), &err);
     if (r < 0) return Status::Unavailable("backend error: " + err);
     if (opt_.cache_verified) {
         std::lock_guard<SpinLock> lk(cache_mu_);
@@ -903,8 +1002,8 @@ Status Verifier::VerifyProposal(const Proposal& p, std::vector<RequestInfo>* req
     if (trace) t_pass = now();
     if (n) {
         int rc = -2;
-        if (!ed() && !k256() && !unkeyed.load()) {
-            // every client has a comb slot: raw signed bytes + DER signatures + slots to the device front end (SHA-256 and
+        if (!ed() && !unkeyed.load()) {
+            // every client has a comb slot (of the scheme's own registry): raw signed bytes + DER signatures + slots to the device front end (SHA-256 and
             // DER parsing run on the GPU); the host only packs the bytes into page-locked staging memory
             std::lock_guard<std::mutex> staging_lock(staging_mu_);
             uint64_t* moff = (uint64_t*)staging(st_moff_, (n + 1) * sizeof(uint64_t));
@@ -924,7 +1023,8 @@ Status Verifier::VerifyProposal(const Proposal& p, std::vector<RequestInfo>* req
                     dslots[i] = slots[i];
                 }
             });
-            rc = co_.submit_many_msgs_keyed(mbuf, moff, sbuf, soff, dslots, n, bitmap.data());
+            rc = k256() ? co_.submit_many_k256_msgs_keyed(mbuf, moff, sbuf, soff, dslots, n, bitmap.data())
+                        : co_.submit_many_msgs_keyed(mbuf, moff, sbuf, soff, dslots, n, bitmap.data());
         }
         if (ed() && !unkeyed.load()) {
             // Ed25519, every client registered: 64-byte signatures + signed bytes + slots; SHA-512(R | A | M) runs on the device with A
@@ -966,7 +1066,13 @@ Status Verifier::VerifyProposal(const Proposal& p, std::vector<RequestInfo>* req
             if (ed()) {
                 rc = co_.submit_many_ed25519(tuples.data(), n, bitmap.data());
             } else if (k256()) {
-                rc = co_.submit_many_k256(tuples.data(), n, bitmap.data());
+                rc = -2;
+                if (!unkeyed.load()) {                  // a backend with the registry but without the front end
+                    std::vector<uint8_t> rsh(n * 96);
+                    for (size_t i = 0; i < n; ++i) memcpy(&rsh[i * 96], &tuples[i * 160], 96);
+                    rc = co_.submit_many_k256_keyed(rsh.data(), slots.data(), n, bitmap.data());
+                }
+                if (rc == -2) rc = co_.submit_many_k256(tuples.data(), n, bitmap.data());
             } else if (!unkeyed.load()) {
                 std::vector<uint8_t> rsh(n * 96);       // r|s|hash; the key comes from the client's slot
                 for (size_t i = 0; i < n; ++i) memcpy(&rsh[i * 96], &tuples[i * 160], 96);
@@ -1167,7 +1273,16 @@ Status Verifier::VerifyConsenterSigBatch(const std::vector<Signature>& sigs, con
             for (size_t i = lo; i < hi; ++i)
                 if (pre[i]) make_tuple((const uint8_t*)keys.find(sigs[i].id)->second.data(), sigs[i].msg, sigs[i].value, &tuples[i * 160]);
         });
-        rc = co_.submit_many_k256(tuples.data(), n, bitmap.data());
+        if (!unkeyed.load()) {
+            // every signer has a slot of the curve's registry: records r | s | hash + slots; a pre-rejected signature travels as an
+            // all-zero record with slot 0xFFFFFFFF (no such key)
+            std::vector<uint8_t> rsh(n * 96);
+            parallel_chunks(n, [&](size_t lo, size_t hi) {
+                for (size_t i = lo; i < hi; ++i) { memcpy(&rsh[i * 96], &tuples[i * 160], 96); if (!pre[i]) slots[i] = 0xFFFFFFFFu; }
+            });
+            rc = co_.submit_many_k256_keyed(rsh.data(), slots.data(), n, bitmap.data());
+        }
+        if (rc == -2) rc = co_.submit_many_k256(tuples.data(), n, bitmap.data());
         if (rc == -2) return Status::Unavailable("backend has no secp256k1 entry");
     } else if (n && !unkeyed.load()) {
         // device front end: the host only lays the bytes out; SHA-256 and DER parsing run on the GPU.

@@ -51,6 +51,7 @@ class Backend {
     virtual void widen_key(long slot) { (void)slot; }
     virtual uint64_t keyed_batches() { return 0; }      // test hook: how many verify_keyed batches ran
     virtual uint64_t widened_keys() { return 0; }       // test hook: how many distinct slots widen_key was given
+    virtual std::vector<uint32_t> last_k256_slots() { return {}; }      // test hook: the slots of the last verify_k256_keyed batch
     // Page-locked staging memory (include/sbv.h: sbv_host_alloc); nullptr = none available, the caller uses the heap
     virtual void* host_alloc(size_t bytes) { (void)bytes; return nullptr; }
     virtual void host_free(void* p) { (void)p; }
@@ -71,6 +72,20 @@ class Backend {
     }
     // secp256k1 variant (include/sbv.h: sbv_secp256k1_verify_batch): n tuples of 160 bytes, same layout as verify().  -2 when unsupported.
     virtual int verify_k256(const uint8_t* tuples, size_t n, uint8_t* bitmap) { (void)tuples; (void)n; (void)bitmap; return -2; }
+    // Registered secp256k1 keys (include/sbv.h: sbv_secp256k1_register_keys): a slot >= 0 for the 64 key bytes, or -1 when the backend
+    // has no registry for this curve (callers then keep the key in the 160-byte tuple).  The registry is the curve's own: its slots
+    // mean nothing to verify_keyed.  widen_key_k256: a 16-bit comb for a consenter's slot.
+    virtual long register_key_k256(const uint8_t q[64]) { (void)q; return -1; }
+    virtual void widen_key_k256(long slot) { (void)slot; }
+    // n records of 96 bytes r|s|hash + slots (sbv_secp256k1_verify_batch_keyed); -2 when unsupported
+    virtual int verify_k256_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* bitmap) {
+        (void)rsh; (void)slots; (void)n; (void)bitmap; return -2;
+    }
+    // raw messages + DER signatures + slots, SHA-256 and the DER parse by the backend (sbv_secp256k1_verify_msgs_keyed); -2 when unsupported
+    virtual int verify_k256_msgs_keyed(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff,
+                                       const uint32_t* slots, size_t n, uint8_t* bitmap) {
+        (void)msgs; (void)moff; (void)sigs; (void)soff; (void)slots; (void)n; (void)bitmap; return -2;
+    }
     virtual int verify_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* bitmap) {
         (void)rsh; (void)slots; (void)n; (void)bitmap; return -2;
     }
@@ -131,6 +146,10 @@ class Coalescer {
     int submit_many_ed25519(const uint8_t* tuples128, size_t n, uint8_t* bitmap);
     int submit_many_ed25519_msgs_keyed(const uint8_t* sigs, const uint8_t* msgs, const uint64_t* moff, const uint32_t* slots, size_t n, uint8_t* bitmap);
     int submit_many_k256(const uint8_t* tuples, size_t n, uint8_t* bitmap);
+    // the registered-key forms of the secp256k1 Verifier (-2 when the backend has none: the caller takes submit_many_k256)
+    int submit_many_k256_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* bitmap);
+    int submit_many_k256_msgs_keyed(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint32_t* slots, size_t n,
+                                    uint8_t* bitmap);
     int submit_many(const uint8_t* tuples, size_t n, uint8_t* bitmap);
     int submit_many_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* bitmap);
     // raw messages + DER signatures + slots through the backend's front end (-2 when it has none)
@@ -164,7 +183,8 @@ class Coalescer {
 // crypto/ecdsa.VerifyASN1).  ED25519: the BASELINE.json configs[4] variant — 64-byte R|S signatures, 32-byte keys
 // (Go crypto/ed25519.Verify); registered-key slots do not apply (the device groups by key inside each batch).
 // SECP256K1: ECDSA over SHA-256 with DER signatures and 64-byte keys exactly like P256, on the other curve
-// (include/sbv.h: sbv_secp256k1_verify_batch); no registered-key slots yet (every tuple carries its key).
+// (include/sbv.h: sbv_secp256k1_verify_batch); consenters and registered clients take slots of the curve's own registry
+// (sbv_secp256k1_register_keys), and batches whose signers all have one go through the keyed entries.
 enum class Scheme { P256 = 0, ED25519 = 1, SECP256K1 = 2 };
 
 struct VerifierOptions {

@@ -27,8 +27,8 @@ const (
 //
 //	Pub   the P-256 key (SchemeP256)
 //	Key   the raw key bytes of the other schemes: 32-byte Ed25519 key, or 64 bytes Qx|Qy big-endian for secp256k1
-//	Slot  >= 0 when the key is registered with the device (sbv_p256_register_keys, or sbv_ed25519_register_keys under
-//	      SchemeEd25519); -1 otherwise
+//	Slot  >= 0 when the key is registered with the device (sbv_p256_register_keys, sbv_ed25519_register_keys under
+//	      SchemeEd25519, sbv_secp256k1_register_keys under SchemeSecp256k1: one registry per scheme); -1 otherwise
 type Item struct {
 	Pub  *ecdsa.PublicKey
 	Key  []byte
@@ -69,6 +69,15 @@ type Backend interface {
 type EdKeyRegistry interface {
 	RegisterKeyEd25519(key []byte) int32
 	WidenKeyEd25519(slot int32)
+}
+
+// K256KeyRegistry is the optional secp256k1 key registry of a backend (sbv_secp256k1_register_keys): RegisterKeySecp256k1 gives
+// the device a 64-byte key Qx|Qy it will see again and returns its slot (-1 when there is no registry: the key then travels
+// inline); WidenKeySecp256k1 gives a consenter's slot a 16-bit comb (sbv_secp256k1_widen_keys: u2*Q in 16 additions instead of
+// 32).  Slots are keyed by the 64 key bytes and belong to this curve's registry alone.  An optional interface, like EdKeyRegistry.
+type K256KeyRegistry interface {
+	RegisterKeySecp256k1(key []byte) int32
+	WidenKeySecp256k1(slot int32)
 }
 
 // ErrNoBatchSigner: the backend has no batch signing entry (the pure-Go backend).

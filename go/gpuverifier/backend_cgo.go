@@ -37,12 +37,14 @@ const (
 //	every item has a slot                      sbv_p256_verify_batch_keyed  96-byte r|s|hash records + slots
 //	otherwise                                  sbv_p256_verify_batch_sharded generic tuples, all GPUs of the node
 //	SchemeEd25519, every item has a slot       sbv_ed25519_verify_msgs_keyed  signatures + raw messages + slots (SHA-512 on the device)
+//	SchemeSecp256k1, every item has a slot     sbv_secp256k1_verify_msgs_keyed (n >= frontEndFrom) / sbv_secp256k1_verify_batch_keyed
 //	SchemeEd25519 / SchemeSecp256k1            sbv_ed25519_verify_msgs / sbv_secp256k1_verify_batch
 type gpuBackend struct {
-	jobs   chan *gpuJob
-	mu     sync.Mutex
-	regs   map[[64]byte]int32
-	edRegs map[[32]byte]int32 // the Ed25519 registry's slots (sbv_ed25519_register_keys), by encoding
+	jobs     chan *gpuJob
+	mu       sync.Mutex
+	regs     map[[64]byte]int32
+	edRegs   map[[32]byte]int32 // the Ed25519 registry's slots (sbv_ed25519_register_keys), by encoding
+	k256Regs map[[64]byte]int32 // the secp256k1 registry's slots (sbv_secp256k1_register_keys), by key bytes: not the slots of regs
 }
 
 type gpuJob struct {
@@ -52,7 +54,7 @@ type gpuJob struct {
 
 // NewDeviceBackend initialises every visible MI355X (sbv_init_all).
 func NewDeviceBackend() (Backend, error) {
-	b := &gpuBackend{jobs: make(chan *gpuJob, 64), regs: map[[64]byte]int32{}, edRegs: map[[32]byte]int32{}}
+	b := &gpuBackend{jobs: make(chan *gpuJob, 64), regs: map[[64]byte]int32{}, edRegs: map[[32]byte]int32{}, k256Regs: map[[64]byte]int32{}}
 	ready := make(chan error, 1)
 	go b.loop(ready)
 	if err := <-ready; err != nil {
@@ -286,8 +288,50 @@ func (b *gpuBackend) verifyEd25519(items []Item) ([]bool, error) {
 	return ok, nil
 }
 
-// verifySecp256k1: generic tuples with the 64-byte key inline (no registered keys for this curve yet).
+// verifySecp256k1Keyed: every item's key has a slot of this curve's registry.  From frontEndFrom signatures on the device front
+// end takes raw messages + DER signatures + slots (sbv_secp256k1_verify_msgs_keyed, chunks of at most 2^21); below, 96-byte
+// r|s|hash records built here (sbv_secp256k1_verify_batch_keyed).
+func (b *gpuBackend) verifySecp256k1Keyed(items []Item) ([]bool, error) {
+	n := len(items)
+	accept := make([]byte, (n+7)/8)
+	slots := make([]uint32, n)
+	for i := range items {
+		slots[i] = uint32(items[i].Slot)
+	}
+	if n >= frontEndFrom {
+		for lo := 0; lo < n; lo += frontEndMax {
+			hi := lo + frontEndMax
+			if hi > n {
+				hi = n
+			}
+			m := hi - lo
+			msgs, moff := packMsgs(func(i int) []byte { return items[lo+i].Msg }, m)
+			sigs, soff := packMsgs(func(i int) []byte { return items[lo+i].Sig }, m)
+			rc := C.sbv_secp256k1_verify_msgs_keyed(u8(msgs), (*C.uint64_t)(unsafe.Pointer(&moff[0])), u8(sigs),
+				(*C.uint64_t)(unsafe.Pointer(&soff[0])), (*C.uint32_t)(unsafe.Pointer(&slots[lo])), C.size_t(m),
+				u8(accept[lo/8:])) // lo is a multiple of 2^21: whole bitmap bytes
+			if rc != 0 {
+				return nil, lastError()
+			}
+		}
+		return bitmapToBools(accept, n), nil
+	}
+	rsh := make([]byte, n*rshBytes)
+	for i := range items {
+		fillRSH(rsh[i*rshBytes:(i+1)*rshBytes], &items[i])
+	}
+	if rc := C.sbv_secp256k1_verify_batch_keyed(u8(rsh), (*C.uint32_t)(unsafe.Pointer(&slots[0])), C.size_t(n), u8(accept)); rc != 0 {
+		return nil, lastError()
+	}
+	return bitmapToBools(accept, n), nil
+}
+
+// verifySecp256k1: when every item's key has a registry slot the keyed entries take the batch (verifySecp256k1Keyed); any other
+// batch travels as generic tuples with the 64-byte key inline.
 func (b *gpuBackend) verifySecp256k1(items []Item) ([]bool, error) {
+	if allSlotted(items) {
+		return b.verifySecp256k1Keyed(items)
+	}
 	n := len(items)
 	buf := make([]byte, n*tupleBytes)
 	for i := range items {
@@ -400,6 +444,48 @@ func (b *gpuBackend) WidenKeyEd25519(slot int32) {
 		var s C.uint32_t
 		s = C.uint32_t(slot)
 		C.sbv_ed25519_widen_keys(&s, C.size_t(1))
+	})
+}
+
+// RegisterKeySecp256k1 builds the key's 8-bit comb on the device once (sbv_secp256k1_register_keys: 270 KiB of HBM per key) and
+// remembers the slot; registering the same bytes again returns the same slot.  -1 when the device refuses (the key then
+// travels inline).
+func (b *gpuBackend) RegisterKeySecp256k1(key []byte) int32 {
+	if len(key) != 64 {
+		return -1
+	}
+	var k [64]byte
+	copy(k[:], key)
+	b.mu.Lock()
+	if s, hit := b.k256Regs[k]; hit {
+		b.mu.Unlock()
+		return s
+	}
+	b.mu.Unlock()
+	slot := int32(-1)
+	b.on(func() {
+		var out C.uint32_t
+		if rc := C.sbv_secp256k1_register_keys(u8(k[:]), 1, &out); rc == 0 {
+			slot = int32(out)
+		}
+	})
+	if slot >= 0 {
+		b.mu.Lock()
+		b.k256Regs[k] = slot
+		b.mu.Unlock()
+	}
+	return slot
+}
+
+// WidenKeySecp256k1: sbv_secp256k1_widen_keys for one slot (best effort: a slot without a 16-bit comb keeps its 8-bit one).
+func (b *gpuBackend) WidenKeySecp256k1(slot int32) {
+	if slot < 0 {
+		return
+	}
+	b.on(func() {
+		var s C.uint32_t
+		s = C.uint32_t(slot)
+		C.sbv_secp256k1_widen_keys(&s, C.size_t(1))
 	})
 }
 

@@ -20,7 +20,8 @@
 //     item slotted -> raw messages + DER + slots (sbv_p256_verify_msgs_keyed: SHA-256 and DER on the device) or, for
 //     small batches, r|s|hash records + slots (sbv_p256_verify_batch_keyed); otherwise generic tuples over all GPUs of
 //     the node (sbv_p256_verify_batch_sharded); Options.Scheme selects Ed25519 (sbv_ed25519_verify_msgs) or secp256k1
-//     (sbv_secp256k1_verify_batch);
+//     (sbv_secp256k1_verify_batch), each with a key registry of its own (EdKeyRegistry, K256KeyRegistry) whose slotted
+//     batches take the scheme's keyed entries;
 //   - a coalescer for backends that take bursts: the <= N-1 goroutines of View.processCommits
 //     (internal/bft/view.go:537-541) each call VerifyConsenterSig with one signature; they are merged into one backend
 //     batch by the first of them (the leader of the burst: no dispatcher goroutine to wake), which polls (spin, then

@@ -143,8 +143,20 @@ func (v *Verifier) RegisterClient(clientID string, pub *ecdsa.PublicKey) {
 // RegisterConsenterRaw / RegisterClientRaw: the registry for SchemeEd25519 (32-byte keys) and SchemeSecp256k1 (64 bytes
 // Qx|Qy big-endian).  Under SchemeEd25519 a backend with an Ed25519 registry (EdKeyRegistry: sbv_ed25519_register_keys) gives
 // the key a device slot — consenters' slots also a 16-bit comb — and batches whose signers all have slots take the keyed
-// entry; secp256k1 keys have no device slots (the device groups by key inside each batch).
+// entry.  Under SchemeSecp256k1 a backend with this curve's registry (K256KeyRegistry: sbv_secp256k1_register_keys) does the same
+// for the 64-byte keys.
 func (v *Verifier) edSlot(key []byte, consenter bool) int32 {
+	if v.opt.Scheme == SchemeSecp256k1 {
+		kreg, has := v.backend.(K256KeyRegistry)
+		if !has || len(key) != 64 {
+			return -1
+		}
+		slot := kreg.RegisterKeySecp256k1(key)
+		if slot >= 0 && consenter {
+			kreg.WidenKeySecp256k1(slot)
+		}
+		return slot
+	}
 	reg, has := v.backend.(EdKeyRegistry)
 	if v.opt.Scheme != SchemeEd25519 || !has || len(key) != 32 {
 		return -1

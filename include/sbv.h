@@ -237,6 +237,48 @@ int sbv_ed25519_verify_batch_keyed_dev(const void* d_rsk, const void* d_slots, s
 int sbv_ed25519_verify_msgs_keyed(const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
                                   const uint32_t* slots, size_t n, uint8_t* accept_bitmap);
 
+/* Registered secp256k1 keys: the consenters' (and registered clients') keys get a slot once, after which a verification against
+ * that key needs no doublings, no per-signature table and no grouping work: u1 * G from the comb of G (13 additions at the default
+ * 20 bits) plus u2 * Q in 32.2 additions from the slot's 8-bit comb of Q (33 x 128 x 64 B = 270 KiB of HBM per key), or in 16 from a
+ * 16-bit comb after sbv_secp256k1_widen_keys (17 windows x 32 768 entries x 64 B = 35.7 MB per key).  Two launches per call: stage A on
+ * the records, then one lane per signature (consensus_amd/csrc/k256_keyed.h).
+ *   keys: m x 64 bytes Qx | Qy big-endian.  slots_out[i] = slot of keys[i].  Slots are keyed by the 64 key BYTES: equal keys share a
+ *     slot, slots are numbered by first registration.  A key that pointFromAffine refuses (a coordinate >= p, a point off
+ *     y^2 = x^3 + 7, (0, 0)) still gets a slot, flagged invalid: every signature against it is rejected.  At most 65 536 keys
+ *     (SBV_EINVAL beyond).  Nothing is allocated before the first registration; capacity doubles from 64 slots, live slots are copied
+ *     on the device.  The combs are built on the device and are byte for byte the tables the grouped step builds for the same key.
+ *   The registry is its own: it never shares a table, a slot index or a hash with the P-256 registry or with either key-table cache
+ *     (a byte string can be a point of both curves).  A slot number of one registry means nothing in the other.
+ *   sbv_secp256k1_wide_keys: cap on the slots with a 16-bit comb (0 = none; default 64 = 2.3 GB; at most 4096); lowering it returns
+ *     the slots beyond the cap to their 8-bit combs.  sbv_secp256k1_widen_keys: 16-bit combs for the named slots, built on the device
+ *     from their 8-bit combs; a slot that is wide already, is invalid or lies beyond the cap stays as it is (no error); an
+ *     unregistered slot is SBV_EINVAL.  stats: out[0] = wide slots, out[1] = 16 (bits), out[2] = the cap, out[3] = KiB per wide
+ *     comb.  sbv_secp256k1_wide_selfcheck(slot) = 1 when the device comb equals the host builder's byte for byte, 0 when it differs,
+ *     SBV_EINVAL when the slot has no wide comb.
+ *   rsh: n x 96 bytes r | s | hash, big-endian: the 160-byte tuple without its key.  slots: n slots.  A wavefront whose live
+ *     signatures all belong to wide slots walks the 16-bit combs, any other the 8-bit combs every slot keeps; verdicts are
+ *     bit-identical to sbv_secp256k1_verify_batch on the equivalent 160-byte tuples.  An out-of-range slot, r or s outside
+ *     [1, n - 1] and R = infinity are rejects, not errors: return codes never mean "invalid signature".  Batches larger than 2^21
+ *     are chunked.  _dev: d_rsh 16-byte aligned, on `hip_stream`, the caller synchronises.
+ *   sbv_secp256k1_verify_msgs_keyed: the device front end of sbv_p256_verify_msgs_keyed (SHA-256 + strict DER parse, which knows
+ *     nothing of the curve) in front of the keyed step: message i = msgs[msg_offsets[i] .. msg_offsets[i+1]), DER signature i =
+ *     sigs[sig_offsets[i] .. sig_offsets[i+1]), signer slots[i]; n <= 2^21; an offset table that does not start at 0 or decreases
+ *     is SBV_EINVAL; a signature that does not parse is a reject.
+ * A failed registration or widening (SBV_ENOMEM, SBV_EDEVICE) leaves the registry as it was.  These entries run on the default
+ * context (registry replication to other devices is not provided); sbv_shutdown forgets the registry.  Without a device every
+ * entry returns what its siblings return (SBV_ENODEV from sbv_init, SBV_ENOTINIT after it). */
+int sbv_secp256k1_register_keys(const uint8_t* keys, size_t m, uint32_t* slots_out);
+int sbv_secp256k1_key_count(void);
+int sbv_secp256k1_clear_keys(void);
+int sbv_secp256k1_wide_keys(uint32_t max_keys);
+int sbv_secp256k1_widen_keys(const uint32_t* slots, size_t m);
+int sbv_secp256k1_wide_key_stats(uint32_t out[4]);
+int sbv_secp256k1_wide_selfcheck(uint32_t slot);
+int sbv_secp256k1_verify_batch_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* accept_bitmap);
+int sbv_secp256k1_verify_batch_keyed_dev(const void* d_rsh, const void* d_slots, size_t n, void* d_bitmap, void* hip_stream);
+int sbv_secp256k1_verify_msgs_keyed(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs,
+                                    const uint64_t* sig_offsets, const uint32_t* slots, size_t n, uint8_t* accept_bitmap);
+
 /* Strict DER parse of an ECDSA-Sig-Value with Go x/crypto/cryptobyte rules
  * (crypto/ecdsa.parseSignature): out = r | s, 32 bytes each, big-endian, zero padded.
  * Returns SBV_OK or SBV_EPARSE (then out is all zero, which every verify rejects). */
