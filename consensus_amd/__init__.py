@@ -142,15 +142,66 @@ def verify_batch_dev(d_tuples_ptr: int, n: int, d_bitmap_ptr: int, stream: int =
     _check(load().sbv_p256_verify_batch_dev(d_tuples_ptr, n, d_bitmap_ptr, stream))
 
 
-def register_keys(keys) -> list:
-    """keys: iterable of 64-byte Qx|Qy -> list of slots (equal keys share a slot)."""
+# ---- the registered-key wrappers of the three schemes: one ctypes body each, named by the C function ----
+_U32 = ctypes.c_uint32
+_PTR = ctypes.c_void_p
+
+
+def _call(name: str, argtypes, *args) -> int:
+    fn = getattr(load(), name)
+    fn.argtypes = argtypes
+    return fn(*args)
+
+
+def _count_or_raise(rc: int) -> int:
+    if rc < 0:
+        _check(rc)
+    return rc
+
+
+def _register_keys(name: str, key_bytes: int, keys) -> list:
     keys = list(keys)
     blob = b"".join(keys)
-    if len(blob) != 64 * len(keys):
-        raise ValueError("every key must be 64 bytes")
-    out = (ctypes.c_uint32 * max(1, len(keys)))()
-    _check(load().sbv_p256_register_keys(blob, len(keys), out))
+    if len(blob) != key_bytes * len(keys):
+        raise ValueError(f"every key must be {key_bytes} bytes")
+    out = (_U32 * max(1, len(keys)))()
+    _check(_call(name, [ctypes.c_char_p, ctypes.c_size_t, _PTR], blob, len(keys), out))
     return list(out[:len(keys)])
+
+
+def _widen_keys(name: str, slots) -> None:
+    slots = list(slots)
+    arr = (_U32 * max(1, len(slots)))(*slots)
+    _check(_call(name, [_PTR, ctypes.c_size_t], arr, len(slots)))
+
+
+def _wide_key_stats(name: str):
+    out = (_U32 * 4)()
+    _check(_call(name, [_PTR], out))
+    return out[0], out[1], out[2], out[3]
+
+
+def _wide_selfcheck(name: str, slot: int) -> bool:
+    return _count_or_raise(_call(name, [_U32], slot)) == 1
+
+
+def _verify_batch_keyed(name: str, recs: bytes, slots, n: Optional[int]) -> bytes:
+    if n is None:
+        n = len(recs) // 96
+    arr = (_U32 * max(1, n))(*slots)
+    out = ctypes.create_string_buffer(max(1, (n + 7) // 8))
+    buf = (ctypes.c_char * len(recs)).from_buffer_copy(recs) if n else None
+    _check(_call(name, [_PTR, _PTR, ctypes.c_size_t, _PTR], buf, arr, n, out))
+    return out.raw[:(n + 7) // 8]
+
+
+def _verify_batch_keyed_dev(name: str, d_recs_ptr: int, d_slots_ptr: int, n: int, d_bitmap_ptr: int, stream: int) -> None:
+    _check(_call(name, [_PTR, _PTR, ctypes.c_size_t, _PTR, _PTR], d_recs_ptr, d_slots_ptr, n, d_bitmap_ptr, stream))
+
+
+def register_keys(keys) -> list:
+    """keys: iterable of 64-byte Qx|Qy -> list of slots (equal keys share a slot)."""
+    return _register_keys("sbv_p256_register_keys", 64, keys)
 
 
 def key_count() -> int:
@@ -166,52 +217,31 @@ WIDE_BITS_AUTO = 1
 
 def wide_keys(bits: int = WIDE_BITS_AUTO, max_keys: int = 64) -> None:
     """sbv_p256_wide_keys: width and cap of the wide combs sbv_p256_widen_keys builds (bits = 0: off); see include/sbv.h."""
-    lib = load()
-    lib.sbv_p256_wide_keys.argtypes = [ctypes.c_int, ctypes.c_uint32]
-    _check(lib.sbv_p256_wide_keys(bits, max_keys))
+    _check(_call("sbv_p256_wide_keys", [ctypes.c_int, _U32], bits, max_keys))
 
 
 def widen_keys(slots) -> None:
     """sbv_p256_widen_keys: a wide comb for each of these registered slots (the consenters')."""
-    slots = list(slots)
-    arr = (ctypes.c_uint32 * max(1, len(slots)))(*slots)
-    lib = load()
-    lib.sbv_p256_widen_keys.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-    _check(lib.sbv_p256_widen_keys(arr, len(slots)))
+    _widen_keys("sbv_p256_widen_keys", slots)
 
 
 def wide_selfcheck(slot: int) -> bool:
     """sbv_p256_wide_selfcheck: the device-built wide comb of `slot` equals the host builder's output byte for byte."""
-    lib = load()
-    lib.sbv_p256_wide_selfcheck.argtypes = [ctypes.c_uint32]
-    rc = lib.sbv_p256_wide_selfcheck(slot)
-    if rc < 0:
-        _check(rc)
-    return rc == 1
+    return _wide_selfcheck("sbv_p256_wide_selfcheck", slot)
 
 
 def wide_key_stats():
     """(slots holding a wide comb, bits, max_keys, KiB per key)"""
-    out = (ctypes.c_uint32 * 4)()
-    lib = load()
-    lib.sbv_p256_wide_key_stats.argtypes = [ctypes.c_void_p]
-    _check(lib.sbv_p256_wide_key_stats(out))
-    return out[0], out[1], out[2], out[3]
+    return _wide_key_stats("sbv_p256_wide_key_stats")
 
 
 def verify_batch_keyed(rsh: bytes, slots, n: Optional[int] = None) -> bytes:
     """Registered-key form: rsh = n x 96 bytes (r|s|hash), slots = n key slots."""
-    if n is None:
-        n = len(rsh) // 96
-    arr = (ctypes.c_uint32 * max(1, n))(*slots)
-    out = ctypes.create_string_buffer(max(1, (n + 7) // 8))
-    buf = (ctypes.c_char * len(rsh)).from_buffer_copy(rsh) if n else None
-    _check(load().sbv_p256_verify_batch_keyed(buf, arr, n, out))
-    return out.raw[:(n + 7) // 8]
+    return _verify_batch_keyed("sbv_p256_verify_batch_keyed", rsh, slots, n)
 
 
 def verify_batch_keyed_dev(d_rsh_ptr: int, d_slots_ptr: int, n: int, d_bitmap_ptr: int, stream: int = 0) -> None:
-    _check(load().sbv_p256_verify_batch_keyed_dev(d_rsh_ptr, d_slots_ptr, n, d_bitmap_ptr, stream))
+    _verify_batch_keyed_dev("sbv_p256_verify_batch_keyed_dev", d_rsh_ptr, d_slots_ptr, n, d_bitmap_ptr, stream)
 
 
 def ed25519_make_tuples(sigs, pks, msgs) -> bytes:
@@ -257,22 +287,11 @@ def ed25519_verify_batch_dev(d_tuples_ptr: int, n: int, d_bitmap_ptr: int, strea
 
 def ed25519_register_keys(pks) -> list:
     """pks: iterable of 32-byte encoded Ed25519 keys -> list of slots (equal encodings share a slot; see include/sbv.h)."""
-    pks = list(pks)
-    blob = b"".join(pks)
-    if len(blob) != 32 * len(pks):
-        raise ValueError("every key must be 32 bytes")
-    out = (ctypes.c_uint32 * max(1, len(pks)))()
-    lib = load()
-    lib.sbv_ed25519_register_keys.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
-    _check(lib.sbv_ed25519_register_keys(blob, len(pks), out))
-    return list(out[:len(pks)])
+    return _register_keys("sbv_ed25519_register_keys", 32, pks)
 
 
 def ed25519_key_count() -> int:
-    rc = load().sbv_ed25519_key_count()
-    if rc < 0:
-        _check(rc)
-    return rc
+    return _count_or_raise(load().sbv_ed25519_key_count())
 
 
 def ed25519_clear_keys() -> None:
@@ -281,56 +300,31 @@ def ed25519_clear_keys() -> None:
 
 def ed25519_wide_keys(max_keys: int = 64) -> None:
     """sbv_ed25519_wide_keys: cap on the registered Ed25519 slots with a 16-bit comb (0 = none)."""
-    lib = load()
-    lib.sbv_ed25519_wide_keys.argtypes = [ctypes.c_uint32]
-    _check(lib.sbv_ed25519_wide_keys(max_keys))
+    _check(_call("sbv_ed25519_wide_keys", [_U32], max_keys))
 
 
 def ed25519_widen_keys(slots) -> None:
     """sbv_ed25519_widen_keys: a 16-bit comb of -A for each of these registered slots (the consenters')."""
-    slots = list(slots)
-    arr = (ctypes.c_uint32 * max(1, len(slots)))(*slots)
-    lib = load()
-    lib.sbv_ed25519_widen_keys.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-    _check(lib.sbv_ed25519_widen_keys(arr, len(slots)))
+    _widen_keys("sbv_ed25519_widen_keys", slots)
 
 
 def ed25519_wide_key_stats():
     """(slots holding a 16-bit comb, 16, cap, KiB per comb)"""
-    out = (ctypes.c_uint32 * 4)()
-    lib = load()
-    lib.sbv_ed25519_wide_key_stats.argtypes = [ctypes.c_void_p]
-    _check(lib.sbv_ed25519_wide_key_stats(out))
-    return out[0], out[1], out[2], out[3]
+    return _wide_key_stats("sbv_ed25519_wide_key_stats")
 
 
 def ed25519_wide_selfcheck(slot: int) -> bool:
     """sbv_ed25519_wide_selfcheck: the device-built 16-bit comb of `slot` equals the host builder's output byte for byte."""
-    lib = load()
-    lib.sbv_ed25519_wide_selfcheck.argtypes = [ctypes.c_uint32]
-    rc = lib.sbv_ed25519_wide_selfcheck(slot)
-    if rc < 0:
-        _check(rc)
-    return rc == 1
+    return _wide_selfcheck("sbv_ed25519_wide_selfcheck", slot)
 
 
 def ed25519_verify_batch_keyed(rsk: bytes, slots, n: Optional[int] = None) -> bytes:
     """Registered-key form: rsk = n x 96 bytes (R | S | k), slots = n key slots -> accept bitmap."""
-    if n is None:
-        n = len(rsk) // 96
-    arr = (ctypes.c_uint32 * max(1, n))(*slots)
-    out = ctypes.create_string_buffer(max(1, (n + 7) // 8))
-    buf = (ctypes.c_char * len(rsk)).from_buffer_copy(rsk) if n else None
-    lib = load()
-    lib.sbv_ed25519_verify_batch_keyed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    _check(lib.sbv_ed25519_verify_batch_keyed(buf, arr, n, out))
-    return out.raw[:(n + 7) // 8]
+    return _verify_batch_keyed("sbv_ed25519_verify_batch_keyed", rsk, slots, n)
 
 
 def ed25519_verify_batch_keyed_dev(d_rsk_ptr: int, d_slots_ptr: int, n: int, d_bitmap_ptr: int, stream: int = 0) -> None:
-    lib = load()
-    lib.sbv_ed25519_verify_batch_keyed_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
-    _check(lib.sbv_ed25519_verify_batch_keyed_dev(d_rsk_ptr, d_slots_ptr, n, d_bitmap_ptr, stream))
+    _verify_batch_keyed_dev("sbv_ed25519_verify_batch_keyed_dev", d_rsk_ptr, d_slots_ptr, n, d_bitmap_ptr, stream)
 
 
 def ed25519_verify_msgs_keyed(sigs, msgs, slots) -> bytes:
@@ -367,22 +361,11 @@ def secp256k1_verify_batch_dev(d_tuples_ptr: int, n: int, d_bitmap_ptr: int, str
 
 def secp256k1_register_keys(keys) -> list:
     """keys: iterable of 64-byte Qx | Qy -> list of slots of the secp256k1 registry (equal keys share a slot; see include/sbv.h)."""
-    keys = list(keys)
-    blob = b"".join(keys)
-    if len(blob) != 64 * len(keys):
-        raise ValueError("every key must be 64 bytes")
-    out = (ctypes.c_uint32 * max(1, len(keys)))()
-    lib = load()
-    lib.sbv_secp256k1_register_keys.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
-    _check(lib.sbv_secp256k1_register_keys(blob, len(keys), out))
-    return list(out[:len(keys)])
+    return _register_keys("sbv_secp256k1_register_keys", 64, keys)
 
 
 def secp256k1_key_count() -> int:
-    rc = load().sbv_secp256k1_key_count()
-    if rc < 0:
-        _check(rc)
-    return rc
+    return _count_or_raise(load().sbv_secp256k1_key_count())
 
 
 def secp256k1_clear_keys() -> None:
@@ -391,56 +374,31 @@ def secp256k1_clear_keys() -> None:
 
 def secp256k1_wide_keys(max_keys: int = 64) -> None:
     """sbv_secp256k1_wide_keys: cap on the registered secp256k1 slots with a 16-bit comb (0 = none)."""
-    lib = load()
-    lib.sbv_secp256k1_wide_keys.argtypes = [ctypes.c_uint32]
-    _check(lib.sbv_secp256k1_wide_keys(max_keys))
+    _check(_call("sbv_secp256k1_wide_keys", [_U32], max_keys))
 
 
 def secp256k1_widen_keys(slots) -> None:
     """sbv_secp256k1_widen_keys: a 16-bit comb of Q for each of these registered slots (the consenters')."""
-    slots = list(slots)
-    arr = (ctypes.c_uint32 * max(1, len(slots)))(*slots)
-    lib = load()
-    lib.sbv_secp256k1_widen_keys.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-    _check(lib.sbv_secp256k1_widen_keys(arr, len(slots)))
+    _widen_keys("sbv_secp256k1_widen_keys", slots)
 
 
 def secp256k1_wide_key_stats():
     """(slots holding a 16-bit comb, 16, cap, KiB per comb)"""
-    out = (ctypes.c_uint32 * 4)()
-    lib = load()
-    lib.sbv_secp256k1_wide_key_stats.argtypes = [ctypes.c_void_p]
-    _check(lib.sbv_secp256k1_wide_key_stats(out))
-    return out[0], out[1], out[2], out[3]
+    return _wide_key_stats("sbv_secp256k1_wide_key_stats")
 
 
 def secp256k1_wide_selfcheck(slot: int) -> bool:
     """sbv_secp256k1_wide_selfcheck: the device-built 16-bit comb of `slot` equals the host builder's output byte for byte."""
-    lib = load()
-    lib.sbv_secp256k1_wide_selfcheck.argtypes = [ctypes.c_uint32]
-    rc = lib.sbv_secp256k1_wide_selfcheck(slot)
-    if rc < 0:
-        _check(rc)
-    return rc == 1
+    return _wide_selfcheck("sbv_secp256k1_wide_selfcheck", slot)
 
 
 def secp256k1_verify_batch_keyed(rsh: bytes, slots, n: Optional[int] = None) -> bytes:
     """Registered-key form: rsh = n x 96 bytes (r | s | hash), slots = n key slots -> accept bitmap."""
-    if n is None:
-        n = len(rsh) // 96
-    arr = (ctypes.c_uint32 * max(1, n))(*slots)
-    out = ctypes.create_string_buffer(max(1, (n + 7) // 8))
-    buf = (ctypes.c_char * len(rsh)).from_buffer_copy(rsh) if n else None
-    lib = load()
-    lib.sbv_secp256k1_verify_batch_keyed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    _check(lib.sbv_secp256k1_verify_batch_keyed(buf, arr, n, out))
-    return out.raw[:(n + 7) // 8]
+    return _verify_batch_keyed("sbv_secp256k1_verify_batch_keyed", rsh, slots, n)
 
 
 def secp256k1_verify_batch_keyed_dev(d_rsh_ptr: int, d_slots_ptr: int, n: int, d_bitmap_ptr: int, stream: int = 0) -> None:
-    lib = load()
-    lib.sbv_secp256k1_verify_batch_keyed_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
-    _check(lib.sbv_secp256k1_verify_batch_keyed_dev(d_rsh_ptr, d_slots_ptr, n, d_bitmap_ptr, stream))
+    _verify_batch_keyed_dev("sbv_secp256k1_verify_batch_keyed_dev", d_rsh_ptr, d_slots_ptr, n, d_bitmap_ptr, stream)
 
 
 def secp256k1_verify_msgs_keyed(msgs, sigs_der, slots) -> bytes:

@@ -49,6 +49,23 @@ struct StageSlot {
     bool used = false;
 };
 
+// The device half of a local registry (registered Ed25519 / secp256k1 keys, see "registered Ed25519 and secp256k1 keys" below), allocated
+// on the first registration.  The tables are bytes here; the scheme's traits hold the per-slot sizes and its *_reg_view the kernels' types.
+struct LocalRegDev {
+    uint8_t* ktab = nullptr;            // slot s: its 8-bit comb
+    uint8_t* kvalid = nullptr;          // slot s: 1 = the key is a point
+    uint8_t* kkeys = nullptr;           // slot s: the key / encoding bytes as registered
+    u32* kwidx = nullptr;               // slot s: index of its 16-bit comb in wtab, or 0xFFFFFFFF (SBV_ED_WIDE_NONE, SBV_K256_WIDE_NONE)
+    size_t key_cap = 0, nkeys = 0;
+    uint8_t* wtab = nullptr;            // comb w belongs to slot wide_slots[w]
+    size_t wtab_cap = 0;
+    std::vector<u32> wide_slots;
+};
+void local_reg_free(LocalRegDev& d) {
+    for (void* p : {(void*)d.ktab, (void*)d.kvalid, (void*)d.kkeys, (void*)d.kwidx, (void*)d.wtab}) if (p) (void)hipFree(p);
+    d = LocalRegDev();
+}
+
 struct Context {
     std::mutex mu;                      // held for the whole of every call that touches this device's buffers
     bool ready = false;
@@ -137,26 +154,8 @@ struct Context {
     size_t wide_nofit_at = (size_t)-1;
     bool kwide_auto = true;             // width by the number of widened keys: 20 bits up to kWideAutoSplit keys, 16 beyond (sbv_p256_wide_keys)
     u32 kwide_max = 64;
-    // registered Ed25519 keys (ed25519_keyed.h; sbv_ed25519_register_keys): the default context's half of g_edreg, allocated on the
-    // first registration.  Slot s: 8-bit comb of -A, valid byte, encoding, index of its 16-bit comb in d_ed_wtab (or SBV_ED_WIDE_NONE)
-    sbv::aniels* d_ed_ktab = nullptr;
-    uint8_t* d_ed_kvalid = nullptr;
-    uint8_t* d_ed_kenc = nullptr;
-    u32* d_ed_kwidx = nullptr;
-    size_t ed_key_cap = 0, ed_nkeys = 0;
-    uint8_t* d_ed_wtab = nullptr;          // comb w (SBV_ED_HOT_COMB_BYTES) belongs to slot ed_wide_slots[w]
-    size_t ed_wtab_cap = 0;
-    std::vector<u32> ed_wide_slots;
-    // registered secp256k1 keys (k256_keyed.h; sbv_secp256k1_register_keys): the default context's half of g_k256reg, allocated on the
-    // first registration.  Slot s: the 64 key bytes, valid byte, 8-bit comb of Q, index of its 16-bit comb in d_k256_wtab (or SBV_K256_WIDE_NONE)
-    sbv::kapt* d_k256_ktab = nullptr;
-    uint8_t* d_k256_kvalid = nullptr;
-    uint8_t* d_k256_kkeys = nullptr;
-    u32* d_k256_kwidx = nullptr;
-    size_t k256_key_cap = 0, k256_nkeys = 0;
-    sbv::kapt* d_k256_wtab = nullptr;      // comb w (SBV_K256_WIDE_ENTRIES) belongs to slot k256_wide_slots[w]
-    size_t k256_wtab_cap = 0;
-    std::vector<u32> k256_wide_slots;
+    // registered Ed25519 / secp256k1 keys: the default context's halves of g_edreg / g_k256reg ("registered Ed25519 and secp256k1 keys" below)
+    LocalRegDev edreg, k256reg;
     int profiling = 0;                     // 0 off, 1 = step triples + dominant-kernel pairs, 2 = dominant-kernel pairs only
     std::vector<hipEvent_t> prof_events;   // triples: before prep, after prep, after verify
     std::vector<hipEvent_t> prof_dom;      // pairs around the dominant kernel of grouped batches (nullptr pair = ungrouped)
@@ -244,6 +243,56 @@ hipError_t memset_now(void* p, int v, size_t bytes) {
     hipError_t e = hipMemset(p, v, bytes);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     return e;
+}
+
+// The host half of a local registry ("registered Ed25519 and secp256k1 keys" below): process-wide, guarded by its own mutex.
+struct LocalRegHost {
+    std::vector<std::string> keys;                    // slot -> the key / encoding bytes
+    std::unordered_map<std::string, u32> index;       // key bytes -> slot (bytes, not points: Ed25519's k hashes the bytes)
+    std::vector<uint8_t> valid;                       // slot -> the bytes are a point
+    u32 wide_max = 64;                                // sbv_*_wide_keys
+    std::mutex mu;
+    void forget() { keys.clear(); index.clear(); valid.clear(); }      // mu held; the widening cap is a setting and stays
+} g_edreg, g_k256reg;
+
+// ---- idioms the three key registries share ----
+// Slot assignment of a register_keys call: a key the index knows keeps its slot, a new one gets the next slot by first appearance
+// in the call (a key named twice gets one slot).  `fresh` = the new keys in slot order, the first of them slot `nreg`.
+void assign_slots(const std::unordered_map<std::string, u32>& index, size_t nreg, const uint8_t* keys, size_t key_bytes, size_t m, u32* slots_out,
+                  std::vector<std::string>& fresh) {
+    std::unordered_map<std::string, u32> pending;
+    for (size_t i = 0; i < m; ++i) {
+        const std::string k((const char*)keys + key_bytes * i, key_bytes);
+        auto it = index.find(k);
+        if (it != index.end()) { slots_out[i] = it->second; continue; }
+        auto pt = pending.find(k);
+        if (pt != pending.end()) { slots_out[i] = pt->second; continue; }
+        const u32 slot = (u32)(nreg + fresh.size());
+        pending.emplace(k, slot);
+        fresh.push_back(k);
+        slots_out[i] = slot;
+    }
+}
+// The 8-bit combs of `count` keys (`entries` table entries each), built on the host in parallel (one-time setup, the kernels' field
+// code): build(key bytes, table) -> the key is a point.
+template <class Entry, class Build>
+void build_combs_parallel(const std::string* keys, size_t count, size_t entries, std::vector<Entry>& tabs, std::vector<uint8_t>& valid, Build build) {
+    tabs.resize(count * entries);
+    valid.assign(count, 0);
+    size_t nt = std::thread::hardware_concurrency();
+    if (nt == 0) nt = 1;
+    if (nt > 64) nt = 64;
+    if (nt > count) nt = count;
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < nt; ++t)
+        th.emplace_back([&, t] {
+            for (size_t j = t; j < count; j += nt) valid[j] = build((const uint8_t*)keys[j].data(), &tabs[j * entries]) ? 1 : 0;
+        });
+    for (auto& x : th) x.join();
+}
+// which wide comb belongs to `slot`: its index in wide_slots, or wide_slots.size() when the slot has none
+size_t wide_comb_of(const std::vector<u32>& wide_slots, u32 slot) {
+    return (size_t)(std::find(wide_slots.begin(), wide_slots.end(), slot) - wide_slots.begin());
 }
 
 constexpr size_t kMaxChunk = (size_t)1 << 21;   // tuples per launch; bounds scratch at ~3.3 GB
@@ -1108,12 +1157,8 @@ int shutdown_context(Context& c) {
     if (c.d_kwidx) (void)hipFree(c.d_kwidx);
     c.d_kwide = nullptr; c.d_kwidx = nullptr; c.kwide_cap = 0; c.wide_slots.clear();
     c.key_index.clear();
-    for (void* p : {(void*)c.d_ed_ktab, (void*)c.d_ed_kvalid, (void*)c.d_ed_kenc, (void*)c.d_ed_kwidx, (void*)c.d_ed_wtab}) if (p) (void)hipFree(p);
-    c.d_ed_ktab = nullptr; c.d_ed_kvalid = nullptr; c.d_ed_kenc = nullptr; c.d_ed_kwidx = nullptr; c.d_ed_wtab = nullptr;
-    c.ed_key_cap = c.ed_nkeys = 0; c.ed_wtab_cap = 0; c.ed_wide_slots.clear();
-    for (void* p : {(void*)c.d_k256_ktab, (void*)c.d_k256_kvalid, (void*)c.d_k256_kkeys, (void*)c.d_k256_kwidx, (void*)c.d_k256_wtab}) if (p) (void)hipFree(p);
-    c.d_k256_ktab = nullptr; c.d_k256_kvalid = nullptr; c.d_k256_kkeys = nullptr; c.d_k256_kwidx = nullptr; c.d_k256_wtab = nullptr;
-    c.k256_key_cap = c.k256_nkeys = 0; c.k256_wtab_cap = 0; c.k256_wide_slots.clear();
+    local_reg_free(c.edreg);
+    local_reg_free(c.k256reg);
     if (c.h_small_in) (void)hipHostFree(c.h_small_in);
     if (c.h_small_out) (void)hipHostFree(c.h_small_out);
     c.h_small_in = c.h_small_out = nullptr; c.d_small_in = c.d_small_out = nullptr;
@@ -1144,13 +1189,13 @@ int shutdown_context(Context& c) {
 }
 }  // namespace
 
-static void ed_registry_forget();
-static void k256_registry_forget();
 extern "C" int sbv_shutdown(void) {
     std::unique_lock<std::shared_mutex> rl(g_reg_mu);
     g_reg = Registry();
-    ed_registry_forget();           // takes g_edreg_mu: g_reg_mu -> g_edreg_mu -> g_mu
-    k256_registry_forget();         // takes g_k256reg_mu alone
+    for (LocalRegHost* h : {&g_edreg, &g_k256reg}) {      // each local mutex in turn, released before g_mu: g_reg_mu -> local mutex, g_reg_mu -> g_mu
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->forget();
+    }
     std::lock_guard<std::mutex> lk(g_mu);
     rccl_teardown();
     for (auto& up : g_ctxs) {
@@ -1522,21 +1567,9 @@ int append_keys(Context& c, const std::string* keys, const sbv::apt* tabs, const
     c.nkeys += count;
     return SBV_OK;
 }
-// the 8-bit combs of `count` keys, built on the host (one-time setup, the same field code as the kernels), in parallel
+// the 8-bit combs of `count` P-256 keys
 void build_key_tables(const std::string* keys, size_t count, std::vector<sbv::apt>& tabs, std::vector<uint8_t>& valid) {
-    tabs.resize(count * (size_t)SBV_KEYTAB_ENTRIES);
-    valid.assign(count, 0);
-    size_t nt = std::thread::hardware_concurrency();
-    if (nt == 0) nt = 1;
-    if (nt > 64) nt = 64;
-    if (nt > count) nt = count;
-    std::vector<std::thread> th;
-    for (size_t t = 0; t < nt; ++t)
-        th.emplace_back([&, t] {
-            for (size_t j = t; j < count; j += nt)
-                valid[j] = sbv::host_build_key_table((const uint8_t*)keys[j].data(), &tabs[j * (size_t)SBV_KEYTAB_ENTRIES]) ? 1 : 0;
-        });
-    for (auto& x : th) x.join();
+    build_combs_parallel(keys, count, (size_t)SBV_KEYTAB_ENTRIES, tabs, valid, sbv::host_build_key_table);
 }
 // g_reg_mu (shared or exclusive) and c.mu held.  Brings device c's replica of the registry up to the process-wide one: the 8-bit
 // combs of the slots it has not seen, then the wide combs of the widened slots it lacks (built on the device: milliseconds).
@@ -1592,8 +1625,7 @@ extern "C" int sbv_p256_wide_selfcheck(uint32_t slot) {
     SBV_ENTER(c);
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    size_t w = c.wide_slots.size();
-    for (size_t i = 0; i < c.wide_slots.size(); ++i) if (c.wide_slots[i] == slot) w = i;
+    const size_t w = wide_comb_of(c.wide_slots, slot);
     if (w == c.wide_slots.size()) { g_err = "sbv_p256_wide_selfcheck: the slot has no wide comb"; return SBV_EINVAL; }
     const std::string* key = nullptr;
     for (const auto& kv : c.key_index) if (kv.second == slot) key = &kv.first;
@@ -1636,18 +1668,7 @@ extern "C" int sbv_p256_register_keys(const uint8_t* keys, size_t m, uint32_t* s
             if (rc != SBV_OK) return rc;
         }
         // de-duplicate, assign slots from the process-wide index
-        std::unordered_map<std::string, u32> pending;
-        for (size_t i = 0; i < m; ++i) {
-            const std::string k((const char*)keys + 64 * i, 64);
-            auto it = g_reg.index.find(k);
-            if (it != g_reg.index.end()) { slots_out[i] = it->second; continue; }
-            auto pt = pending.find(k);
-            if (pt != pending.end()) { slots_out[i] = pt->second; continue; }
-            const u32 slot = (u32)(g_reg.keys.size() + fresh.size());
-            pending.emplace(k, slot);
-            fresh.push_back(k);
-            slots_out[i] = slot;
-        }
+        assign_slots(g_reg.index, g_reg.keys.size(), keys, 64, m, slots_out, fresh);
         if (fresh.empty()) return SBV_OK;
         std::vector<sbv::apt> tabs;
         std::vector<uint8_t> valid;
@@ -2007,96 +2028,42 @@ extern "C" int sbv_ed25519_verify_msgs(const uint8_t* sigs, const uint8_t* pks, 
         });
 }
 
-// ---- registered Ed25519 keys (ed25519_keyed.h; include/sbv.h: sbv_ed25519_register_keys) ---------------------------------------
-// The registry is process-wide on the host — the slot index (encoding bytes -> slot), every registered encoding and its valid flag, the
-// widening cap — and lives on the default context's device: per slot the 8-bit comb of -A (384 KiB), the valid byte, the encoding for
-// the device front end, and for widened slots a 16-bit comb (64 MiB).  The host copy is what a replication to other contexts would be
-// built from.  Lock order: g_reg_mu -> g_edreg_mu -> g_mu -> Context::mu (registration, widening and clearing take g_edreg_mu and then
-// the default context; the verify entries take the context alone and read its half, which only changes under its lock).
+// ---- registered Ed25519 and secp256k1 keys (ed25519_keyed.h, k256_keyed.h; include/sbv.h: sbv_ed25519_register_keys, sbv_secp256k1_register_keys) ----
+// Two local registries, one implementation (the local_* templates below) over a traits struct per scheme (EdReg, K256Reg).
+// A registry is process-wide on the host (LocalRegHost: the slot index key bytes -> slot, every registered key and its valid flag, the
+// widening cap) and lives on the default context's device (LocalRegDev: per slot the 8-bit comb, the valid byte, the key bytes and, for
+// widened slots, the index of a 16-bit comb in the wide pool).  The host copy is what a replication to other contexts would be built from.
+// The two registries share nothing with each other, with the P-256 registry (Context::key_index, d_ktab) or with the key-table caches
+// (grp.kc, k256pool.kc): a byte string can be a key of several schemes.
+//   Ed25519    32-byte encodings; 8-bit comb of -A (384 KiB) built on the host in parallel and uploaded with the valid bytes and the
+//              encodings (the device front end reads them); 16-bit comb 64 MiB, one builder launch for all the slots of a call.
+//   secp256k1  64-byte keys, uploaded first (the builder's input); 8-bit comb of Q (270 KiB) built on the device by the grouped step's
+//              chain / rows / fill lanes, the valid bytes read back; 16-bit comb 35.7 MB, one builder launch per slot from the 8-bit comb.
+// Lock order: g_reg_mu -> the local registry's mutex -> g_mu -> Context::mu.  Registration, widening, clearing and the diagnostics take the
+// registry's mutex and then the default context; the verify entries take the context alone and read its half, which only changes under
+// its lock.  sbv_shutdown takes g_reg_mu and then each local mutex in turn.
+// Ordering on the device: every stream of this library is non-blocking, and a device-to-device hipMemcpy, like hipMemset (memset_now),
+// is ordered in the null stream only.  Both reserve functions therefore wait for the null stream after their copies, before the old
+// arrays are freed and before any kernel can read the new ones.
 namespace {
-struct EdRegistry {
-    std::vector<std::string> keys;                    // slot -> the 32 encoding bytes
-    std::unordered_map<std::string, u32> index;       // encoding bytes -> slot (bytes, not points: k hashes the bytes)
-    std::vector<uint8_t> valid;                       // slot -> the encoding is a point
-    u32 wide_max = 64;                                // sbv_ed25519_wide_keys
-} g_edreg;
-std::mutex g_edreg_mu;
-constexpr u32 kEdWideBuildBlocks = 256;              // the wide-comb builder's grid: 16 384 lanes, 84 MB of scratch while it runs
+constexpr u32 kEdWideBuildBlocks = 256;              // the Ed25519 wide-comb builder's grid: 16 384 lanes, 84 MB of scratch while it runs
+constexpr u32 kK256RegBuildKeys = 512;               // slots per pass of the secp256k1 comb builder: 78 MB of scratch while it runs
 
 sbv::EdKeyedRegistry ed_reg_view(const Context& c) {
+    const LocalRegDev& d = c.edreg;
     sbv::EdKeyedRegistry r;
-    r.ktab = c.d_ed_ktab; r.kvalid = c.d_ed_kvalid; r.kenc = c.d_ed_kenc;
-    r.wtab = c.d_ed_wtab; r.kwidx = c.ed_wide_slots.empty() ? nullptr : c.d_ed_kwidx;
-    r.nkeys = (u32)c.ed_nkeys;
+    r.ktab = reinterpret_cast<const sbv::aniels*>(d.ktab); r.kvalid = d.kvalid; r.kenc = d.kkeys;
+    r.wtab = d.wtab; r.kwidx = d.wide_slots.empty() ? nullptr : d.kwidx;
+    r.nkeys = (u32)d.nkeys;
     return r;
 }
-
-// c.mu held, the device current: room for `want` slots.  Doubles from 64 slots, copies the live slots on the device; a failure leaves the
-// old arrays (and so the registry) as they were.
-int ed_reg_reserve(Context& c, size_t want) {
-    if (want <= c.ed_key_cap) return SBV_OK;
-    size_t cap = c.ed_key_cap ? c.ed_key_cap : 64;
-    while (cap < want) cap *= 2;
-    if (cap > SBV_ED_REG_MAX_KEYS) cap = SBV_ED_REG_MAX_KEYS;
-    sbv::aniels* kt = nullptr; uint8_t* kv = nullptr; uint8_t* ke = nullptr; u32* kw = nullptr;
-    auto drop = [&] { for (void* p : {(void*)kt, (void*)kv, (void*)ke, (void*)kw}) if (p) (void)hipFree(p); (void)hipGetLastError(); };
-    if (hipMalloc(&kt, cap * (size_t)SBV_ED_KEYTAB_ENTRIES * sizeof(sbv::aniels)) != hipSuccess || hipMalloc(&kv, cap) != hipSuccess ||
-        hipMalloc(&ke, cap * 32) != hipSuccess || hipMalloc(&kw, cap * sizeof(u32)) != hipSuccess) {
-        drop();
-        g_err = "sbv_ed25519_register_keys: no device memory for the registry";
-        return SBV_ENOMEM;
-    }
-    const size_t n = c.ed_nkeys;
-    hipError_t e = hipDeviceSynchronize();          // nothing in flight reads the old arrays any more
-    if (e == hipSuccess && n) e = hipMemcpy(kt, c.d_ed_ktab, n * (size_t)SBV_ED_KEYTAB_ENTRIES * sizeof(sbv::aniels), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess && n) e = hipMemcpy(kv, c.d_ed_kvalid, n, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess && n) e = hipMemcpy(ke, c.d_ed_kenc, n * 32, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess && n) e = hipMemcpy(kw, c.d_ed_kwidx, n * sizeof(u32), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = memset_now(kw + n, 0xFF, (cap - n) * sizeof(u32));
-    if (e != hipSuccess) { drop(); return fail(SBV_EDEVICE, "sbv_ed25519_register_keys: growing the registry", e); }
-    for (void* p : {(void*)c.d_ed_ktab, (void*)c.d_ed_kvalid, (void*)c.d_ed_kenc, (void*)c.d_ed_kwidx}) if (p) (void)hipFree(p);
-    c.d_ed_ktab = kt; c.d_ed_kvalid = kv; c.d_ed_kenc = ke; c.d_ed_kwidx = kw;
-    c.ed_key_cap = cap;
-    return SBV_OK;
-}
-
-// c.mu held, the device current: room for `want` 16-bit combs (doubling, at most the cap), the combs there copied on the device
-int ed_wide_reserve(Context& c, size_t want, size_t cap_max) {
-    if (want <= c.ed_wtab_cap) return SBV_OK;
-    size_t cap = c.ed_wtab_cap ? c.ed_wtab_cap : 1;
-    while (cap < want) cap *= 2;
-    if (cap > cap_max) cap = cap_max;
-    uint8_t* w = nullptr;
-    if (hipMalloc(&w, cap * SBV_ED_HOT_COMB_BYTES) != hipSuccess) {
-        (void)hipGetLastError();
-        g_err = "sbv_ed25519_widen_keys: no device memory for the 16-bit combs";
-        return SBV_ENOMEM;
-    }
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess && !c.ed_wide_slots.empty())
-        e = hipMemcpy(w, c.d_ed_wtab, c.ed_wide_slots.size() * SBV_ED_HOT_COMB_BYTES, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) { (void)hipFree(w); return fail(SBV_EDEVICE, "sbv_ed25519_widen_keys: growing the comb pool", e); }
-    if (c.d_ed_wtab) (void)hipFree(c.d_ed_wtab);
-    c.d_ed_wtab = w;
-    c.ed_wtab_cap = cap;
-    return SBV_OK;
-}
-
-// `count` slots' 8-bit combs, built on the host in parallel (one-time setup, the kernels' field code)
-void ed_build_reg_combs(const std::string* keys, size_t count, std::vector<sbv::aniels>& tabs, std::vector<uint8_t>& valid) {
-    tabs.resize(count * (size_t)SBV_ED_KEYTAB_ENTRIES);
-    valid.assign(count, 0);
-    size_t nt = std::thread::hardware_concurrency();
-    if (nt == 0) nt = 1;
-    if (nt > 64) nt = 64;
-    if (nt > count) nt = count;
-    std::vector<std::thread> th;
-    for (size_t t = 0; t < nt; ++t)
-        th.emplace_back([&, t] {
-            for (size_t j = t; j < count; j += nt)
-                valid[j] = sbv::ed_keyed_host_comb((const uint8_t*)keys[j].data(), &tabs[j * (size_t)SBV_ED_KEYTAB_ENTRIES]) ? 1 : 0;
-        });
-    for (auto& x : th) x.join();
+sbv::K256KeyedRegistry k256_reg_view(const Context& c) {
+    const LocalRegDev& d = c.k256reg;
+    sbv::K256KeyedRegistry r;
+    r.ktab = reinterpret_cast<const sbv::kapt*>(d.ktab); r.kvalid = d.kvalid;
+    r.wtab = reinterpret_cast<const sbv::kapt*>(d.wtab); r.kwidx = d.wide_slots.empty() ? nullptr : d.kwidx;
+    r.nkeys = (u32)d.nkeys;
+    return r;
 }
 
 // one chunk (m <= c.cap) of keyed records on `stream`: expand into the qtab planes (128 of their 1792 bytes per tuple), the accumulator,
@@ -2112,237 +2079,405 @@ int enqueue_ed_keyed(Context& c, const uint8_t* d_recs, const u32* d_slots, size
                                                           d_bitmap, stream));
     return SBV_OK;
 }
-// the tables every keyed call needs: the comb of B of the grouped step (ensure_ed_bcomb falls back to the one-lane kernel's at 16 bits)
-int ensure_ed_keyed(Context& c) {
-    const int rc = ensure_ed_table(c);
-    return rc == SBV_OK ? ensure_ed_bcomb(c) : rc;
-}
-}  // namespace
-
-static void ed_registry_forget() {
-    std::lock_guard<std::mutex> lk(g_edreg_mu);
-    const u32 wm = g_edreg.wide_max;
-    g_edreg = EdRegistry();
-    g_edreg.wide_max = wm;
+// one chunk (m <= c.cap) of keyed records on `stream`: stage A on the records into the scratch planes, then the keyed stage B
+int enqueue_k256_keyed(Context& c, const uint8_t* d_recs, const u32* d_slots, size_t m, uint8_t* d_bitmap, hipStream_t stream, hipEvent_t after_prep = nullptr) {
+    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_verify_keyed(d_recs, d_slots, m, scratch_view(c), k256_reg_view(c), c.d_k256_gcomb, c.k256_gbits, d_bitmap, stream, after_prep));
+    return SBV_OK;
 }
 
-extern "C" int sbv_ed25519_register_keys(const uint8_t* pks, size_t m, uint32_t* slots_out) {
-    std::lock_guard<std::mutex> rl(g_edreg_mu);
-    SBV_ENTER(c);
+// g_err of a registry call: the scheme's prefix + "_" + `what` ("register_keys: ..."), and the HIP error's text behind it if there is one
+template <class T>
+int local_fail(int code, const char* what, hipError_t e = hipSuccess) {
+    g_err = std::string(T::kPrefix) + "_" + what;
+    if (e != hipSuccess) g_err += std::string(": ") + hipGetErrorString(e);
+    return code;
+}
+
+// Per-scheme traits: the sizes, and the three operations that differ.  Each runs with the registry's mutex and c.mu held and the
+// device current.
+//   build_slots   the 8-bit combs, valid bytes and key bytes of slots [s0, s0 + fresh.size()) on the device (they lie beyond nkeys: no batch
+//                 reads them yet); valid[i] = fresh[i] is a point
+//   build_wide    combs w0, w0 + 1, ... of the wide pool = the 16-bit combs of the slots in `todo`, complete when it returns
+//   wide_matches  1 = `got` (kWideBytes read back from the pool) is the host builder's 16-bit comb of `key`; 0 also when key is not a point
+struct EdReg {
+    static constexpr const char* kPrefix = "sbv_ed25519";
+    static constexpr size_t kKeyBytes = 32, kCombBytes = (size_t)SBV_ED_KEYTAB_ENTRIES * sizeof(sbv::aniels), kWideBytes = SBV_ED_HOT_COMB_BYTES;
+    static constexpr size_t kRecBytes = SBV_ED_REC_BYTES, kMaxKeys = SBV_ED_REG_MAX_KEYS;
+    static constexpr u32 kWideBits = SBV_ED_HOT_BITS;
+    static constexpr bool kStageA = false;             // run_chunks_*: the keyed step has no stage A of its own to time
+    static LocalRegHost& host() { return g_edreg; }
+    static LocalRegDev& dev(Context& c) { return c.edreg; }
+    // the tables every keyed call needs: the comb of B of the grouped step (ensure_ed_bcomb falls back to the one-lane kernel's at 16 bits)
+    static int ensure(Context& c) {
+        const int rc = ensure_ed_table(c);
+        return rc == SBV_OK ? ensure_ed_bcomb(c) : rc;
+    }
+    static int enqueue(Context& c, const uint8_t* d_recs, const u32* d_slots, size_t m, uint8_t* d_bitmap, hipStream_t stream, hipEvent_t) {
+        return enqueue_ed_keyed(c, d_recs, d_slots, m, d_bitmap, stream);
+    }
+    static int build_slots(Context&, LocalRegDev& d, size_t s0, const std::vector<std::string>& fresh, const std::string& blob, std::vector<uint8_t>& valid) {
+        std::vector<sbv::aniels> tabs;
+        build_combs_parallel(fresh.data(), fresh.size(), (size_t)SBV_ED_KEYTAB_ENTRIES, tabs, valid, sbv::ed_keyed_host_comb);
+        HIP_TRY(SBV_EDEVICE, hipMemcpy(d.ktab + s0 * kCombBytes, tabs.data(), tabs.size() * sizeof(sbv::aniels), hipMemcpyHostToDevice));
+        HIP_TRY(SBV_EDEVICE, hipMemcpy(d.kvalid + s0, valid.data(), valid.size(), hipMemcpyHostToDevice));
+        HIP_TRY(SBV_EDEVICE, hipMemcpy(d.kkeys + s0 * kKeyBytes, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        return SBV_OK;
+    }
+    // one launch over the (slot, comb) pairs
+    static int build_wide(Context& c, LocalRegDev& d, const std::vector<u32>& todo, size_t w0) {
+        std::vector<u32> plist(2 * todo.size());
+        for (size_t i = 0; i < todo.size(); ++i) { plist[2 * i] = todo[i]; plist[2 * i + 1] = (u32)(w0 + i); }
+        u32* d_plist = nullptr;
+        u32* d_tmp = nullptr;
+        const size_t tmp_bytes = (size_t)kEdWideBuildBlocks * 64 * SBV_ED_HOT_TMP_WORDS * sizeof(u32);
+        auto drop = [&] { if (d_plist) (void)hipFree(d_plist); if (d_tmp) (void)hipFree(d_tmp); };
+        if (hipMalloc(&d_plist, plist.size() * sizeof(u32)) != hipSuccess || hipMalloc(&d_tmp, tmp_bytes) != hipSuccess) {
+            drop();
+            (void)hipGetLastError();
+            return local_fail<EdReg>(SBV_ENOMEM, "widen_keys: no device memory for the builder");
+        }
+        hipError_t e = hipMemcpy(d_plist, plist.data(), plist.size() * sizeof(u32), hipMemcpyHostToDevice);
+        if (e == hipSuccess && c.busy_valid) e = hipStreamWaitEvent(c.stream, c.busy, 0);
+        if (e == hipSuccess) e = sbv::launch_ed_keyed_widen(d_plist, (u32)todo.size(), ed_reg_view(c).ktab, d_tmp, kEdWideBuildBlocks, d.wtab, c.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+        drop();
+        return e == hipSuccess ? SBV_OK : local_fail<EdReg>(SBV_EDEVICE, "widen_keys: building the combs", e);
+    }
+    // the comb of -A (build_ed_window_of, one thread per window), entry by entry at the pool's pitch
+    static int wide_matches(const std::string& key, const uint8_t* got) {
+        u32 enc[8];
+        memcpy(enc, key.data(), 32);
+        sbv::ept A;
+        if (!sbv::ed_decompress(A, enc)) return 0;
+        sbv::fe25_neg(A.X, A.X);
+        sbv::fe25_neg(A.T, A.T);
+        std::vector<sbv::aniels> want((size_t)SBV_ED_HOT_WINDOWS * SBV_ED_HOT_PER_WINDOW);
+        std::vector<std::thread> th;
+        for (int j = 0; j < SBV_ED_HOT_WINDOWS; ++j)
+            th.emplace_back([&, j] { sbv::build_ed_window_of(A, SBV_ED_HOT_BITS, j, want.data() + (size_t)j * SBV_ED_HOT_PER_WINDOW); });
+        for (auto& t : th) t.join();
+        for (size_t e = 0; e < want.size(); ++e)
+            if (memcmp(got + e * SBV_ED_HOT_PITCH, &want[e], sizeof(sbv::aniels)) != 0) return 0;
+        return 1;
+    }
+};
+
+struct K256Reg {
+    static constexpr const char* kPrefix = "sbv_secp256k1";
+    static constexpr size_t kKeyBytes = SBV_K256_KEY_BYTES, kCombBytes = (size_t)SBV_K256_KEYTAB_ENTRIES * sizeof(sbv::kapt), kWideBytes = SBV_K256_WIDE_COMB_BYTES;
+    static constexpr size_t kRecBytes = SBV_K256_REC_BYTES, kMaxKeys = SBV_K256_REG_MAX_KEYS;
+    static constexpr u32 kWideBits = SBV_K256_WIDE_BITS;
+    static constexpr bool kStageA = true;              // run_chunks_*: the step records after_prep behind its stage A
+    static LocalRegHost& host() { return g_k256reg; }
+    static LocalRegDev& dev(Context& c) { return c.k256reg; }
+    // the table every keyed call needs: the comb of G of the grouped step (which borrows the one-lane kernel's at 16 bits)
+    static int ensure(Context& c) {
+        const int rc = ensure_k256_table(c);
+        return rc == SBV_OK ? ensure_k256_gcomb(c) : rc;
+    }
+    static int enqueue(Context& c, const uint8_t* d_recs, const u32* d_slots, size_t m, uint8_t* d_bitmap, hipStream_t stream, hipEvent_t after_prep) {
+        return enqueue_k256_keyed(c, d_recs, d_slots, m, d_bitmap, stream, after_prep);
+    }
+    // on the device, in passes of kK256RegBuildKeys slots that share one scratch buffer
+    static int build_slots(Context& c, LocalRegDev& d, size_t s0, const std::vector<std::string>& fresh, const std::string& blob, std::vector<uint8_t>& valid) {
+        const size_t nf = fresh.size();
+        const u32 pass = nf < kK256RegBuildKeys ? (u32)nf : kK256RegBuildKeys;
+        u32* d_work = nullptr;
+        if (hipMalloc(&d_work, sbv::k256_reg_build_words(pass) * sizeof(u32)) != hipSuccess) {
+            (void)hipGetLastError();
+            return local_fail<K256Reg>(SBV_ENOMEM, "register_keys: no device memory for the builder");
+        }
+        valid.assign(nf, 0);
+        hipError_t e = hipMemcpy(d.kkeys + s0 * kKeyBytes, blob.data(), blob.size(), hipMemcpyHostToDevice);
+        for (size_t off = 0; off < nf && e == hipSuccess; off += pass) {
+            const u32 cnt = (u32)(nf - off < pass ? nf - off : pass);
+            e = sbv::launch_k256_reg_build(d.kkeys, (u32)(s0 + off), cnt, d_work, reinterpret_cast<sbv::kapt*>(d.ktab), d.kvalid, c.stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c.stream);        // the next pass reuses the scratch
+        }
+        (void)hipFree(d_work);                      // build scratch lives for the call only
+        if (e == hipSuccess) e = hipMemcpy(valid.data(), d.kvalid + s0, nf, hipMemcpyDeviceToHost);
+        return e == hipSuccess ? SBV_OK : local_fail<K256Reg>(SBV_EDEVICE, "register_keys: building the combs", e);
+    }
+    // one launch per slot, one after the other on the stream: they share the scratch
+    static int build_wide(Context& c, LocalRegDev& d, const std::vector<u32>& todo, size_t w0) {
+        u32* d_tmp = nullptr;
+        if (hipMalloc(&d_tmp, sbv::k256_widetab_tmp_words() * sizeof(u32)) != hipSuccess) {
+            (void)hipGetLastError();
+            return local_fail<K256Reg>(SBV_ENOMEM, "widen_keys: no device memory for the builder");
+        }
+        hipError_t e = hipSuccess;
+        if (c.busy_valid) e = hipStreamWaitEvent(c.stream, c.busy, 0);
+        for (size_t i = 0; i < todo.size() && e == hipSuccess; ++i)
+            e = sbv::launch_k256_widetab(k256_reg_view(c).ktab, todo[i], d_tmp, reinterpret_cast<sbv::kapt*>(d.wtab), (u32)(w0 + i), c.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+        (void)hipFree(d_tmp);                       // build scratch lives for the call only
+        return e == hipSuccess ? SBV_OK : local_fail<K256Reg>(SBV_EDEVICE, "widen_keys: building the combs", e);
+    }
+    // the comb of Q (host_build_k256_wide_comb), byte for byte
+    static int wide_matches(const std::string& key, const uint8_t* got) {
+        std::vector<sbv::kapt> want(SBV_K256_WIDE_ENTRIES);
+        if (!sbv::host_build_k256_wide_comb((const uint8_t*)key.data(), want.data())) return 0;
+        return memcmp(got, want.data(), kWideBytes) == 0 ? 1 : 0;
+    }
+};
+
+// every registry entry but key_count: the registry's mutex, then the default context
+#define SBV_ENTER_REG(T, h, c, d)                     \
+    LocalRegHost& h = T::host();                      \
+    std::lock_guard<std::mutex> rl(h.mu);             \
+    SBV_ENTER(c);                                     \
+    LocalRegDev& d = T::dev(c)
+
+// c.mu held, the device current: room for `want` slots.  Doubles from 64 slots, copies the live slots on the device; a failure leaves the
+// old arrays (and so the registry) as they were.
+template <class T>
+int local_reg_reserve(LocalRegDev& d, size_t want) {
+    if (want <= d.key_cap) return SBV_OK;
+    size_t cap = d.key_cap ? d.key_cap : 64;
+    while (cap < want) cap *= 2;
+    if (cap > T::kMaxKeys) cap = T::kMaxKeys;
+    uint8_t* kt = nullptr; uint8_t* kv = nullptr; uint8_t* kk = nullptr; u32* kw = nullptr;
+    auto drop = [&] { for (void* p : {(void*)kt, (void*)kv, (void*)kk, (void*)kw}) if (p) (void)hipFree(p); (void)hipGetLastError(); };
+    if (hipMalloc(&kt, cap * T::kCombBytes) != hipSuccess || hipMalloc(&kv, cap) != hipSuccess ||
+        hipMalloc(&kk, cap * T::kKeyBytes) != hipSuccess || hipMalloc(&kw, cap * sizeof(u32)) != hipSuccess) {
+        drop();
+        return local_fail<T>(SBV_ENOMEM, "register_keys: no device memory for the registry");
+    }
+    const size_t n = d.nkeys;
+    hipError_t e = hipDeviceSynchronize();          // nothing in flight reads the old arrays any more
+    if (e == hipSuccess && n) e = hipMemcpy(kt, d.ktab, n * T::kCombBytes, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(kv, d.kvalid, n, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(kk, d.kkeys, n * T::kKeyBytes, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(kw, d.kwidx, n * sizeof(u32), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);     // the copies are ordered in the null stream only (banner above)
+    if (e == hipSuccess) e = memset_now(kw + n, 0xFF, (cap - n) * sizeof(u32));
+    if (e != hipSuccess) { drop(); return local_fail<T>(SBV_EDEVICE, "register_keys: growing the registry", e); }
+    for (void* p : {(void*)d.ktab, (void*)d.kvalid, (void*)d.kkeys, (void*)d.kwidx}) if (p) (void)hipFree(p);
+    d.ktab = kt; d.kvalid = kv; d.kkeys = kk; d.kwidx = kw;
+    d.key_cap = cap;
+    return SBV_OK;
+}
+
+// c.mu held, the device current: room for `want` 16-bit combs (doubling from 1, at most the cap), the combs there copied on the device
+template <class T>
+int local_wide_reserve(LocalRegDev& d, size_t want, size_t cap_max) {
+    if (want <= d.wtab_cap) return SBV_OK;
+    size_t cap = d.wtab_cap ? d.wtab_cap : 1;
+    while (cap < want) cap *= 2;
+    if (cap > cap_max) cap = cap_max;
+    uint8_t* w = nullptr;
+    if (hipMalloc(&w, cap * T::kWideBytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return local_fail<T>(SBV_ENOMEM, "widen_keys: no device memory for the 16-bit combs");
+    }
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess && !d.wide_slots.empty()) e = hipMemcpy(w, d.wtab, d.wide_slots.size() * T::kWideBytes, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);     // as in local_reg_reserve
+    if (e != hipSuccess) { (void)hipFree(w); return local_fail<T>(SBV_EDEVICE, "widen_keys: growing the comb pool", e); }
+    if (d.wtab) (void)hipFree(d.wtab);
+    d.wtab = w;
+    d.wtab_cap = cap;
+    return SBV_OK;
+}
+
+template <class T>
+int local_register_keys(const uint8_t* keys, size_t m, uint32_t* slots_out) {
+    SBV_ENTER_REG(T, h, c, d);
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (m == 0) return SBV_OK;
-    if (!pks || !slots_out) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (!keys || !slots_out) { g_err = "null pointer"; return SBV_EINVAL; }
     std::vector<u32> out(m);
-    std::vector<std::string> fresh;                 // encodings that need a slot, in slot order
-    std::unordered_map<std::string, u32> pending;
-    for (size_t i = 0; i < m; ++i) {
-        const std::string k((const char*)pks + 32 * i, 32);
-        auto it = g_edreg.index.find(k);
-        if (it != g_edreg.index.end()) { out[i] = it->second; continue; }
-        auto pt = pending.find(k);
-        if (pt != pending.end()) { out[i] = pt->second; continue; }
-        const u32 slot = (u32)(g_edreg.keys.size() + fresh.size());
-        pending.emplace(k, slot);
-        fresh.push_back(k);
-        out[i] = slot;
-    }
-    if (g_edreg.keys.size() + fresh.size() > SBV_ED_REG_MAX_KEYS) { g_err = "sbv_ed25519_register_keys: more than 65536 keys"; return SBV_EINVAL; }
+    std::vector<std::string> fresh;                 // keys that need a slot, in slot order
+    assign_slots(h.index, h.keys.size(), keys, T::kKeyBytes, m, out.data(), fresh);
+    if (h.keys.size() + fresh.size() > T::kMaxKeys) return local_fail<T>(SBV_EINVAL, "register_keys: more than 65536 keys");
     if (!fresh.empty()) {
         HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-        std::vector<sbv::aniels> tabs;
-        std::vector<uint8_t> valid;
-        ed_build_reg_combs(fresh.data(), fresh.size(), tabs, valid);
-        std::string enc;
-        for (const std::string& k : fresh) enc += k;
-        const int rc = ed_reg_reserve(c, c.ed_nkeys + fresh.size());
+        int rc = local_reg_reserve<T>(d, d.nkeys + fresh.size());
         if (rc != SBV_OK) return rc;
-        // the new slots lie beyond ed_nkeys: no batch reads them until the count below is raised
-        const size_t s0 = c.ed_nkeys;
-        HIP_TRY(SBV_EDEVICE, hipMemcpy(c.d_ed_ktab + s0 * (size_t)SBV_ED_KEYTAB_ENTRIES, tabs.data(), tabs.size() * sizeof(sbv::aniels), hipMemcpyHostToDevice));
-        HIP_TRY(SBV_EDEVICE, hipMemcpy(c.d_ed_kvalid + s0, valid.data(), valid.size(), hipMemcpyHostToDevice));
-        HIP_TRY(SBV_EDEVICE, hipMemcpy(c.d_ed_kenc + s0 * 32, enc.data(), enc.size(), hipMemcpyHostToDevice));
-        c.ed_nkeys += fresh.size();
+        std::string blob;
+        for (const std::string& k : fresh) blob += k;
+        std::vector<uint8_t> valid;
+        if ((rc = T::build_slots(c, d, d.nkeys, fresh, blob, valid)) != SBV_OK) return rc;
+        // only now: a count raised or an index entry left behind by a failed call would hand a slot number to the wrong key's comb
+        d.nkeys += fresh.size();
         for (size_t i = 0; i < fresh.size(); ++i) {
-            g_edreg.index.emplace(fresh[i], (u32)g_edreg.keys.size());
-            g_edreg.keys.push_back(fresh[i]);
-            g_edreg.valid.push_back(valid[i]);
+            h.index.emplace(fresh[i], (u32)h.keys.size());
+            h.keys.push_back(fresh[i]);
+            h.valid.push_back(valid[i]);
         }
     }
     memcpy(slots_out, out.data(), m * sizeof(u32));
     return SBV_OK;
 }
 
-extern "C" int sbv_ed25519_key_count(void) {
+template <class T>
+int local_key_count() {
     SBV_ENTER(c);
-    return c.ready ? (int)c.ed_nkeys : SBV_ENOTINIT;
+    return c.ready ? (int)T::dev(c).nkeys : SBV_ENOTINIT;
 }
 
-extern "C" int sbv_ed25519_clear_keys(void) {
-    std::lock_guard<std::mutex> rl(g_edreg_mu);
-    SBV_ENTER(c);
+template <class T>
+int local_clear_keys() {
+    SBV_ENTER_REG(T, h, c, d);
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    if (c.d_ed_kwidx && c.ed_key_cap) HIP_TRY(SBV_EDEVICE, memset_now(c.d_ed_kwidx, 0xFF, c.ed_key_cap * sizeof(u32)));
-    c.ed_nkeys = 0;                  // the allocations stay for the next registry
-    c.ed_wide_slots.clear();
-    const u32 wm = g_edreg.wide_max;
-    g_edreg = EdRegistry();
-    g_edreg.wide_max = wm;
+    if (d.kwidx && d.key_cap) HIP_TRY(SBV_EDEVICE, memset_now(d.kwidx, 0xFF, d.key_cap * sizeof(u32)));
+    d.nkeys = 0;                     // the allocations stay for the next registry
+    d.wide_slots.clear();
+    h.forget();
     return SBV_OK;
 }
 
-extern "C" int sbv_ed25519_wide_keys(uint32_t max_keys) {
-    std::lock_guard<std::mutex> rl(g_edreg_mu);
-    SBV_ENTER(c);
+template <class T>
+int local_wide_keys(uint32_t max_keys) {
+    SBV_ENTER_REG(T, h, c, d);
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
-    if (max_keys > 4096) { g_err = "sbv_ed25519_wide_keys: at most 4096 keys"; return SBV_EINVAL; }
-    g_edreg.wide_max = max_keys;
-    if (c.ed_wide_slots.size() <= max_keys) return SBV_OK;
-    // fewer than are wide: the first max_keys slots keep their combs (combs 0 .. max_keys - 1), the others go back to their 8-bit combs
+    if (max_keys > 4096) return local_fail<T>(SBV_EINVAL, "wide_keys: at most 4096 keys");
+    h.wide_max = max_keys;
+    if (d.wide_slots.size() <= max_keys) return SBV_OK;
+    // fewer than are wide: the first max_keys widened slots keep their combs (combs 0 .. max_keys - 1), the others go back to their 8-bit combs
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    const u32 none = SBV_ED_WIDE_NONE;
-    for (size_t w = max_keys; w < c.ed_wide_slots.size(); ++w)
-        HIP_TRY(SBV_EDEVICE, hipMemcpy(c.d_ed_kwidx + c.ed_wide_slots[w], &none, sizeof(u32), hipMemcpyHostToDevice));
-    c.ed_wide_slots.resize(max_keys);
-    if (max_keys == 0 && c.d_ed_wtab) { (void)hipFree(c.d_ed_wtab); c.d_ed_wtab = nullptr; c.ed_wtab_cap = 0; }
+    const u32 none = 0xFFFFFFFFu;
+    for (size_t w = max_keys; w < d.wide_slots.size(); ++w)
+        HIP_TRY(SBV_EDEVICE, hipMemcpy(d.kwidx + d.wide_slots[w], &none, sizeof(u32), hipMemcpyHostToDevice));
+    d.wide_slots.resize(max_keys);
+    if (max_keys == 0 && d.wtab) { (void)hipFree(d.wtab); d.wtab = nullptr; d.wtab_cap = 0; }
     return SBV_OK;
 }
 
-extern "C" int sbv_ed25519_widen_keys(const uint32_t* slots, size_t m) {
-    std::lock_guard<std::mutex> rl(g_edreg_mu);
-    SBV_ENTER(c);
+template <class T>
+int local_widen_keys(const uint32_t* slots, size_t m) {
+    SBV_ENTER_REG(T, h, c, d);
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (m == 0) return SBV_OK;
     if (!slots) { g_err = "null pointer"; return SBV_EINVAL; }
     for (size_t i = 0; i < m; ++i)
-        if (slots[i] >= c.ed_nkeys) { g_err = "sbv_ed25519_widen_keys: unregistered slot"; return SBV_EINVAL; }
+        if (slots[i] >= d.nkeys) return local_fail<T>(SBV_EINVAL, "widen_keys: unregistered slot");
     // the slots that get a comb now: registered, a point, not wide yet, within the cap (the others stay narrow: no error)
     std::vector<u32> todo;
     for (size_t i = 0; i < m; ++i) {
         const u32 s = slots[i];
-        if (!g_edreg.valid[s]) continue;
-        if (std::find(c.ed_wide_slots.begin(), c.ed_wide_slots.end(), s) != c.ed_wide_slots.end()) continue;
+        if (!h.valid[s]) continue;
+        if (wide_comb_of(d.wide_slots, s) != d.wide_slots.size()) continue;
         if (std::find(todo.begin(), todo.end(), s) != todo.end()) continue;
-        if (c.ed_wide_slots.size() + todo.size() >= g_edreg.wide_max) break;
+        if (d.wide_slots.size() + todo.size() >= h.wide_max) break;
         todo.push_back(s);
     }
     if (todo.empty()) return SBV_OK;
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    const size_t w0 = c.ed_wide_slots.size();
-    int rc = ed_wide_reserve(c, w0 + todo.size(), g_edreg.wide_max);
+    const size_t w0 = d.wide_slots.size();
+    int rc = local_wide_reserve<T>(d, w0 + todo.size(), h.wide_max);
+    if (rc == SBV_OK) rc = T::build_wide(c, d, todo, w0);
     if (rc != SBV_OK) return rc;
-    std::vector<u32> plist(2 * todo.size());
-    for (size_t i = 0; i < todo.size(); ++i) { plist[2 * i] = todo[i]; plist[2 * i + 1] = (u32)(w0 + i); }
-    u32* d_plist = nullptr;
-    u32* d_tmp = nullptr;
-    const size_t tmp_bytes = (size_t)kEdWideBuildBlocks * 64 * SBV_ED_HOT_TMP_WORDS * sizeof(u32);
-    auto drop = [&] { if (d_plist) (void)hipFree(d_plist); if (d_tmp) (void)hipFree(d_tmp); };
-    if (hipMalloc(&d_plist, plist.size() * sizeof(u32)) != hipSuccess || hipMalloc(&d_tmp, tmp_bytes) != hipSuccess) {
-        drop();
-        (void)hipGetLastError();
-        g_err = "sbv_ed25519_widen_keys: no device memory for the builder";
-        return SBV_ENOMEM;
-    }
-    hipError_t e = hipMemcpy(d_plist, plist.data(), plist.size() * sizeof(u32), hipMemcpyHostToDevice);
-    if (e == hipSuccess && c.busy_valid) e = hipStreamWaitEvent(c.stream, c.busy, 0);
-    if (e == hipSuccess) e = sbv::launch_ed_keyed_widen(d_plist, (u32)todo.size(), c.d_ed_ktab, d_tmp, kEdWideBuildBlocks, c.d_ed_wtab, c.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    drop();
-    if (e != hipSuccess) return fail(SBV_EDEVICE, "sbv_ed25519_widen_keys: building the combs", e);
-    // publish: a comb is used only once it is complete
+    // publish: a comb is used only once it is complete; a failure takes back what this call published and leaves wide_slots as it was
     for (size_t i = 0; i < todo.size(); ++i) {
         const u32 w = (u32)(w0 + i);
-        e = hipMemcpy(c.d_ed_kwidx + todo[i], &w, sizeof(u32), hipMemcpyHostToDevice);
+        const hipError_t e = hipMemcpy(d.kwidx + todo[i], &w, sizeof(u32), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
-            const u32 none = SBV_ED_WIDE_NONE;
-            for (size_t j = 0; j < i; ++j) (void)hipMemcpy(c.d_ed_kwidx + todo[j], &none, sizeof(u32), hipMemcpyHostToDevice);
-            return fail(SBV_EDEVICE, "sbv_ed25519_widen_keys: publish", e);
+            const u32 none = 0xFFFFFFFFu;
+            for (size_t j = 0; j < i; ++j) (void)hipMemcpy(d.kwidx + todo[j], &none, sizeof(u32), hipMemcpyHostToDevice);
+            return local_fail<T>(SBV_EDEVICE, "widen_keys: publish", e);
         }
     }
-    c.ed_wide_slots.insert(c.ed_wide_slots.end(), todo.begin(), todo.end());
+    d.wide_slots.insert(d.wide_slots.end(), todo.begin(), todo.end());
     return SBV_OK;
 }
 
-extern "C" int sbv_ed25519_wide_key_stats(uint32_t out[4]) {
-    std::lock_guard<std::mutex> rl(g_edreg_mu);
-    SBV_ENTER(c);
+template <class T>
+int local_wide_key_stats(uint32_t out[4]) {
+    SBV_ENTER_REG(T, h, c, d);
     if (!c.ready) return SBV_ENOTINIT;
     if (!out) return SBV_EINVAL;
-    out[0] = (u32)c.ed_wide_slots.size(); out[1] = SBV_ED_HOT_BITS; out[2] = g_edreg.wide_max;
-    out[3] = (u32)(SBV_ED_HOT_COMB_BYTES >> 10);
+    out[0] = (u32)d.wide_slots.size(); out[1] = T::kWideBits; out[2] = h.wide_max;
+    out[3] = (u32)(T::kWideBytes >> 10);
     return SBV_OK;
 }
 
-// 1 = the device-resident 16-bit comb of `slot` equals the host builder's comb of -A (build_ed_window_of) entry by entry
-extern "C" int sbv_ed25519_wide_selfcheck(uint32_t slot) {
-    std::lock_guard<std::mutex> rl(g_edreg_mu);
-    SBV_ENTER(c);
+// 1 = the device-resident 16-bit comb of `slot` equals the host builder's (T::wide_matches)
+template <class T>
+int local_wide_selfcheck(uint32_t slot) {
+    SBV_ENTER_REG(T, h, c, d);
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
-    size_t w = c.ed_wide_slots.size();
-    for (size_t i = 0; i < c.ed_wide_slots.size(); ++i) if (c.ed_wide_slots[i] == slot) w = i;
-    if (w == c.ed_wide_slots.size()) { g_err = "sbv_ed25519_wide_selfcheck: the slot has no wide comb"; return SBV_EINVAL; }
-    u32 key[8];
-    memcpy(key, g_edreg.keys[slot].data(), 32);
-    sbv::ept A;
-    if (!sbv::ed_decompress(A, key)) return 0;                          // only points are widened
-    sbv::fe25_neg(A.X, A.X);
-    sbv::fe25_neg(A.T, A.T);
-    std::vector<sbv::aniels> want((size_t)SBV_ED_HOT_WINDOWS * SBV_ED_HOT_PER_WINDOW);
-    {
-        std::vector<std::thread> th;
-        for (int j = 0; j < SBV_ED_HOT_WINDOWS; ++j)
-            th.emplace_back([&, j] { sbv::build_ed_window_of(A, SBV_ED_HOT_BITS, j, want.data() + (size_t)j * SBV_ED_HOT_PER_WINDOW); });
-        for (auto& t : th) t.join();
-    }
+    const size_t w = wide_comb_of(d.wide_slots, slot);
+    if (w == d.wide_slots.size()) return local_fail<T>(SBV_EINVAL, "wide_selfcheck: the slot has no wide comb");
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    std::vector<uint8_t> got(SBV_ED_HOT_COMB_BYTES);
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), c.d_ed_wtab + w * SBV_ED_HOT_COMB_BYTES, got.size(), hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < want.size(); ++e)
-        if (memcmp(got.data() + e * SBV_ED_HOT_PITCH, &want[e], sizeof(sbv::aniels)) != 0) return 0;
-    return 1;
+    std::vector<uint8_t> got(T::kWideBytes);
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), d.wtab + w * T::kWideBytes, got.size(), hipMemcpyDeviceToHost));
+    return T::wide_matches(h.keys[slot], got.data());
 }
 
-extern "C" int sbv_ed25519_verify_batch_keyed_dev(const void* d_rsk, const void* d_slots, size_t n, void* d_bitmap, void* hip_stream) {
+template <class T>
+int local_verify_keyed_dev(const void* d_recs, const void* d_slots, size_t n, void* d_bitmap, void* hip_stream) {
     SBV_ENTER(c);
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (n == 0) return SBV_OK;
-    if (!d_rsk || !d_slots || !d_bitmap || (reinterpret_cast<uintptr_t>(d_rsk) & 15)) { g_err = "null or misaligned device pointer"; return SBV_EINVAL; }
+    if (!d_recs || !d_slots || !d_bitmap || (reinterpret_cast<uintptr_t>(d_recs) & 15)) { g_err = "null or misaligned device pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (c.ed_nkeys == 0) {           // every slot is out of range: every record is a reject
+    if (T::dev(c).nkeys == 0) {      // every slot is out of range: every record is a reject
         HIP_TRY(SBV_EDEVICE, hipMemsetAsync(d_bitmap, 0, (n + 7) / 8, stream));
         return SBV_OK;
     }
-    const int rc = ensure_ed_keyed(c);
+    const int rc = T::ensure(c);
     if (rc != SBV_OK) return rc;
-    const uint8_t* src = static_cast<const uint8_t*>(d_rsk);
+    const uint8_t* src = static_cast<const uint8_t*>(d_recs);
     const u32* sl = static_cast<const u32*>(d_slots);
     uint8_t* dst = static_cast<uint8_t*>(d_bitmap);
-    return run_chunks_dev(c, n, stream, false, [&](size_t off, size_t m, hipEvent_t, hipEvent_t*, int*) {
-        return enqueue_ed_keyed(c, src + off * SBV_ED_REC_BYTES, sl + off, m, dst + off / 8, stream);
+    return run_chunks_dev(c, n, stream, T::kStageA, [&](size_t off, size_t m, hipEvent_t after_prep, hipEvent_t*, int*) {
+        return T::enqueue(c, src + off * T::kRecBytes, sl + off, m, dst + off / 8, stream, after_prep);
     });
 }
 
-extern "C" int sbv_ed25519_verify_batch_keyed(const uint8_t* rsk, const uint32_t* slots, size_t n, uint8_t* accept_bitmap) {
+template <class T>
+int local_verify_keyed(const uint8_t* recs, const uint32_t* slots, size_t n, uint8_t* accept_bitmap) {
     SBV_ENTER(c);
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (n == 0) return SBV_OK;
-    if (!rsk || !slots || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
-    if (c.ed_nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
+    if (!recs || !slots || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (T::dev(c).nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    const int rc = ensure_ed_keyed(c);
+    const int rc = T::ensure(c);
     if (rc != SBV_OK) return rc;
-    return run_chunks_host(c, n, accept_bitmap, t0, false,
+    return run_chunks_host(c, n, accept_bitmap, t0, T::kStageA,
         [&](size_t off, size_t m) {
-            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, rsk + off * SBV_ED_REC_BYTES, m * SBV_ED_REC_BYTES, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, recs + off * T::kRecBytes, m * T::kRecBytes, hipMemcpyHostToDevice, c.stream));
             HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots + off, m * sizeof(u32), hipMemcpyHostToDevice, c.stream));
             return SBV_OK;
         },
-        [&](size_t, size_t m, hipEvent_t) { return enqueue_ed_keyed(c, c.d_tuples, c.d_slots, m, c.d_bitmap, c.stream); });
+        [&](size_t, size_t m, hipEvent_t after_prep) { return T::enqueue(c, c.d_tuples, c.d_slots, m, c.d_bitmap, c.stream, after_prep); });
+}
+}  // namespace
+
+extern "C" int sbv_ed25519_register_keys(const uint8_t* pks, size_t m, uint32_t* slots_out) { return local_register_keys<EdReg>(pks, m, slots_out); }
+extern "C" int sbv_ed25519_key_count(void) { return local_key_count<EdReg>(); }
+extern "C" int sbv_ed25519_clear_keys(void) { return local_clear_keys<EdReg>(); }
+extern "C" int sbv_ed25519_wide_keys(uint32_t max_keys) { return local_wide_keys<EdReg>(max_keys); }
+extern "C" int sbv_ed25519_widen_keys(const uint32_t* slots, size_t m) { return local_widen_keys<EdReg>(slots, m); }
+extern "C" int sbv_ed25519_wide_key_stats(uint32_t out[4]) { return local_wide_key_stats<EdReg>(out); }
+extern "C" int sbv_ed25519_wide_selfcheck(uint32_t slot) { return local_wide_selfcheck<EdReg>(slot); }
+extern "C" int sbv_ed25519_verify_batch_keyed_dev(const void* d_rsk, const void* d_slots, size_t n, void* d_bitmap, void* hip_stream) {
+    return local_verify_keyed_dev<EdReg>(d_rsk, d_slots, n, d_bitmap, hip_stream);
+}
+extern "C" int sbv_ed25519_verify_batch_keyed(const uint8_t* rsk, const uint32_t* slots, size_t n, uint8_t* accept_bitmap) {
+    return local_verify_keyed<EdReg>(rsk, slots, n, accept_bitmap);
+}
+
+extern "C" int sbv_secp256k1_register_keys(const uint8_t* keys, size_t m, uint32_t* slots_out) { return local_register_keys<K256Reg>(keys, m, slots_out); }
+extern "C" int sbv_secp256k1_key_count(void) { return local_key_count<K256Reg>(); }
+extern "C" int sbv_secp256k1_clear_keys(void) { return local_clear_keys<K256Reg>(); }
+extern "C" int sbv_secp256k1_wide_keys(uint32_t max_keys) { return local_wide_keys<K256Reg>(max_keys); }
+extern "C" int sbv_secp256k1_widen_keys(const uint32_t* slots, size_t m) { return local_widen_keys<K256Reg>(slots, m); }
+extern "C" int sbv_secp256k1_wide_key_stats(uint32_t out[4]) { return local_wide_key_stats<K256Reg>(out); }
+extern "C" int sbv_secp256k1_wide_selfcheck(uint32_t slot) { return local_wide_selfcheck<K256Reg>(slot); }
+extern "C" int sbv_secp256k1_verify_batch_keyed_dev(const void* d_rsh, const void* d_slots, size_t n, void* d_bitmap, void* hip_stream) {
+    return local_verify_keyed_dev<K256Reg>(d_rsh, d_slots, n, d_bitmap, hip_stream);
+}
+extern "C" int sbv_secp256k1_verify_batch_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* accept_bitmap) {
+    return local_verify_keyed<K256Reg>(rsh, slots, n, accept_bitmap);
 }
 
 extern "C" int sbv_ed25519_verify_msgs_keyed(const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
@@ -2355,10 +2490,10 @@ extern "C" int sbv_ed25519_verify_msgs_keyed(const uint8_t* sigs, const uint8_t*
     size_t mbytes = 0;
     int rc = check_offsets(msg_offsets, n, msgs, mbytes);
     if (rc != SBV_OK) return rc;
-    if (c.ed_nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
+    if (c.edreg.nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    if ((rc = ensure_ed_keyed(c)) != SBV_OK) return rc;
+    if ((rc = EdReg::ensure(c)) != SBV_OK) return rc;
     if ((rc = grow(c.d_msgs, c.msgs_cap, mbytes + 16)) != SBV_OK) return rc;
     if ((rc = grow(c.d_sigs, c.sigs_cap, n * 64 + 16)) != SBV_OK) return rc;
     if ((rc = grow(c.d_moff, c.moff_cap, n + 1)) != SBV_OK) return rc;
@@ -2378,314 +2513,6 @@ extern "C" int sbv_ed25519_verify_msgs_keyed(const uint8_t* sigs, const uint8_t*
         });
 }
 
-// ---- registered secp256k1 keys (k256_keyed.h; include/sbv.h: sbv_secp256k1_register_keys) -------------------------------------
-// The Ed25519 registry's shape on this curve.  Process-wide on the host: the slot index (64 key bytes -> slot), every registered key,
-// its valid flag and the widening cap.  On the default context's device, per slot: the key bytes (the chain's input), the valid byte,
-// the 8-bit comb of Q (270 KiB, built on the device by the grouped step's chain / rows / fill lanes) and for widened slots a 16-bit
-// comb (35.7 MB, built on the device from the 8-bit comb).  The registry shares nothing with the P-256 registry (Context::key_index,
-// d_ktab) or with either key-table cache (grp.kc, k256pool.kc): a byte string can be a point of both curves.
-// Lock order: g_k256reg_mu -> g_mu -> Context::mu; the verify entries take the context alone and read its half.
-namespace {
-struct K256Registry {
-    std::vector<std::string> keys;                    // slot -> the 64 key bytes
-    std::unordered_map<std::string, u32> index;       // key bytes -> slot
-    std::vector<uint8_t> valid;                       // slot -> the key is a point of the curve
-    u32 wide_max = 64;                                // sbv_secp256k1_wide_keys
-} g_k256reg;
-std::mutex g_k256reg_mu;
-constexpr u32 kK256RegBuildKeys = 512;               // slots per pass of the comb builder: 78 MB of scratch while it runs
-
-sbv::K256KeyedRegistry k256_reg_view(const Context& c) {
-    sbv::K256KeyedRegistry r;
-    r.ktab = c.d_k256_ktab; r.kvalid = c.d_k256_kvalid;
-    r.wtab = c.d_k256_wtab; r.kwidx = c.k256_wide_slots.empty() ? nullptr : c.d_k256_kwidx;
-    r.nkeys = (u32)c.k256_nkeys;
-    return r;
-}
-
-// c.mu held, the device current: room for `want` slots.  Doubles from 64 slots, copies the live slots on the device; a failure leaves
-// the old arrays (and so the registry) as they were.
-int k256_reg_reserve(Context& c, size_t want) {
-    if (want <= c.k256_key_cap) return SBV_OK;
-    size_t cap = c.k256_key_cap ? c.k256_key_cap : 64;
-    while (cap < want) cap *= 2;
-    if (cap > SBV_K256_REG_MAX_KEYS) cap = SBV_K256_REG_MAX_KEYS;
-    sbv::kapt* kt = nullptr; uint8_t* kv = nullptr; uint8_t* kk = nullptr; u32* kw = nullptr;
-    auto drop = [&] { for (void* p : {(void*)kt, (void*)kv, (void*)kk, (void*)kw}) if (p) (void)hipFree(p); (void)hipGetLastError(); };
-    if (hipMalloc(&kt, cap * (size_t)SBV_K256_KEYTAB_ENTRIES * sizeof(sbv::kapt)) != hipSuccess || hipMalloc(&kv, cap) != hipSuccess ||
-        hipMalloc(&kk, cap * SBV_K256_KEY_BYTES) != hipSuccess || hipMalloc(&kw, cap * sizeof(u32)) != hipSuccess) {
-        drop();
-        g_err = "sbv_secp256k1_register_keys: no device memory for the registry";
-        return SBV_ENOMEM;
-    }
-    const size_t n = c.k256_nkeys;
-    hipError_t e = hipDeviceSynchronize();          // nothing in flight reads the old arrays any more
-    if (e == hipSuccess && n) e = hipMemcpy(kt, c.d_k256_ktab, n * (size_t)SBV_K256_KEYTAB_ENTRIES * sizeof(sbv::kapt), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess && n) e = hipMemcpy(kv, c.d_k256_kvalid, n, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess && n) e = hipMemcpy(kk, c.d_k256_kkeys, n * SBV_K256_KEY_BYTES, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess && n) e = hipMemcpy(kw, c.d_k256_kwidx, n * sizeof(u32), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);     // device-to-device copies are ordered in the null stream only (see memset_now)
-    if (e == hipSuccess) e = memset_now(kw + n, 0xFF, (cap - n) * sizeof(u32));
-    if (e != hipSuccess) { drop(); return fail(SBV_EDEVICE, "sbv_secp256k1_register_keys: growing the registry", e); }
-    for (void* p : {(void*)c.d_k256_ktab, (void*)c.d_k256_kvalid, (void*)c.d_k256_kkeys, (void*)c.d_k256_kwidx}) if (p) (void)hipFree(p);
-    c.d_k256_ktab = kt; c.d_k256_kvalid = kv; c.d_k256_kkeys = kk; c.d_k256_kwidx = kw;
-    c.k256_key_cap = cap;
-    return SBV_OK;
-}
-
-// c.mu held, the device current: room for `want` 16-bit combs (doubling, at most the cap), the combs there copied on the device
-int k256_wide_reserve(Context& c, size_t want, size_t cap_max) {
-    if (want <= c.k256_wtab_cap) return SBV_OK;
-    size_t cap = c.k256_wtab_cap ? c.k256_wtab_cap : 1;
-    while (cap < want) cap *= 2;
-    if (cap > cap_max) cap = cap_max;
-    sbv::kapt* w = nullptr;
-    if (hipMalloc(&w, cap * SBV_K256_WIDE_COMB_BYTES) != hipSuccess) {
-        (void)hipGetLastError();
-        g_err = "sbv_secp256k1_widen_keys: no device memory for the 16-bit combs";
-        return SBV_ENOMEM;
-    }
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess && !c.k256_wide_slots.empty())
-        e = hipMemcpy(w, c.d_k256_wtab, c.k256_wide_slots.size() * SBV_K256_WIDE_COMB_BYTES, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) { (void)hipFree(w); return fail(SBV_EDEVICE, "sbv_secp256k1_widen_keys: growing the comb pool", e); }
-    if (c.d_k256_wtab) (void)hipFree(c.d_k256_wtab);
-    c.d_k256_wtab = w;
-    c.k256_wtab_cap = cap;
-    return SBV_OK;
-}
-
-// one chunk (m <= c.cap) of keyed records on `stream`: stage A on the records into the scratch planes, then the keyed stage B
-int enqueue_k256_keyed(Context& c, const uint8_t* d_recs, const u32* d_slots, size_t m, uint8_t* d_bitmap, hipStream_t stream, hipEvent_t after_prep = nullptr) {
-    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_verify_keyed(d_recs, d_slots, m, scratch_view(c), k256_reg_view(c), c.d_k256_gcomb, c.k256_gbits, d_bitmap, stream, after_prep));
-    return SBV_OK;
-}
-// the table every keyed call needs: the comb of G of the grouped step (which borrows the one-lane kernel's at 16 bits)
-int ensure_k256_keyed(Context& c) {
-    const int rc = ensure_k256_table(c);
-    return rc == SBV_OK ? ensure_k256_gcomb(c) : rc;
-}
-}  // namespace
-
-static void k256_registry_forget() {
-    std::lock_guard<std::mutex> lk(g_k256reg_mu);
-    const u32 wm = g_k256reg.wide_max;
-    g_k256reg = K256Registry();
-    g_k256reg.wide_max = wm;
-}
-
-extern "C" int sbv_secp256k1_register_keys(const uint8_t* keys, size_t m, uint32_t* slots_out) {
-    std::lock_guard<std::mutex> rl(g_k256reg_mu);
-    SBV_ENTER(c);
-    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
-    if (m == 0) return SBV_OK;
-    if (!keys || !slots_out) { g_err = "null pointer"; return SBV_EINVAL; }
-    std::vector<u32> out(m);
-    std::string fresh;                              // keys that need a slot, in slot order
-    std::unordered_map<std::string, u32> pending;
-    for (size_t i = 0; i < m; ++i) {
-        const std::string k((const char*)keys + SBV_K256_KEY_BYTES * i, SBV_K256_KEY_BYTES);
-        auto it = g_k256reg.index.find(k);
-        if (it != g_k256reg.index.end()) { out[i] = it->second; continue; }
-        auto pt = pending.find(k);
-        if (pt != pending.end()) { out[i] = pt->second; continue; }
-        const u32 slot = (u32)(g_k256reg.keys.size() + pending.size());
-        pending.emplace(k, slot);
-        fresh += k;
-        out[i] = slot;
-    }
-    const size_t nf = pending.size();
-    if (g_k256reg.keys.size() + nf > SBV_K256_REG_MAX_KEYS) { g_err = "sbv_secp256k1_register_keys: more than 65536 keys"; return SBV_EINVAL; }
-    if (nf) {
-        HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-        const int rc = k256_reg_reserve(c, c.k256_nkeys + nf);
-        if (rc != SBV_OK) return rc;
-        // the new slots lie beyond k256_nkeys: no batch reads them until the count below is raised
-        const size_t s0 = c.k256_nkeys;
-        const u32 pass = nf < kK256RegBuildKeys ? (u32)nf : kK256RegBuildKeys;
-        u32* d_work = nullptr;
-        if (hipMalloc(&d_work, sbv::k256_reg_build_words(pass) * sizeof(u32)) != hipSuccess) {
-            (void)hipGetLastError();
-            g_err = "sbv_secp256k1_register_keys: no device memory for the builder";
-            return SBV_ENOMEM;
-        }
-        std::vector<uint8_t> valid(nf);
-        hipError_t e = hipMemcpy(c.d_k256_kkeys + s0 * SBV_K256_KEY_BYTES, fresh.data(), fresh.size(), hipMemcpyHostToDevice);
-        for (size_t off = 0; off < nf && e == hipSuccess; off += pass) {
-            const u32 cnt = (u32)(nf - off < pass ? nf - off : pass);
-            e = sbv::launch_k256_reg_build(c.d_k256_kkeys, (u32)(s0 + off), cnt, d_work, c.d_k256_ktab, c.d_k256_kvalid, c.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c.stream);        // the next pass reuses the scratch
-        }
-        (void)hipFree(d_work);                      // build scratch lives for the call only
-        if (e == hipSuccess) e = hipMemcpy(valid.data(), c.d_k256_kvalid + s0, nf, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return fail(SBV_EDEVICE, "sbv_secp256k1_register_keys: building the combs", e);
-        c.k256_nkeys += nf;
-        for (size_t i = 0; i < nf; ++i) {
-            const std::string k = fresh.substr(i * SBV_K256_KEY_BYTES, SBV_K256_KEY_BYTES);
-            g_k256reg.index.emplace(k, (u32)g_k256reg.keys.size());
-            g_k256reg.keys.push_back(k);
-            g_k256reg.valid.push_back(valid[i]);
-        }
-    }
-    memcpy(slots_out, out.data(), m * sizeof(u32));
-    return SBV_OK;
-}
-
-extern "C" int sbv_secp256k1_key_count(void) {
-    SBV_ENTER(c);
-    return c.ready ? (int)c.k256_nkeys : SBV_ENOTINIT;
-}
-
-extern "C" int sbv_secp256k1_clear_keys(void) {
-    std::lock_guard<std::mutex> rl(g_k256reg_mu);
-    SBV_ENTER(c);
-    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
-    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    if (c.d_k256_kwidx && c.k256_key_cap) HIP_TRY(SBV_EDEVICE, memset_now(c.d_k256_kwidx, 0xFF, c.k256_key_cap * sizeof(u32)));
-    c.k256_nkeys = 0;                // the allocations stay for the next registry
-    c.k256_wide_slots.clear();
-    const u32 wm = g_k256reg.wide_max;
-    g_k256reg = K256Registry();
-    g_k256reg.wide_max = wm;
-    return SBV_OK;
-}
-
-extern "C" int sbv_secp256k1_wide_keys(uint32_t max_keys) {
-    std::lock_guard<std::mutex> rl(g_k256reg_mu);
-    SBV_ENTER(c);
-    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
-    if (max_keys > 4096) { g_err = "sbv_secp256k1_wide_keys: at most 4096 keys"; return SBV_EINVAL; }
-    g_k256reg.wide_max = max_keys;
-    if (c.k256_wide_slots.size() <= max_keys) return SBV_OK;
-    // fewer than are wide: the first max_keys widened slots keep their combs, the others go back to their 8-bit combs
-    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    const u32 none = SBV_K256_WIDE_NONE;
-    for (size_t w = max_keys; w < c.k256_wide_slots.size(); ++w)
-        HIP_TRY(SBV_EDEVICE, hipMemcpy(c.d_k256_kwidx + c.k256_wide_slots[w], &none, sizeof(u32), hipMemcpyHostToDevice));
-    c.k256_wide_slots.resize(max_keys);
-    if (max_keys == 0 && c.d_k256_wtab) { (void)hipFree(c.d_k256_wtab); c.d_k256_wtab = nullptr; c.k256_wtab_cap = 0; }
-    return SBV_OK;
-}
-
-extern "C" int sbv_secp256k1_widen_keys(const uint32_t* slots, size_t m) {
-    std::lock_guard<std::mutex> rl(g_k256reg_mu);
-    SBV_ENTER(c);
-    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
-    if (m == 0) return SBV_OK;
-    if (!slots) { g_err = "null pointer"; return SBV_EINVAL; }
-    for (size_t i = 0; i < m; ++i)
-        if (slots[i] >= c.k256_nkeys) { g_err = "sbv_secp256k1_widen_keys: unregistered slot"; return SBV_EINVAL; }
-    // the slots that get a comb now: registered, a point, not wide yet, within the cap (the others stay narrow: no error)
-    std::vector<u32> todo;
-    for (size_t i = 0; i < m; ++i) {
-        const u32 s = slots[i];
-        if (!g_k256reg.valid[s]) continue;
-        if (std::find(c.k256_wide_slots.begin(), c.k256_wide_slots.end(), s) != c.k256_wide_slots.end()) continue;
-        if (std::find(todo.begin(), todo.end(), s) != todo.end()) continue;
-        if (c.k256_wide_slots.size() + todo.size() >= g_k256reg.wide_max) break;
-        todo.push_back(s);
-    }
-    if (todo.empty()) return SBV_OK;
-    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    const size_t w0 = c.k256_wide_slots.size();
-    const int rc = k256_wide_reserve(c, w0 + todo.size(), g_k256reg.wide_max);
-    if (rc != SBV_OK) return rc;
-    u32* d_tmp = nullptr;
-    if (hipMalloc(&d_tmp, sbv::k256_widetab_tmp_words() * sizeof(u32)) != hipSuccess) {
-        (void)hipGetLastError();
-        g_err = "sbv_secp256k1_widen_keys: no device memory for the builder";
-        return SBV_ENOMEM;
-    }
-    hipError_t e = hipSuccess;
-    if (c.busy_valid) e = hipStreamWaitEvent(c.stream, c.busy, 0);
-    for (size_t i = 0; i < todo.size() && e == hipSuccess; ++i)       // one after the other on the stream: they share the scratch
-        e = sbv::launch_k256_widetab(c.d_k256_ktab, todo[i], d_tmp, c.d_k256_wtab, (u32)(w0 + i), c.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    (void)hipFree(d_tmp);                           // build scratch lives for the call only
-    if (e != hipSuccess) return fail(SBV_EDEVICE, "sbv_secp256k1_widen_keys: building the combs", e);
-    // publish: a comb is used only once it is complete
-    for (size_t i = 0; i < todo.size(); ++i) {
-        const u32 w = (u32)(w0 + i);
-        e = hipMemcpy(c.d_k256_kwidx + todo[i], &w, sizeof(u32), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            const u32 none = SBV_K256_WIDE_NONE;
-            for (size_t j = 0; j < i; ++j) (void)hipMemcpy(c.d_k256_kwidx + todo[j], &none, sizeof(u32), hipMemcpyHostToDevice);
-            return fail(SBV_EDEVICE, "sbv_secp256k1_widen_keys: publish", e);
-        }
-    }
-    c.k256_wide_slots.insert(c.k256_wide_slots.end(), todo.begin(), todo.end());
-    return SBV_OK;
-}
-
-extern "C" int sbv_secp256k1_wide_key_stats(uint32_t out[4]) {
-    std::lock_guard<std::mutex> rl(g_k256reg_mu);
-    SBV_ENTER(c);
-    if (!c.ready) return SBV_ENOTINIT;
-    if (!out) return SBV_EINVAL;
-    out[0] = (u32)c.k256_wide_slots.size(); out[1] = SBV_K256_WIDE_BITS; out[2] = g_k256reg.wide_max;
-    out[3] = (u32)(SBV_K256_WIDE_COMB_BYTES >> 10);
-    return SBV_OK;
-}
-
-// 1 = the device-resident 16-bit comb of `slot` equals the host builder's comb of Q (k256_build_window_of) byte for byte
-extern "C" int sbv_secp256k1_wide_selfcheck(uint32_t slot) {
-    std::lock_guard<std::mutex> rl(g_k256reg_mu);
-    SBV_ENTER(c);
-    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
-    size_t w = c.k256_wide_slots.size();
-    for (size_t i = 0; i < c.k256_wide_slots.size(); ++i) if (c.k256_wide_slots[i] == slot) w = i;
-    if (w == c.k256_wide_slots.size()) { g_err = "sbv_secp256k1_wide_selfcheck: the slot has no wide comb"; return SBV_EINVAL; }
-    std::vector<sbv::kapt> want(SBV_K256_WIDE_ENTRIES), got(SBV_K256_WIDE_ENTRIES);
-    if (!sbv::host_build_k256_wide_comb((const uint8_t*)g_k256reg.keys[slot].data(), want.data())) return 0;      // only points are widened
-    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), c.d_k256_wtab + w * SBV_K256_WIDE_ENTRIES, SBV_K256_WIDE_COMB_BYTES, hipMemcpyDeviceToHost));
-    return memcmp(got.data(), want.data(), SBV_K256_WIDE_COMB_BYTES) == 0 ? 1 : 0;
-}
-
-extern "C" int sbv_secp256k1_verify_batch_keyed_dev(const void* d_rsh, const void* d_slots, size_t n, void* d_bitmap, void* hip_stream) {
-    SBV_ENTER(c);
-    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
-    if (n == 0) return SBV_OK;
-    if (!d_rsh || !d_slots || !d_bitmap || (reinterpret_cast<uintptr_t>(d_rsh) & 15)) { g_err = "null or misaligned device pointer"; return SBV_EINVAL; }
-    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (c.k256_nkeys == 0) {         // every slot is out of range: every record is a reject
-        HIP_TRY(SBV_EDEVICE, hipMemsetAsync(d_bitmap, 0, (n + 7) / 8, stream));
-        return SBV_OK;
-    }
-    const int rc = ensure_k256_keyed(c);
-    if (rc != SBV_OK) return rc;
-    const uint8_t* src = static_cast<const uint8_t*>(d_rsh);
-    const u32* sl = static_cast<const u32*>(d_slots);
-    uint8_t* dst = static_cast<uint8_t*>(d_bitmap);
-    return run_chunks_dev(c, n, stream, true, [&](size_t off, size_t m, hipEvent_t after_prep, hipEvent_t*, int*) {
-        return enqueue_k256_keyed(c, src + off * SBV_K256_REC_BYTES, sl + off, m, dst + off / 8, stream, after_prep);
-    });
-}
-
-extern "C" int sbv_secp256k1_verify_batch_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* accept_bitmap) {
-    SBV_ENTER(c);
-    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
-    if (n == 0) return SBV_OK;
-    if (!rsh || !slots || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
-    if (c.k256_nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    const int rc = ensure_k256_keyed(c);
-    if (rc != SBV_OK) return rc;
-    return run_chunks_host(c, n, accept_bitmap, t0, true,
-        [&](size_t off, size_t m) {
-            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_tuples, rsh + off * SBV_K256_REC_BYTES, m * SBV_K256_REC_BYTES, hipMemcpyHostToDevice, c.stream));
-            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_slots, slots + off, m * sizeof(u32), hipMemcpyHostToDevice, c.stream));
-            return SBV_OK;
-        },
-        [&](size_t, size_t m, hipEvent_t after_prep) { return enqueue_k256_keyed(c, c.d_tuples, c.d_slots, m, c.d_bitmap, c.stream, after_prep); });
-}
-
 // the message front end (SHA-256 + strict DER -> r | s | hash records, curve-agnostic) in front of the keyed step
 extern "C" int sbv_secp256k1_verify_msgs_keyed(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs,
                                                const uint64_t* sig_offsets, const uint32_t* slots, size_t n, uint8_t* accept_bitmap) {
@@ -2698,10 +2525,10 @@ extern "C" int sbv_secp256k1_verify_msgs_keyed(const uint8_t* msgs, const uint64
     int rc = check_offsets(msg_offsets, n, msgs, mbytes);
     if (rc == SBV_OK) rc = check_offsets(sig_offsets, n, sigs, sbytes);
     if (rc != SBV_OK) return rc;
-    if (c.k256_nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
+    if (c.k256reg.nkeys == 0) { memset(accept_bitmap, 0, (n + 7) / 8); return SBV_OK; }
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    if ((rc = ensure_k256_keyed(c)) != SBV_OK) return rc;
+    if ((rc = K256Reg::ensure(c)) != SBV_OK) return rc;
     if ((rc = grow(c.d_msgs, c.msgs_cap, mbytes + 16)) != SBV_OK) return rc;
     if ((rc = grow(c.d_sigs, c.sigs_cap, sbytes + 16)) != SBV_OK) return rc;
     if ((rc = grow(c.d_moff, c.moff_cap, n + 1)) != SBV_OK) return rc;
