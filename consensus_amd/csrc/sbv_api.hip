@@ -951,7 +951,7 @@ extern "C" int sbv_device_count(void) {
 namespace {
 // The G combs are the same for every device: built once per process on the host, uploaded to each device.
 std::vector<sbv::apt> g_h_gtab, g_h_g16r;
-int g_gbits = 20;                     // window width of the carry-free kernels' comb of G (SBV_G_BITS: 12..22)
+int g_gbits = 20;                     // window width of the carry-free kernels' comb of G (SBV_G_BITS: 12..22); tests/scalar_cases.py reads this line
 std::once_flag g_tables_once;
 void build_host_tables() {
     if (const char* e = getenv("SBV_G_BITS")) { const int v = atoi(e); if (v >= 12 && v <= 22) g_gbits = v; }
@@ -1791,7 +1791,7 @@ extern "C" int sbv_p256_verify_batch_keyed(const uint8_t* rsh, const uint32_t* s
 namespace {
 std::vector<sbv::aniels> g_h_ed_b16, g_h_ed_bcomb;     // built once per process, uploaded to each context on its first Ed25519 call
 std::once_flag g_ed_b16_once, g_ed_bcomb_once;
-int g_ed_bbits = 20;
+int g_ed_bbits = 20;                  // tests/scalar_cases.py reads this line
 int ensure_ed_table(Context& c) {
     if (c.d_btab) return SBV_OK;
     std::call_once(g_ed_b16_once, [] {
@@ -1862,7 +1862,7 @@ namespace {
 std::vector<sbv::kapt> g_h_k256_gtab;           // built once per process, uploaded to each context on its first secp256k1 call
 std::once_flag g_k256_once;
 std::vector<sbv::kapt> g_h_k256_gcomb;          // the grouped step's comb, built once per process
-int g_k256_gbits = 20;
+int g_k256_gbits = 20;                // tests/scalar_cases.py reads this line
 std::once_flag g_k256_gcomb_once;
 int ensure_k256_gcomb(Context& c) {
     if (c.d_k256_gcomb) return SBV_OK;

@@ -365,8 +365,13 @@ def test_registered_key_full_batch_2_20(gpu):
 
 
 def test_exact_pass_forced(golden_vectors):
-    """Experimental two-launch stage B (SBV_STAGEB_FAST=1): fast kernel, then the exact kernel on flagged
-    wavefronts; SBV_FORCE_EXACT=1 flags all of them.  Verdicts must equal the default single-launch mode."""
+    """A fresh process verifies the golden tuple vectors, a seeded batch of 5000 through the generic entry and the same batch through
+    the registered-key entry.  The process environment carries SBV_STAGEB_FAST=1 and SBV_FORCE_EXACT=1: they once selected an
+    experimental two-launch stage B (a fast kernel, then the exact kernel on flagged wavefronts); nothing in the library reads them
+    any more, every addition of the one stage B there is is exact, and the variables only show that unknown settings are ignored.
+    What the exact pass existed for — an accumulator that equals + or - the entry about to be added, in the middle of a walk — is
+    held by the mid-walk cases of tests/scalar_cases.py, here through the same two entries and in tests/test_gpu_scalar_walks.py
+    through every path."""
     import subprocess
     import sys
     code = r'''
@@ -384,6 +389,17 @@ keys = sorted(set(bytes(t[i * 160 + 96:i * 160 + 160]) for i in range(5000)))
 reg = dict(zip(keys, sbv.register_keys(keys)))
 rsh = b"".join(bytes(t[i * 160:i * 160 + 96]) for i in range(5000))
 assert sbv.verify_batch_keyed(rsh, [reg[bytes(t[i * 160 + 96:i * 160 + 160])] for i in range(5000)], 5000) == valid.tobytes()
+sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
+import scalar_cases as sc
+mid = [c for c in sc.cases("p256") if c.family == "collision"]
+want = [c.expect for c in mid]
+assert len(mid) >= 100 and sum(c.designed_reject for c in mid) >= 8
+got = sbv.bitmap_to_list(sbv.verify_batch(sc.blob(mid), len(mid)), len(mid))
+assert got == want, [(c.walker, c.name) for c, g in zip(mid, got) if g != c.expect]
+recs, slots, mkeys = sc.split_keyed("p256", sc.blob(mid))
+mreg = sbv.register_keys(mkeys)
+got = sbv.bitmap_to_list(sbv.verify_batch_keyed(recs, [mreg[s] for s in slots], len(mid)), len(mid))
+assert got == want, [(c.walker, c.name) for c, g in zip(mid, got) if g != c.expect]
 print("forced-exact ok")
 '''
     env = dict(os.environ, SBV_FORCE_EXACT="1", SBV_STAGEB_FAST="1")
