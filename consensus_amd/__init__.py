@@ -697,6 +697,63 @@ def debug_hot_check(device: int = 0):
     return tuple(out)
 
 
+GROUP_ARRAYS = ("ht", "rep", "cnt", "slot_of", "group_rep", "counters", "slots", "grp_idx", "grp_of", "ung_idx", "ung_cand", "gcount", "gcursor",
+                "tslot", "cold", "acc", "cache_keys", "cache_count")       # SBV_GROUP_ARRAY_* of include/sbv.h, in order
+GROUP_HEADER = ("scheme", "n", "ht_mask", "max_groups", "min_count", "sample_mask", "min_samples", "seed", "sorted", "kc_cap", "kc_enabled", "serial",
+                "groups", "cached")
+
+
+def debug_group_header(device: int = 0):
+    """sbv_debug_group_header: the 16 header words of the last grouped launch of context `device` (word 0 = 0xFFFFFFFF: none yet;
+    word 11 = the serial number of grouped launches)."""
+    out = (ctypes.c_uint32 * 16)()
+    _check(_call("sbv_debug_group_header", [ctypes.c_int, _PTR], device, out))
+    return tuple(out)
+
+
+def group_readout_from(header, array):
+    """The read-out dict of a grouped step from a pair of entries shaped like sbv_debug_group_header / sbv_debug_group_array
+    (header() -> 16 words, array(which, count, address) -> 0): the header fields by name and one numpy array per GROUP_ARRAYS name, each
+    cut to the length the counters give it.  None before the first grouped launch.  (The test emulator exports the same pair.)"""
+    import numpy as np
+    h = header()
+    if h[0] == 0xFFFFFFFF:
+        return None
+    ro = {name: int(h[i]) for i, name in enumerate(GROUP_HEADER)}
+
+    def get(name, count, dtype=np.uint32):
+        out = np.zeros(max(int(count), 1), dtype=dtype)
+        rc = array(GROUP_ARRAYS.index(name), int(count), out.ctypes.data)
+        if rc != SBV_OK:
+            raise SbvError(rc, f"group read-out of {name}[{count}]")
+        return out[:int(count)]
+
+    n, groups, srt = ro["n"], ro["groups"], ro["sorted"]
+    c = ro["counters"] = get("counters", 12)
+    ro["ht"] = get("ht", ro["ht_mask"] + 1)
+    for name in ("rep", "cnt", "slot_of", "slots"):
+        ro[name] = get(name, n)
+    ro["acc"] = get("acc", n, np.uint8)
+    ro["group_rep"], ro["tslot"], ro["cold"] = get("group_rep", groups), get("tslot", groups), get("cold", groups, np.uint8)
+    ro["grp_idx"] = get("grp_idx", min(int(c[1]), n))
+    ro["ung_idx"] = get("ung_idx", min(int(c[2]), n))
+    ro["grp_of"] = get("grp_of", min(int(c[1]), n) if srt else 0)
+    ro["ung_cand"] = get("ung_cand", min(int(c[4]), n) if srt else 0)
+    ro["gcount"], ro["gcursor"] = get("gcount", groups if srt else 0), get("gcursor", groups if srt else 0)
+    ro["cache_count"] = get("cache_count", 4)
+    ro["cache_keys"] = get("cache_keys", min(int(ro["cache_count"][0]), ro["kc_cap"]) * 16).reshape(-1, 16)
+    return ro
+
+
+def debug_group_readout(device: int = 0):
+    """sbv_debug_group_header + sbv_debug_group_array: what the LAST grouped launch of any scheme left in context `device` — the grouping
+    table, representatives, counts, lists, sort cursors, table slots, verdict bytes and the scheme's cached keys — as a dict of header
+    fields and numpy arrays (group_readout_from).  Tests and tools only: it waits for the device and copies every array."""
+    load()
+    return group_readout_from(lambda: debug_group_header(device),
+                              lambda which, count, addr: _call("sbv_debug_group_array", [ctypes.c_int, ctypes.c_int, ctypes.c_size_t, _PTR], device, which, count, addr))
+
+
 def hot_keys(max_keys: int = 1024, min_hits: int = 0) -> None:
     """sbv_p256_hot_keys: wide combs for hot cache slots of the generic path (0 keys = off)."""
     lib = load()

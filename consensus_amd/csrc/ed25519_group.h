@@ -46,6 +46,7 @@ SBV_HD bool ed_tuple_key_load(const uint8_t* tuples, size_t idx, ept& A) {
 SBV_HD bool ed_group_split_lane(size_t i, const GroupState& g) {
     const u32 s = g.slot_of[g.rep[i]];
     if (s == SBV_GROUP_NONE) {
+        g.slots[i] = SBV_GROUP_NONE;                         // as the kernel's compaction does (group_split_emit)
         g.ung_idx[SBV_ATOMIC_ADD(&g.counters[2], 1u)] = (u32)i;
     } else {
         g.slots[i] = s;

@@ -252,7 +252,7 @@ hipError_t launch_ed25519_verify_grouped(const uint8_t* d_tuples, size_t n, cons
     // key-sorted grouped list (p256_group.h): the Q phase walks runs of equal keys; the accumulator is tuple-major so that the
     // G phase can still start at once, in tuple order
     const size_t sort_lds = (size_t)b.max_groups * sizeof(u32);
-    g.sorted = y.sorted && b.gcount && b.grp_of && sort_lds <= 64 * 1024 ? 1u : 0u;
+    g.sorted = ed25519_group_step_sorted(y, b) ? 1u : 0u;
     group_set_threshold(g, b.min_count);
     // 2 chunks (the context's setting) also after the finish left the Q phase: 3 / 4 chunks 4.41-4.51 / 4.36-4.45 ms against 4.19-4.33 per cold 2^20
     // step, 3.33-3.35 / 3.38-3.42 against 3.20-3.23 warm (profiles/r04/ab_ed_chunks_r04o.jsonl)

@@ -228,7 +228,7 @@ __device__ __forceinline__ u32 group_compact_pos(bool mine, u32* counter) {
     return base + (u32)__popcll(m & ((1ull << lane) - 1ull));
 }
 // key-sorted step, pass 1 (group_classify_lane): the group of every tuple; ungrouped tuples become candidates
-// (P-256: list = ung_cand, counter = counters[4]; Ed25519 has no key check in front of the one-lane kernel: ung_idx, counters[2])
+// (every scheme: list = ung_cand, counter = counters[4]; the scheme's own key check — k_group_keycheck, k_k256_keycheck, k_ed_keycheck — turns them into ung_idx)
 static __global__ __launch_bounds__(256) void k_group_classify(size_t n, GroupState g, u32* __restrict__ list, u32* __restrict__ counter) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const bool active = i < n;

@@ -581,7 +581,7 @@ hipError_t launch_p256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
     // key-sorted grouped list: needs the per-tuple records of stage A; one LDS word per group while the histogram fits (<= 16 384
     // groups), plain global atomics beyond (the kernels decide: group_kernels_common.h)
     const size_t sort_lds = (size_t)(b.max_groups > SBV_SORT_LDS_GROUPS ? SBV_SORT_LDS_GROUPS : b.max_groups) * sizeof(u32);
-    g.sorted = y.sorted && s_in.rec && b.gcount && b.grp_of && b.ung_cand ? 1u : 0u;
+    g.sorted = p256_group_step_sorted(y, s_in, b) ? 1u : 0u;
     // Stage A writes EITHER the per-tuple records (key-sorted step: every reader takes them) OR the limb-major planes
     Scratch s = s_in;
     if (!g.sorted) s.rec = nullptr;

@@ -117,6 +117,12 @@ struct GroupSync {
     size_t coop_max = (size_t)1 << 15;     // P-256: batches up to this size finish in ONE launch of 8 lanes per grouped tuple (k_group_coop; SBV_GROUP_COOP_MAX, 0 = off).  Measured in round 4 (profiles/r04/ab_coop_r04a.jsonl): warm 2^10 0.30 -> 0.19 ms, 2^12 0.34 -> 0.22, 2^14 0.37 -> 0.27, 2^15 0.39 -> 0.33
     size_t gsplit_min = (size_t)1 << 19;   // P-256: batches from this size run the G phase as its own 3-waves-per-SIMD kernel (SBV_GPHASE_SPLIT_MIN; 0 = never)
 };
+// Whether a scheme's grouped launcher builds the key-sorted list (GroupState::sorted) for these buffers: ONE rule per scheme, used by the
+// launcher itself and by whoever reports what it did (sbv_api.hip: sbv_debug_group_header).  P-256 needs stage A's per-tuple records and
+// the sort's arrays; Ed25519 one LDS word per group within 64 KiB; secp256k1 has the sorted form only.
+inline bool p256_group_step_sorted(const GroupSync& y, const Scratch& s, const GroupBuffers& b) { return y.sorted && s.rec && b.gcount && b.grp_of && b.ung_cand; }
+inline bool ed25519_group_step_sorted(const GroupSync& y, const GroupBuffers& b) { return y.sorted && b.gcount && b.grp_of && (size_t)b.max_groups * sizeof(u32) <= 64 * 1024; }
+inline bool k256_group_step_sorted(const GroupSync&, const GroupBuffers&) { return true; }
 // Enqueues stage A AND stage B of a grouped batch.  ev_fork must have been recorded on `stream` first.  after_prep
 // (optional) is recorded on `stream` once stage A is ordered before it.  prof (optional): 2 * chunks
 // events, a pair around every Q-phase launch; *prof_pairs = the number of pairs used.

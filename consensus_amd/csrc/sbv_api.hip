@@ -94,6 +94,8 @@ struct Context {
     // in-step key grouping (p256_group.h)
     sbv::GroupBuffers grp;
     sbv::EdGroupBuffers edgrp;          // Ed25519 grouped step: per-batch combs of -A (the rest is shared with grp)
+    // host-side scalars of the last grouped launch's GroupState, for sbv_debug_group_header / _array (tests and tools)
+    struct LastGroup { int scheme = -1; size_t n = 0; u32 ht_mask = 0, max_groups = 0, min_count = 0, sample_mask = 0, min_samples = 0, seed = 0, sorted = 0, serial = 0; } last_group;
     bool group_enabled = true;
     // Batches from this size on take the grouped step.  With the key-table cache ON (the default) that is nearly every batch:
     // cached keys are grouped whatever their count (p256_group.h: group_assign_lane), so a warm batch of a few thousand
@@ -607,6 +609,18 @@ sbv::GroupBuffers variant_view(const Context& c, size_t n) {
     return bv;
 }
 
+// Remembers what the grouped launch of `scheme` over n tuples is about to see (b: c.grp or its variant_view; sorted: as the scheme's
+// launcher decides it) — the read-out of sbv_debug_group_header.  Called when the step is enqueued.
+void note_grouped_launch(Context& c, int scheme, size_t n, const sbv::GroupBuffers& b, bool sorted) {
+    sbv::GroupState g{};
+    if (b.sample_shift >= 0) sbv::group_set_sampling(g, b.min_count, (u32)b.sample_shift);
+    else sbv::group_set_threshold(g, b.min_count);
+    Context::LastGroup& l = c.last_group;
+    l.scheme = scheme; l.n = n; l.ht_mask = b.ht_mask; l.seed = b.seed; l.max_groups = b.max_groups; l.min_count = g.min_count; l.sample_mask = g.sample_mask; l.min_samples = g.min_samples;
+    l.sorted = sorted ? 1u : 0u;
+    ++l.serial;
+}
+
 int ensure_ed_group_buffers(Context& c, size_t n) {
     int rc = ensure_group_buffers(c, n);
     if (rc != SBV_OK) return rc;
@@ -719,7 +733,9 @@ int enqueue_ed25519(Context& c, const uint8_t* d_tuples, size_t n, uint8_t* d_bi
     if (grouped) {
         HIP_TRY(SBV_EDEVICE, hipEventRecord(c.gsync.ev_fork, stream));
         if (c.edgrp.wtab && c.edgrp.kc.enabled) ++c.edgrp.hot_tick;     // the clock of the hot keys' decay
-        const hipError_t ge = sbv::launch_ed25519_verify_grouped(d_tuples, n, variant_view(c, n), c.edgrp, c.d_qtab, c.d_btab, sbv::edcomb_make(c.d_ed_bcomb, c.ed_bbits, c.ed_bpitch), d_bitmap, stream, c.gsync, dom, dom_pairs);
+        const sbv::GroupBuffers bv = variant_view(c, n);
+        note_grouped_launch(c, SBV_SCHEME_ED25519, n, bv, sbv::ed25519_group_step_sorted(c.gsync, bv));
+        const hipError_t ge = sbv::launch_ed25519_verify_grouped(d_tuples, n, bv, c.edgrp, c.d_qtab, c.d_btab, sbv::edcomb_make(c.d_ed_bcomb, c.ed_bbits, c.ed_bpitch), d_bitmap, stream, c.gsync, dom, dom_pairs);
         if (ge != hipSuccess) {          // a slot is published before its tables are built (see enqueue()): forget the cache
             (void)hipDeviceSynchronize();
             (void)key_cache_forget(c.edgrp.kc);
@@ -761,6 +777,7 @@ int enqueue(Context& c, const uint8_t* d_tuples, size_t n, uint8_t* d_bitmap, hi
         if (y.tstreams > 1 && stream != c.stream) y.side_t = c.stream;
         else y.tstreams = 1;
         if (c.grp.wtab && c.grp.kc.enabled) ++c.grp.hot_tick;           // the clock of the hot keys' decay (p256_group.h)
+        note_grouped_launch(c, SBV_SCHEME_P256, n, c.grp, sbv::p256_group_step_sorted(y, sg, c.grp));
         const hipError_t ge = sbv::launch_p256_verify_grouped(d_tuples, sg, n, c.grp, c.d_qtab, c.d_gtab, sbv::gcomb_make(c.d_g16r, c.g_bits), d_bitmap, stream, y,
                                                               after_prep, dom, dom_pairs);
         if (ge != hipSuccess) {
@@ -1901,7 +1918,9 @@ int enqueue_k256(Context& c, const uint8_t* d_tuples, size_t m, uint8_t* d_bitma
         sbv::GroupSync y = c.gsync;                 // second table stream: the context's own, when the caller's runs the step (enqueue() says why)
         if (y.tstreams > 1 && stream != c.stream) y.side_t = c.stream;
         else y.tstreams = 1;
-        const hipError_t ge = sbv::launch_k256_verify_grouped(d_tuples, s, m, variant_view(c, m), c.k256pool, c.d_qtab, c.d_k256_gtab, c.d_k256_gcomb, c.k256_gbits, d_bitmap, stream, y, dom, dom_pairs);
+        const sbv::GroupBuffers bv = variant_view(c, m);
+        note_grouped_launch(c, SBV_SCHEME_SECP256K1, m, bv, sbv::k256_group_step_sorted(y, bv));
+        const hipError_t ge = sbv::launch_k256_verify_grouped(d_tuples, s, m, bv, c.k256pool, c.d_qtab, c.d_k256_gtab, c.d_k256_gcomb, c.k256_gbits, d_bitmap, stream, y, dom, dom_pairs);
         if (ge != hipSuccess) {
             (void)hipDeviceSynchronize();
             (void)key_cache_forget(c.k256pool.kc);
@@ -2931,6 +2950,80 @@ extern "C" int sbv_debug_hot_check(int device, uint32_t out[8]) {
             if (memcmp(&got[e], &want[e], sizeof(sbv::apt)) != 0) { if (!bad) first = e; ++bad; }
         if (bad) { if (!out[1]) { out[2] = w; out[3] = (u32)first; out[4] = (u32)bad; } ++out[1]; }
     }
+    return SBV_OK;
+}
+
+// Diagnostics: the grouping state the LAST grouped launch of any scheme left in context `device` (p256_group.h: GroupState; the lists,
+// counters and cache slots no verdict shows).  Both entries take the context's lock, wait for the device and copy; they launch nothing.
+// out: [0] scheme (SBV_SCHEME_*; 0xFFFFFFFF = no grouped launch yet), [1] n, [2] ht_mask, [3] max_groups, [4] min_count, [5] sample_mask,
+// [6] min_samples, [7] seed, [8] sorted — as that launch's GroupState had them (the Ed25519 / secp256k1 steps: their view's capacity and
+// threshold) —, [9] kc.cap and [10] kc.enabled of the scheme's key-table cache, [11] serial number (grows by one per grouped launch),
+// [12] groups = min(counters[0], max_groups), [13] cached keys = min(count[0], kc.cap), [14], [15] reserved (0).
+extern "C" int sbv_debug_group_header(int device, uint32_t out[16]) {
+    Context* cp;
+    { std::lock_guard<std::mutex> lk(g_mu); cp = context_of(device, false); }
+    if (!cp || !out) return SBV_EINVAL;
+    std::lock_guard<std::mutex> lkc(cp->mu);
+    Context& c = *cp;
+    if (!c.ready) return SBV_ENOTINIT;
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    const Context::LastGroup& l = c.last_group;
+    out[0] = (u32)l.scheme;
+    out[11] = l.serial;
+    if (l.scheme < 0 || !c.grp.counters) { out[0] = 0xFFFFFFFFu; return SBV_OK; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+    const sbv::KeyCache& kc = *scheme_cache(c, l.scheme);
+    u32 groups = 0, cached = 0;
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(&groups, c.grp.counters, sizeof groups, hipMemcpyDeviceToHost));
+    if (kc.count) HIP_TRY(SBV_EDEVICE, hipMemcpy(&cached, kc.count, sizeof cached, hipMemcpyDeviceToHost));
+    out[1] = (u32)l.n; out[2] = l.ht_mask; out[3] = l.max_groups; out[4] = l.min_count; out[5] = l.sample_mask; out[6] = l.min_samples;
+    out[7] = l.seed; out[8] = l.sorted; out[9] = kc.cap; out[10] = kc.enabled;
+    out[12] = groups < l.max_groups ? groups : l.max_groups;
+    out[13] = cached < kc.cap ? cached : kc.cap;
+    return SBV_OK;
+}
+// Elements [0, count) of array `which` (SBV_GROUP_ARRAY_*, include/sbv.h) of that state into `out`; SBV_EINVAL when the array does not exist
+// or holds fewer than `count` elements (n per tuple, max_groups per group, ht_mask + 1, kc.cap x 16 key words, ...).
+extern "C" int sbv_debug_group_array(int device, int which, size_t count, void* out) {
+    Context* cp;
+    { std::lock_guard<std::mutex> lk(g_mu); cp = context_of(device, false); }
+    if (!cp || (!out && count)) return SBV_EINVAL;
+    std::lock_guard<std::mutex> lkc(cp->mu);
+    Context& c = *cp;
+    if (!c.ready) return SBV_ENOTINIT;
+    const Context::LastGroup& l = c.last_group;
+    if (l.scheme < 0 || !c.grp.counters) return SBV_EINVAL;
+    const sbv::GroupBuffers& b = c.grp;
+    const sbv::KeyCache& kc = *scheme_cache(c, l.scheme);
+    const size_t n = l.n, G = l.max_groups;
+    const void* src = nullptr;
+    size_t have = 0, elem = sizeof(u32);
+    switch (which) {
+        case SBV_GROUP_ARRAY_HT: src = b.ht; have = (size_t)(l.ht_mask < b.ht_mask ? l.ht_mask : b.ht_mask) + 1; break;
+        case SBV_GROUP_ARRAY_REP: src = b.rep; have = n; break;
+        case SBV_GROUP_ARRAY_CNT: src = b.cnt; have = n; break;
+        case SBV_GROUP_ARRAY_SLOT_OF: src = b.slot_of; have = n; break;
+        case SBV_GROUP_ARRAY_GROUP_REP: src = b.group_rep; have = G; break;
+        case SBV_GROUP_ARRAY_COUNTERS: src = b.counters; have = SBV_GROUP_COUNTERS; break;
+        case SBV_GROUP_ARRAY_SLOTS: src = b.slots; have = n; break;
+        case SBV_GROUP_ARRAY_GRP_IDX: src = b.grp_idx; have = n; break;
+        case SBV_GROUP_ARRAY_GRP_OF: src = b.grp_of; have = n; break;
+        case SBV_GROUP_ARRAY_UNG_IDX: src = b.ung_idx; have = n; break;
+        case SBV_GROUP_ARRAY_UNG_CAND: src = b.ung_cand; have = n; break;
+        case SBV_GROUP_ARRAY_GCOUNT: src = b.gcount; have = G; break;
+        case SBV_GROUP_ARRAY_GCURSOR: src = b.gcount ? b.gcount + G : nullptr; have = G; break;      // as every launcher lays it out, behind ITS max_groups counts
+        case SBV_GROUP_ARRAY_TSLOT: src = b.tslot; have = G; break;
+        case SBV_GROUP_ARRAY_COLD: src = b.cold; have = G; elem = 1; break;
+        case SBV_GROUP_ARRAY_ACC: src = b.acc; have = n; elem = 1; break;
+        case SBV_GROUP_ARRAY_CACHE_KEYS: src = kc.keys; have = (size_t)kc.cap * 16; break;
+        case SBV_GROUP_ARRAY_CACHE_COUNT: src = kc.count; have = 4; break;
+        default: return SBV_EINVAL;
+    }
+    if (!src || count > have) return SBV_EINVAL;
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+    if (count) HIP_TRY(SBV_EDEVICE, hipMemcpy(out, src, count * elem, hipMemcpyDeviceToHost));
     return SBV_OK;
 }
 

@@ -342,6 +342,34 @@ int sbv_p256_pool_stats(uint32_t out[6]);
  * pool's bookkeeping.  out[0] promoted slots, [1] combs that differ, [2] the first such comb, [3] its first differing entry, [4] how many of
  * its entries differ, [5] index / owner inconsistencies, [6] combs claimed by more than one slot, [7] combs handed out so far.  Slow. */
 int sbv_debug_hot_check(int device, uint32_t out[8]);
+/* Diagnostics (tests / tools): the key-grouping state that the LAST grouped launch of any scheme left in context `device` — the hash
+ * table, representatives, counts, group lists, sort cursors and key-cache slots that no verdict shows.  Both calls wait for the device and
+ * copy; they launch nothing.  sbv_debug_group_header: out[0] scheme (SBV_SCHEME_*; 0xFFFFFFFF before the first grouped launch), [1] n of
+ * that launch, [2] ht_mask, [3] max_groups, [4] min_count, [5] sample_mask, [6] min_samples, [7] the grouping hash's seed, [8] sorted — as
+ * the launch saw them —, [9] capacity and [10] on / off of the scheme's key-table cache, [11] a serial number that grows by one per grouped
+ * launch, [12] groups of the batch, [13] cached keys, [14..15] 0.  sbv_debug_group_array copies elements [0, count) of one array
+ * (u32 each; COLD and ACC: bytes) and answers SBV_EINVAL beyond its length: n for the per-tuple arrays, max_groups for the per-group
+ * ones, ht_mask + 1, 12 counters, capacity x 16 key words, 4 cache counters. */
+#define SBV_GROUP_ARRAY_HT 0
+#define SBV_GROUP_ARRAY_REP 1
+#define SBV_GROUP_ARRAY_CNT 2
+#define SBV_GROUP_ARRAY_SLOT_OF 3
+#define SBV_GROUP_ARRAY_GROUP_REP 4
+#define SBV_GROUP_ARRAY_COUNTERS 5
+#define SBV_GROUP_ARRAY_SLOTS 6
+#define SBV_GROUP_ARRAY_GRP_IDX 7
+#define SBV_GROUP_ARRAY_GRP_OF 8
+#define SBV_GROUP_ARRAY_UNG_IDX 9
+#define SBV_GROUP_ARRAY_UNG_CAND 10
+#define SBV_GROUP_ARRAY_GCOUNT 11
+#define SBV_GROUP_ARRAY_GCURSOR 12
+#define SBV_GROUP_ARRAY_TSLOT 13
+#define SBV_GROUP_ARRAY_COLD 14
+#define SBV_GROUP_ARRAY_ACC 15
+#define SBV_GROUP_ARRAY_CACHE_KEYS 16
+#define SBV_GROUP_ARRAY_CACHE_COUNT 17
+int sbv_debug_group_header(int device, uint32_t out[16]);
+int sbv_debug_group_array(int device, int which, size_t count, void* out);
 /* Hot keys (round 5): wide combs in the GENERIC path.  A key that arrives inside tuples — a client key of VerifyProposal
  * (internal/bft/view.go:553-559), a consenter of a replica that registered nothing — and keeps being hit is promoted: once the
  * key-table cache has verified `min_hits` tuples against its slot, a 16-bit comb (35.7 MB; up to `max_keys` of them, default 1024 =

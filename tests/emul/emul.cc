@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/sbv.h"
 #include "../../consensus_amd/csrc/p256_core.h"
 #include "p256_legacy_m32.h"
 #include "../../consensus_amd/csrc/ed25519_core.h"
@@ -282,6 +283,39 @@ static void emul_window_fill(bool top, u32* tmp, apt* row);
 static bool g_fill_shared = true;       // SBV_FILL_SHARED: one inversion per window in the fill (k_keytab29_fill_shared)
 void sbve_set_fill_shared(int on) { g_fill_shared = on != 0; }
 void sbve_set_group_coop(int on) { g_group_coop = on != 0; }     // k_group_coop instead of the G phase + Q launches (key-sorted step only)
+// ---- read-out of the last emulated grouped step: the twin of sbv_debug_group_header / sbv_debug_group_array (include/sbv.h), so that
+// tests/group_model.py checks what the lane functions leave behind with the same code that checks the kernels' output.  The verdict
+// bytes are the emulated bitmap's bits (the emulator packs its verdicts directly).
+static u32 g_ro_header[16] = {0xFFFFFFFFu};
+static std::vector<u32> g_ro_words[18];
+static std::vector<uint8_t> g_ro_bytes[18];
+static void emul_note_readout(int scheme, size_t n, const GroupState& g, const KeyCache& kc, const u32* tslot, const uint8_t* cold, const uint8_t* bitmap) {
+    const u32 serial = g_ro_header[0] == 0xFFFFFFFFu ? 0 : g_ro_header[11];
+    const u32 groups = g.counters[0] < g.max_groups ? g.counters[0] : g.max_groups;
+    const u32 cached = kc.count ? (kc.count[0] < kc.cap ? kc.count[0] : kc.cap) : 0;
+    const u32 h[16] = {(u32)scheme, (u32)n, g.ht_mask, g.max_groups, g.min_count, g.sample_mask, g.min_samples, g.seed, g.sorted, kc.cap, kc.enabled, serial + 1, groups, cached, 0, 0};
+    memcpy(g_ro_header, h, sizeof h);
+    auto put = [](int which, const u32* p, size_t count) { g_ro_words[which].assign(p, p + (p ? count : 0)); };
+    put(SBV_GROUP_ARRAY_HT, g.ht, (size_t)g.ht_mask + 1);
+    put(SBV_GROUP_ARRAY_REP, g.rep, n); put(SBV_GROUP_ARRAY_CNT, g.cnt, n); put(SBV_GROUP_ARRAY_SLOT_OF, g.slot_of, n); put(SBV_GROUP_ARRAY_SLOTS, g.slots, n);
+    put(SBV_GROUP_ARRAY_GROUP_REP, g.group_rep, groups); put(SBV_GROUP_ARRAY_COUNTERS, g.counters, SBV_GROUP_COUNTERS);
+    put(SBV_GROUP_ARRAY_GRP_IDX, g.grp_idx, n); put(SBV_GROUP_ARRAY_GRP_OF, g.grp_of, n); put(SBV_GROUP_ARRAY_UNG_IDX, g.ung_idx, n); put(SBV_GROUP_ARRAY_UNG_CAND, g.ung_cand, n);
+    put(SBV_GROUP_ARRAY_GCOUNT, g.gcount, groups); put(SBV_GROUP_ARRAY_GCURSOR, g.gcursor, groups); put(SBV_GROUP_ARRAY_TSLOT, tslot, groups);
+    put(SBV_GROUP_ARRAY_CACHE_KEYS, kc.keys, (size_t)cached * 16);
+    const u32 zero4[4] = {0, 0, 0, 0};
+    put(SBV_GROUP_ARRAY_CACHE_COUNT, kc.count ? kc.count : zero4, 4);
+    g_ro_bytes[SBV_GROUP_ARRAY_COLD].assign(cold, cold + groups);
+    g_ro_bytes[SBV_GROUP_ARRAY_ACC].resize(n);
+    for (size_t i = 0; i < n; ++i) g_ro_bytes[SBV_GROUP_ARRAY_ACC][i] = (bitmap[i >> 3] >> (i & 7)) & 1;
+}
+void sbve_group_readout_header(u32 out[16]) { memcpy(out, g_ro_header, sizeof g_ro_header); }
+int sbve_group_readout_array(int which, size_t count, void* out) {
+    if (which < 0 || which >= 18 || g_ro_header[0] == 0xFFFFFFFFu) return -2;
+    const bool bytes = which == SBV_GROUP_ARRAY_COLD || which == SBV_GROUP_ARRAY_ACC;
+    if (count > (bytes ? g_ro_bytes[which].size() : g_ro_words[which].size())) return -2;
+    if (count) memcpy(out, bytes ? (const void*)g_ro_bytes[which].data() : (const void*)g_ro_words[which].data(), count * (bytes ? 1 : 4));
+    return 0;
+}
 // grouped form: generic tuples, keys grouped inside the call (p256_group.h), emulated sequentially.
 // stats_out[0..3] = groups, grouped tuples, ungrouped tuples, ungrouped tuples rejected for their key.
 void sbve_p256_verify_batch_grouped(const uint8_t* tuples, size_t n, uint8_t* bitmap, u32 min_count, u32 max_groups,
@@ -577,6 +611,7 @@ void sbve_p256_verify_batch_grouped(const uint8_t* tuples, size_t n, uint8_t* bi
         if (v) bitmap[t >> 3] |= (uint8_t)(1u << (t & 7));
     }
     free(qtab); free(ktab); free(ntab); free(bases);
+    emul_note_readout(SBV_SCHEME_P256, n, g, kc, tslot.data(), cold.data(), bitmap);
     if (stats_out) { stats_out[0] = ngroups; stats_out[1] = counters[1]; stats_out[2] = counters[2]; stats_out[3] = counters[3]; }
 }
 
@@ -1145,6 +1180,7 @@ void sbve_ed25519_verify_batch_grouped(const uint8_t* tuples_in, size_t n, uint8
         if (v) bitmap[t >> 3] |= (uint8_t)(1u << (t & 7));
     }
     free(qtab); free(tmpa); free(ktab); free(jbases); free(tuples); free(gacc);
+    emul_note_readout(SBV_SCHEME_ED25519, n, g, kc, tslot.data(), cold.data(), bitmap);
     if (stats_out) { stats_out[0] = ngroups; stats_out[1] = counters[1]; stats_out[2] = counters[2]; stats_out[3] = counters[3]; }
 }
 // Ed25519 message front end (sha512_dev.h): 512-bit little-endian x -> x mod L; sig | pk | msg -> 128-byte tuple
@@ -1400,6 +1436,7 @@ void sbve_k256_verify_batch_grouped(const uint8_t* tuples, size_t n, uint8_t* bi
         if (k256_verify_lane(s, t, qtab, k256_gtab())) bitmap[t >> 3] |= (uint8_t)(1u << (t & 7));
     }
     free(qtab); free(ktab);
+    emul_note_readout(SBV_SCHEME_SECP256K1, n, g, kc, tslot.data(), cold.data(), bitmap);
     if (stats_out) { stats_out[0] = ngroups; stats_out[1] = counters[1]; stats_out[2] = counters[2]; stats_out[3] = counters[3]; }
 }
 
