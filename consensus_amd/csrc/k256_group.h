@@ -398,6 +398,35 @@ SBV_HD bool k256_qphase_lane_sorted(const Scratch& s, size_t t, size_t L, u32 sl
     return ok && k256_rx_matches(R, r);
 }
 
+// ---- hot keys (p256_group.h: "hot keys" / "life cycle"; the pool's combs have the layout of k256_keyed.h: SBV_K256_WIDE_*) ---------
+// Which Q kernel serves a wavefront of the key-sorted list, from two wave-level facts.  A lane is live when its group number is below
+// the group count and its table slot's key is a point; it is wide when the class kernel marked its group (wide[grp]: the slot is cached,
+// not being built in this batch, and owns a 16-bit comb).  The wide pass takes a wavefront only if a lane of it is live and every live
+// lane is wide; every other wavefront — a mixed one (every cached key keeps its full 8-bit comb: this scheme has no rows-only class)
+// and one without a live lane (somebody has to write its rejects) — stays with k_k256_qphase.  ONE function for both Q kernels and the
+// emulator (tests/emul/k256_hot_emul.cc): round 5's bug lived in two copies of such a rule.
+SBV_HD bool k256_lane_live(u32 grp, u32 groups, const u32* tslot, u32 nslots, const uint8_t* kvalid) {
+    if (grp >= groups) return false;
+    const u32 slot = tslot[grp];
+    return slot < nslots && kvalid[slot] != 0;
+}
+SBV_HD bool k256_lane_wide(u32 grp, u32 groups, const uint8_t* wide) { return grp < groups && wide[grp] != 0; }
+SBV_HD bool k256_wave_is_wide(bool any_live, bool any_live_not_wide) { return any_live && !any_live_not_wide; }
+// One lane of the wide pass: the parked u1 * G plus u2 * Q in 17 additions from the slot's 16-bit comb (the walker of the registered
+// path's widened slots), then the verdict.  A dead lane of a wide wavefront walks comb 0 — it exists whenever a wavefront is wide —
+// and rejects.  wc: the comb as the callers make it, kgcomb{wtab + kwide[slot] * SBV_K256_WIDE_ENTRIES, 16, 17} (k256_keyed.h).
+SBV_HD bool k256_qphase_wide_lane(const Scratch& s, size_t t, size_t L, bool live, const kgcomb& wc, const u32* gacc) {
+    u256 u2;
+    rec_load256(u2, s.rec, t, SBV_REC_U2);
+    kjpt R;
+    k256_gacc_load(R, gacc, s.cap, L);
+    k256_gphase_point(R, u2, wc);
+    u256 r;
+    rec_load256(r, s.rec, t, SBV_REC_R);
+    const bool ok = live && s.rec[t * SBV_REC_WORDS + SBV_REC_OK] != 0;
+    return ok && k256_rx_matches(R, r);
+}
+
 // key check of the ungrouped candidates (the P-256 step's group_keycheck_lane on this curve)
 SBV_HD bool k256_keycheck_lane(const uint8_t* tuples, size_t L, const GroupState& g, uint8_t* acc) {
     const u32 i = g.ung_cand[L];

@@ -6,6 +6,9 @@
 //   side_a: insert assign | chain chunk 0 | chain chunk 1
 //   side_b:        wait(assign) classify keycheck sort | wait(chain c) rows fill of chunk c
 //
+// With the hot-key pool on (sbv_secp256k1_hot_keys; off by default) side_b also runs the class kernel behind the sort, the wide pass
+// beside the chunks' Q launches and, behind the batch's last table windows, the tail that promotes (launch_k256_verify_grouped).
+//
 // The curve has a comb pool and a persistent key-table cache of its own (KeyPool: slots [0, kc.cap) are kept between batches,
 // [kc.cap, kc.cap + max_groups) are the per-batch area) — NOT the P-256 one: cache slots are found by the 64 key bytes, and a byte
 // string can be a point of both curves, so a shared table would let a crafted key be verified against the other curve's comb.
@@ -16,6 +19,7 @@
 
 #include "group_kernels_common.h"
 #include "k256_group.h"
+#include "k256_keyed.h"
 #include "p256_kernels.h"
 
 namespace sbv {
@@ -108,10 +112,18 @@ __global__ __launch_bounds__(SBV_VERIFY_BLOCK, 2) void k_k256_gphase_generic(Scr
 #ifndef SBV_K256_QPHASE_WAVES
 #define SBV_K256_QPHASE_WAVES 2      // 3 waves: 17-25 spilled dwords (the Jacobian addition on 64-bit columns needs them), measured no faster in rounds 3-4
 #endif
+// hot keys: is this wavefront the wide pass's (k256_group.h: k256_wave_is_wide)?  Both Q kernels ask with the same arguments.
+static __device__ __forceinline__ bool k256_wave_is_wide_dev(u32 grp, const GroupState& g, const u32* __restrict__ tslot, u32 table_slots,
+                                                             const uint8_t* __restrict__ kvalid, const uint8_t* __restrict__ wide, bool& live) {
+    const u32 groups = group_count(g);
+    live = k256_lane_live(grp, groups, tslot, table_slots, kvalid);
+    const bool w = k256_lane_wide(grp, groups, wide);
+    return k256_wave_is_wide(__ballot(live) != 0, __ballot(live && !w) != 0);
+}
 template <bool LAST>
 __global__ __launch_bounds__(SBV_VERIFY_BLOCK, SBV_K256_QPHASE_WAVES) void k_k256_qphase(Scratch s, GroupState g, const kapt* __restrict__ ktab, const uint8_t* __restrict__ kvalid,
                                                                    const u32* __restrict__ tslot, u32 table_slots,
-                                                                   u32* __restrict__ gacc, uint8_t* __restrict__ acc, int j0, int j1) {
+                                                                   u32* __restrict__ gacc, uint8_t* __restrict__ acc, int j0, int j1, const uint8_t* __restrict__ wide) {
     // key-sorted list, XCD-aware block order (p256_group_kernels.hip: k_verify_keyed_q)
     const u32 lanes = g.counters[1];
     const u32 per = ((lanes + SBV_VERIFY_BLOCK - 1) / SBV_VERIFY_BLOCK + 7) >> 3;
@@ -121,8 +133,62 @@ __global__ __launch_bounds__(SBV_VERIFY_BLOCK, SBV_K256_QPHASE_WAVES) void k_k25
     if (L >= lanes) return;
     const u32 t = g.grp_idx[L];
     const u32 grp = g.grp_of[L];
+    if (wide) {                                                       // null: the pool is off, nothing is skipped
+        bool live;
+        if (k256_wave_is_wide_dev(grp, g, tslot, table_slots, kvalid, wide, live)) return;      // k_k256_qphase_wide's wavefront
+    }
     const bool v = k256_qphase_lane_sorted(s, t, L, grp < group_count(g) ? tslot[grp] : SBV_GROUP_NONE, table_slots, ktab, kvalid, gacc, j0, j1, LAST);
     if (LAST) acc[t] = v ? 1 : 0;
+}
+// The wide pass (k256_group.h: hot keys): the wavefronts of the key-sorted list whose live lanes ALL belong to promoted cache slots —
+// u2 * Q in 17 additions from the slot's 16-bit comb instead of 32.2 from its 8-bit comb, one launch that needs no table of this batch.
+// Same block order as k_k256_qphase: the two kernels split the same wavefronts.
+__global__ __launch_bounds__(SBV_VERIFY_BLOCK, 2) void k_k256_qphase_wide(Scratch s, GroupState g, const uint8_t* __restrict__ kvalid, const u32* __restrict__ tslot,
+                                                                        u32 table_slots, const uint8_t* __restrict__ wide, const u32* __restrict__ kwide,
+                                                                        const kapt* __restrict__ wtab, u32 wide_cap, u32* __restrict__ wstat,
+                                                                        const u32* __restrict__ gacc, uint8_t* __restrict__ acc) {
+    if (g.counters[8] == 0) return;                                   // no group of this batch owns a comb
+    const u32 lanes = g.counters[1];
+    const u32 per = ((lanes + SBV_VERIFY_BLOCK - 1) / SBV_VERIFY_BLOCK + 7) >> 3;
+    const u32 local = blockIdx.x >> 3;
+    if (local >= per) return;
+    const u32 L = ((blockIdx.x & 7u) * per + local) * SBV_VERIFY_BLOCK + threadIdx.x;
+    if (L >= lanes) return;
+    const u32 t = g.grp_idx[L];
+    const u32 grp = g.grp_of[L];
+    bool live;
+    if (!k256_wave_is_wide_dev(grp, g, tslot, table_slots, kvalid, wide, live)) return;
+    const unsigned long long am = __ballot(live);
+    if ((threadIdx.x & 63) == (unsigned)__ffsll((long long)__ballot(true)) - 1u) atomicAdd(wstat, (u32)__popcll(am));     // statistics: live lanes of the wide pass
+    u32 w = live ? kwide[tslot[grp]] : 0u;                            // live in a wide wavefront: a cache slot that owns a comb (wide[grp] says so)
+    if (w >= wide_cap) { w = 0; live = false; }                       // never read past the pool
+    const kgcomb wc = {wtab + (size_t)w * SBV_K256_WIDE_ENTRIES, SBV_K256_WIDE_BITS, SBV_K256_WIDE_WINDOWS};
+    acc[t] = k256_qphase_wide_lane(s, t, L, live, wc, gacc) ? 1 : 0;
+}
+// Hot keys, per batch: the groups' tuple counts go to their cache slots' hit counters, and wide[k] = the slot owns a comb and is not
+// being built in this batch (p256_group.h: group_hot_class_lane); counters[8] = how many such groups (0 = the wide pass has no wavefront)
+__global__ __launch_bounds__(256) void k_k256_hot_class(GroupState g, const u32* __restrict__ tslot, const uint8_t* __restrict__ cold, HotKeys hk,
+                                                        uint8_t* __restrict__ wide) {
+    const u32 groups = group_count(g);
+    for (u32 k = blockIdx.x * 256 + threadIdx.x; k < groups; k += gridDim.x * 256) {
+        group_hot_class_lane(k, g, tslot, cold, hk.cache_cap, hk.kwide, hk.khits, wide);
+        if (wide[k]) atomicAdd(&g.counters[8], 1u);
+    }
+}
+// The builder of this batch's promotions: lane (promotion i, builder lane) writes one run of comb plist[2 i + 1] from the promoted cache
+// slot's 8-bit comb (k256_keyed.h: k256_widetab_lane).  A bounded grid walks promote_live x SBV_K256_WIDE_LANES items; scratch is per
+// lane of the grid.
+__global__ __launch_bounds__(64) void k_k256_promote_build(const u32* __restrict__ plist, const u32* __restrict__ hot, const kapt* __restrict__ ktab, u32 cache_cap,
+                                                           u32* __restrict__ tmp, kapt* __restrict__ wtab, u32 wide_cap) {
+    const u32 total = promote_live(hot) * SBV_K256_WIDE_LANES;
+    const u32 gid = blockIdx.x * 64 + threadIdx.x;
+    u32* mine = tmp + (size_t)gid * SBV_K256_WIDE_TMP_WORDS;
+    for (u32 item = gid; item < total; item += gridDim.x * 64) {
+        const u32 i = item / SBV_K256_WIDE_LANES, lane = item % SBV_K256_WIDE_LANES;
+        const u32 slot = plist[2 * i], w = plist[2 * i + 1];
+        if (slot >= cache_cap || w >= wide_cap) continue;             // an empty entry (0xFFFFFFFF: the pool was full)
+        k256_widetab_lane(ktab + (size_t)slot * SBV_K256_KEYTAB_ENTRIES, lane, mine, wtab + (size_t)w * SBV_K256_WIDE_ENTRIES);
+    }
 }
 
 // stage A + stage B of a grouped secp256k1 batch.  ev_fork must have been recorded on `stream` first.  kp: this curve's comb
@@ -158,21 +224,32 @@ hipError_t launch_k256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
     SBV_TRY(hipEventRecord(y.ev_assign, y.side_a));
     hipLaunchKernelGGL((k_key_cache_lookup_t<160, 96, 16>), dim3((b.max_groups + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, kp.kc, b.tslot, b.cold);
     hipLaunchKernelGGL((k_key_cache_insert_t<160, 96, 16>), dim3((b.max_groups + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, kp.kc, b.tslot);
+    // hot keys (k256_group.h): only with a pool to promote into, the cache on and the key-sorted list — the Ed25519 launcher's conditions
+    const bool hot_on = kp.wtab && kp.kwide && kp.wide && kp.build_blocks && kp.kc.enabled && g.sorted;
+    const HotKeys hk = {kp.wtab, hot_on ? kp.kwide : nullptr, kp.khits, kp.hot, kp.plist, kp.kc.cap, kp.wide_cap, kp.promote_min, kp.wowner, kp.elist};
+    const uint8_t* wide = hot_on ? kp.wide : nullptr;
+    if (hot_on) SBV_TRY(hipEventRecord(y.ev_cache, y.side_a));         // table slots assigned: the class kernel (side_b) reads them
     {   // stage A: SBV_K256_PREP_T tuples per lane share one inversion (Montgomery's trick).  Measured in round 4
         // (profiles/r04/ab_k256_prep_t_r04a.jsonl): 1 / 4 / 8 tuples per inversion 4.97 / 4.79 / 4.68 ms per 2^20 step.
         const size_t per_block = (size_t)64 * SBV_K256_PREP_T;
         hipLaunchKernelGGL(k_k256_prep_chunk, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(64), 0, stream, d_tuples, n, s, SBV_K256_PREP_T);
     }
     SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_assign, 0));
+    if (hot_on) SBV_TRY(hipMemsetAsync(kp.hot + 1, 0, 3 * sizeof(u32), y.side_b));       // behind the previous batch's builder, which reads hot[1]
     hipLaunchKernelGGL(k_group_classify, dim3(gn), dim3(256), 0, y.side_b, n, g, b.ung_cand, b.counters + 4);
     hipLaunchKernelGGL(k_k256_keycheck, dim3(gn), dim3(256), 0, y.side_b, d_tuples, g, b.acc);
     const unsigned tiles = (unsigned)((n + SBV_SORT_TILE - 1) / SBV_SORT_TILE);
     hipLaunchKernelGGL(k_group_sort_count, dim3(tiles), dim3(1024), sort_lds, y.side_b, n, g);
     hipLaunchKernelGGL(k_group_sort_scan, dim3(1), dim3(1024), 0, y.side_b, g);
     hipLaunchKernelGGL(k_group_sort_scatter, dim3(tiles), dim3(1024), sort_lds, y.side_b, n, g);
+    if (hot_on) {
+        SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_cache, 0));
+        hipLaunchKernelGGL(k_k256_hot_class, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, b.cold, hk, kp.wide);
+    }
     SBV_TRY(hipEventRecord(y.ev_split, y.side_b));
     SBV_TRY(hipStreamWaitEvent(stream, y.ev_split, 0));
     hipLaunchKernelGGL(k_k256_gphase_generic, dim3(2 * gv), dim3(SBV_VERIFY_BLOCK), 0, stream, s, g, d_qtab, d_gtab, kgcomb_make(d_gcomb, gcomb_bits), b.gacc, b.acc, gv);
+    if (hot_on) SBV_TRY(hipEventRecord(y.ev_class, stream));            // the G phase is enqueued: the wide pass (side_b) adds to its sums
     const int chunks = 2;
     for (int c = 0; c < chunks; ++c) {
         const int j_first = SBV_GTAB_WINDOWS * c / chunks, j_end = SBV_GTAB_WINDOWS * (c + 1) / chunks, j_count = j_end - j_first;
@@ -186,9 +263,31 @@ hipError_t launch_k256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
         SBV_TRY(hipEventRecord(y.ev_tables[c], tb));
         SBV_TRY(hipStreamWaitEvent(stream, y.ev_tables[c], 0));
         if (prof) SBV_TRY(hipEventRecord(prof[2 * c], stream));
-        if (c + 1 == chunks) hipLaunchKernelGGL(k_k256_qphase<true>, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, s, g, ktab, kvalid, b.tslot, table_slots, b.gacc, b.acc, j_first, j_end);
-        else hipLaunchKernelGGL(k_k256_qphase<false>, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, s, g, ktab, kvalid, b.tslot, table_slots, b.gacc, b.acc, j_first, j_end);
+        if (c + 1 == chunks) hipLaunchKernelGGL(k_k256_qphase<true>, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, s, g, ktab, kvalid, b.tslot, table_slots, b.gacc, b.acc, j_first, j_end, wide);
+        else hipLaunchKernelGGL(k_k256_qphase<false>, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, s, g, ktab, kvalid, b.tslot, table_slots, b.gacc, b.acc, j_first, j_end, wide);
         if (prof) SBV_TRY(hipEventRecord(prof[2 * c + 1], stream));
+    }
+    if (hot_on) {
+        // The wide pass, on side_b behind the G phase and the class kernel and beside the chunks' launches: it needs no table (ed25519_group_kernels.hip
+        // says why not on `stream` in front of them).  Then the tail, still on side_b: behind this batch's last table windows — those built on
+        // side_t too: the builder reads a promoted slot's 8-bit comb, which this very batch may have built — and behind the wide pass (an
+        // evicted comb is rewritten).  Stream order: the clock sweep, which slots get a comb, the evictions; then — the next batch's side_a may
+        // rewrite tslot from here on — the combs themselves and their publication.  The next batch's class kernel queues up behind all of it
+        // on this stream: a comb is used only once it is complete.  (The wave rule reads the valid byte of every lane's slot, a cold group's
+        // included: chunk 0's chain writes those, and side_b has waited for it in front of chunk 0's rows — both Q kernels see them final.)
+        SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_class, 0));
+        hipLaunchKernelGGL(k_k256_qphase_wide, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, y.side_b, s, g, kvalid, b.tslot, table_slots, wide, kp.kwide,
+                           reinterpret_cast<const kapt*>(kp.wtab), kp.wide_cap, kp.hot + 2, b.gacc, b.acc);
+        SBV_TRY(hipEventRecord(y.ev_wide, y.side_b));
+        SBV_TRY(hipStreamWaitEvent(stream, y.ev_wide, 0));
+        for (int c = 0; c < chunks; ++c) SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_tables[c], 0));
+        if (kp.hot_tick % SBV_HOT_DECAY_EVERY == SBV_HOT_DECAY_EVERY - 1) hipLaunchKernelGGL(k_hot_decay, dim3((kp.kc.cap + 255) / 256), dim3(256), 0, y.side_b, hk);
+        hipLaunchKernelGGL(k_promote_select, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, kvalid, hk);
+        hipLaunchKernelGGL(k_promote_evict, dim3(1), dim3(1024), 0, y.side_b, hk);
+        SBV_TRY(hipEventRecord(y.ev_promoted, y.side_b));
+        hipLaunchKernelGGL(k_k256_promote_build, dim3(kp.build_blocks), dim3(64), 0, y.side_b, kp.plist, kp.hot, ktab, kp.kc.cap, kp.ptmp,
+                           reinterpret_cast<kapt*>(kp.wtab), kp.wide_cap);
+        hipLaunchKernelGGL(k_promote_publish, dim3(1), dim3(64), 0, y.side_b, kp.plist, kp.hot, kp.kwide, kp.wowner);
     }
     hipLaunchKernelGGL(k_pack_bitmap, dim3((unsigned)(((n + 7) / 8 + 255) / 256)), dim3(256), 0, stream, b.acc, n, d_bitmap);
 #undef SBV_TRY

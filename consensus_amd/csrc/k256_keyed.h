@@ -41,6 +41,15 @@ namespace sbv {
 #define SBV_K256_WIDE_RUNS_PER_WINDOW (SBV_K256_WIDE_PER_WINDOW / SBV_K256_WIDE_RUN)
 #define SBV_K256_WIDE_LANES ((SBV_K256_WIDE_WINDOWS - 1) * SBV_K256_WIDE_RUNS_PER_WINDOW + 1)
 #define SBV_K256_WIDE_TMP_WORDS (SBV_K256_WIDE_RUN * 36)                      // per lane: 64 points x (X, Y, Z, prefix)
+// the hot-key pool's builder (k256_group_kernels.hip: k_k256_promote_build): a bounded grid of 64-lane workgroups walks the
+// promotions' SBV_K256_WIDE_LANES lanes each; at most 4 wavefronts per CU and 9 KiB of scratch per lane of the grid = 604 MB, fewer
+// for a pool so small that a batch's promotions (at most 64, at most the pool) have fewer lanes than that
+#define SBV_K256_HOT_BUILD_BLOCKS 1024u
+SBV_HD u32 k256_hot_build_blocks(u32 pool) {
+    const u32 combs = pool < 64u ? pool : 64u;
+    const u32 need = (combs * (u32)SBV_K256_WIDE_LANES + 63u) / 64u;
+    return need < SBV_K256_HOT_BUILD_BLOCKS ? need : SBV_K256_HOT_BUILD_BLOCKS;
+}
 
 // the device half of the registry as the kernels see it
 struct K256KeyedRegistry {

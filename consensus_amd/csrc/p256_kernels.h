@@ -96,6 +96,18 @@ struct KeyPool {
     uint8_t* kvalid = nullptr;  // (kc.cap + max_groups)
     KeyCache kc = {};
     u32 max_groups = 0;
+    // hot keys of this scheme (k256_group.h; sbv_secp256k1_hot_keys): 16-bit combs for promoted cache slots and the bookkeeping of
+    // EdGroupBuffers (same meaning, same kernels: group_kernels_common.h); wtab == nullptr = off, which is the default
+    void* wtab = nullptr;       // [wide_cap] combs of 17 x 32 768 64-byte affine entries (k256_keyed.h: SBV_K256_WIDE_*)
+    u32 *kwide = nullptr, *khits = nullptr;     // [kc.cap]
+    u32* hot = nullptr;         // [4] combs handed out | promotions of this batch | lanes of the wide pass | eviction candidates
+    u32* plist = nullptr;       // [2 x SBV_PROMOTE_MAX] (slot, comb)
+    u32* wowner = nullptr;      // [wide_cap]
+    u32* elist = nullptr;       // [SBV_PROMOTE_MAX]
+    u32* ptmp = nullptr;        // the builder's scratch: SBV_K256_WIDE_TMP_WORDS per lane of its grid
+    uint8_t* wide = nullptr;    // [max_groups] this batch's groups whose slot owns a comb
+    u32 wide_cap = 0, promote_min = 4096, hot_tick = 0;
+    u32 build_blocks = 0;       // workgroups of the builder's grid (k256_keyed.h: k256_hot_build_blocks); ptmp holds their lanes' scratch
 };
 // streams and events of the grouped step; owned by the context.  `chunks` (1..SBV_GROUP_MAX_CHUNKS) = how
 // many pieces the 33 key-comb windows are built and consumed in.

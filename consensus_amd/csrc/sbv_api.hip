@@ -115,6 +115,7 @@ struct Context {
     // hot keys (p256_group.h): wide combs for cache slots that keep being hit — how many (0 = off; 35.7 MB each) and from how many tuples on
     u32 hot_keys = 1024, hot_min_hits = 4096;
     u32 ed_hot_keys = 1024, ed_hot_min_hits = 4096;
+    u32 k256_hot_keys = 0, k256_hot_min_hits = 4096;      // secp256k1: off unless sbv_secp256k1_hot_keys / SBV_K256_HOT_KEYS asks for a pool
     bool pools_shrunk = false;          // fit_group_pools() gave this device smaller pools than asked for (sbv_p256_pool_stats)
     unsigned group_nomem_events = 0;    // how often a grouped batch fell back to the one-lane kernel for lack of memory (sbv_p256_pool_stats)
     unsigned group_nomem_skip = 0;      // grouped batches to run ungrouped before the pools are tried again (after an SBV_ENOMEM)
@@ -181,6 +182,7 @@ struct Settings {
     int wide_bits = SBV_WIDE_BITS_AUTO; u32 wide_max = 64;          // sbv_p256_wide_keys; env SBV_KEYED_WIDE_BITS (0 = off, 1 = auto), SBV_KEYED_WIDE_MAX
     u32 hot_keys = 1024, hot_min_hits = 4096;                       // sbv_p256_hot_keys; env SBV_HOT_KEYS (0 = off), SBV_HOT_MIN_HITS
     u32 ed_hot_keys = 1024, ed_hot_min_hits = 4096;                 // sbv_ed25519_hot_keys; env SBV_ED_HOT_KEYS (0 = off), SBV_ED_HOT_MIN_HITS
+    u32 k256_hot_keys = 0, k256_hot_min_hits = 4096;                // sbv_secp256k1_hot_keys; env SBV_K256_HOT_KEYS (default 0 = off), SBV_K256_HOT_MIN_HITS
 } g_settings;
 std::mutex g_set_mu;
 std::unique_ptr<Context> g_ctxs[kMaxDevices];
@@ -425,6 +427,29 @@ void ed_hot_free(sbv::EdGroupBuffers& e) {
     e.ptmp = nullptr; e.wide = nullptr; e.wide_cap = 0;
 }
 
+// the same for the secp256k1 scheme's pool (k256_group.h: hot keys)
+hipError_t k256_hot_forget(sbv::KeyPool& kp) {
+    if (!kp.kwide) return hipSuccess;
+    hipError_t r = memset_now(kp.kwide, 0xFF, (size_t)kp.kc.cap * sizeof(u32));
+    if (r == hipSuccess) r = memset_now(kp.khits, 0, (size_t)kp.kc.cap * sizeof(u32));
+    if (r == hipSuccess) r = memset_now(kp.hot, 0, 4 * sizeof(u32));
+    if (r == hipSuccess) r = memset_now(kp.wowner, 0xFF, (size_t)kp.wide_cap * sizeof(u32));
+    return r;
+}
+void k256_hot_free(sbv::KeyPool& kp) {
+    void* part[] = {kp.wtab, kp.kwide, kp.khits, kp.hot, kp.plist, kp.wowner, kp.elist, kp.ptmp, kp.wide};
+    for (void* q : part) if (q) (void)hipFree(q);
+    kp.wtab = nullptr; kp.kwide = nullptr; kp.khits = nullptr; kp.hot = nullptr; kp.plist = nullptr; kp.wowner = nullptr; kp.elist = nullptr;
+    kp.ptmp = nullptr; kp.wide = nullptr; kp.wide_cap = 0; kp.build_blocks = 0;
+}
+void k256_pool_free(sbv::KeyPool& kp) {
+    if (kp.ktab) (void)hipFree(kp.ktab);
+    if (kp.kvalid) (void)hipFree(kp.kvalid);
+    key_cache_free(kp.kc);
+    k256_hot_free(kp);
+    kp = sbv::KeyPool();
+}
+
 // keep_pools: the comb pools and key-table caches of the three schemes depend on (cache capacity, max_groups) only — a batch larger
 // than any before regrows the per-tuple arrays and must leave every cached comb where it is
 void free_group_buffers(Context& c, bool keep_pools = false) {
@@ -455,10 +480,7 @@ void free_group_buffers(Context& c, bool keep_pools = false) {
     key_cache_free(c.edgrp.kc);
     ed_hot_free(c.edgrp);
     c.edgrp = sbv::EdGroupBuffers();
-    if (c.k256pool.ktab) (void)hipFree(c.k256pool.ktab);
-    if (c.k256pool.kvalid) (void)hipFree(c.k256pool.kvalid);
-    key_cache_free(c.k256pool.kc);
-    c.k256pool = sbv::KeyPool();
+    k256_pool_free(c.k256pool);
 }
 
 bool wide_pool_fits(const Context& c, size_t extra_bytes, unsigned percent = 15);
@@ -686,20 +708,41 @@ int ensure_k256_group_buffers(Context& c, size_t n) {
     sbv::KeyPool& kp = c.k256pool;
     const size_t K = c.kc_caps[1];
     const u32 vg = variant_groups(c);
+    kp.promote_min = c.k256_hot_min_hits;
     if (kp.ktab && kp.max_groups == vg && kp.kc.cap == K) {
         kp.kc.enabled = c.kc_on[1] ? 1u : 0u;
         return SBV_OK;
     }
     HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    if (kp.ktab) (void)hipFree(kp.ktab);
-    if (kp.kvalid) (void)hipFree(kp.kvalid);
-    key_cache_free(kp.kc);
-    kp = sbv::KeyPool();
+    k256_pool_free(kp);
     HIP_TRY(SBV_ENOMEM, hipMalloc(&kp.ktab, (K + vg) * (size_t)SBV_KEYTAB_ENTRIES * sizeof(sbv::apt)));
     HIP_TRY(SBV_ENOMEM, hipMalloc(&kp.kvalid, K + vg));
     rc = key_cache_alloc(kp.kc, K, c.kc_on[1]);
     if (rc != SBV_OK) return rc;
     kp.max_groups = vg;
+    kp.promote_min = c.k256_hot_min_hits;
+    // hot keys of this scheme: an OPTIONAL pool of 35.7 MB combs, off unless asked for (sbv_secp256k1_hot_keys), as large as asked for if the
+    // device has the room (wide_pool_fits), smaller or absent otherwise — a failed allocation leaves the feature off, it never fails the
+    // batch; verdicts never depend on it.  The pool is zeroed once: a comb's top window holds one entry, the builder writes no other of it.
+    if (c.k256_hot_keys && K) {
+        size_t want = c.k256_hot_keys > 4096 ? 4096 : c.k256_hot_keys;
+        auto scratch_of = [](size_t w) { return (size_t)sbv::k256_hot_build_blocks((u32)w) * 64 * SBV_K256_WIDE_TMP_WORDS * sizeof(u32); };
+        while (want && !wide_pool_fits(c, want * SBV_K256_WIDE_COMB_BYTES + scratch_of(want))) want /= 2;
+        if (want) {
+            const size_t scratch = scratch_of(want);
+            const bool got = hipMalloc(&kp.wtab, want * SBV_K256_WIDE_COMB_BYTES) == hipSuccess && hipMalloc(&kp.kwide, K * sizeof(u32)) == hipSuccess &&
+                             hipMalloc(&kp.khits, K * sizeof(u32)) == hipSuccess && hipMalloc(&kp.hot, 4 * sizeof(u32)) == hipSuccess &&
+                             hipMalloc(&kp.plist, 2 * SBV_PROMOTE_MAX * sizeof(u32)) == hipSuccess && hipMalloc(&kp.ptmp, scratch) == hipSuccess &&
+                             hipMalloc(&kp.wowner, want * sizeof(u32)) == hipSuccess && hipMalloc(&kp.elist, SBV_PROMOTE_MAX * sizeof(u32)) == hipSuccess &&
+                             hipMalloc(&kp.wide, vg) == hipSuccess;
+            if (got) { kp.wide_cap = (u32)want; kp.build_blocks = sbv::k256_hot_build_blocks((u32)want); }
+            if (!got || k256_hot_forget(kp) != hipSuccess || memset_now(kp.wide, 0, vg) != hipSuccess ||
+                memset_now(kp.wtab, 0, want * SBV_K256_WIDE_COMB_BYTES) != hipSuccess) {
+                (void)hipGetLastError();
+                k256_hot_free(kp);
+            }
+        }
+    }
     return SBV_OK;
 }
 
@@ -1054,11 +1097,14 @@ int init_context(Context& c, int device) {
         c.kwide_auto = g_settings.wide_bits == SBV_WIDE_BITS_AUTO; c.kwide_bits = c.kwide_auto ? 20 : g_settings.wide_bits; c.kwide_max = g_settings.wide_max;
         c.hot_keys = g_settings.hot_keys; c.hot_min_hits = g_settings.hot_min_hits;
         c.ed_hot_keys = g_settings.ed_hot_keys; c.ed_hot_min_hits = g_settings.ed_hot_min_hits;
+        c.k256_hot_keys = g_settings.k256_hot_keys; c.k256_hot_min_hits = g_settings.k256_hot_min_hits;
     }
     if (const char* e = getenv("SBV_HOT_KEYS")) { const long v = atol(e); if (v >= 0 && v <= 4096) c.hot_keys = (u32)v; }
     if (const char* e = getenv("SBV_HOT_MIN_HITS")) { const long v = atol(e); if (v >= 1) c.hot_min_hits = (u32)v; }
     if (const char* e = getenv("SBV_ED_HOT_KEYS")) { const long v = atol(e); if (v >= 0 && v <= 4096) c.ed_hot_keys = (u32)v; }
     if (const char* e = getenv("SBV_ED_HOT_MIN_HITS")) { const long v = atol(e); if (v >= 1) c.ed_hot_min_hits = (u32)v; }
+    if (const char* e = getenv("SBV_K256_HOT_KEYS")) { const long v = atol(e); if (v >= 0 && v <= 4096) c.k256_hot_keys = (u32)v; }
+    if (const char* e = getenv("SBV_K256_HOT_MIN_HITS")) { const long v = atol(e); if (v >= 1) c.k256_hot_min_hits = (u32)v; }
     if (const char* e = getenv("SBV_KEYED_WIDE_BITS")) { const int v = atoi(e); if (v == 0) c.kwide_max = 0; else if (v == SBV_WIDE_BITS_AUTO) c.kwide_auto = true; else if (v >= 10 && v <= 20) { c.kwide_bits = v; c.kwide_auto = false; } }
     if (const char* e = getenv("SBV_KEYED_WIDE_MAX")) { const long v = atol(e); if (v >= 0 && v <= 4096) c.kwide_max = (u32)v; }
     if (const char* e = getenv("SBV_GROUP_SAMPLE_SHIFT")) { const int v = atoi(e); if (v >= 0 && v <= 6) c.group_sample_shift = v; }
@@ -1918,12 +1964,14 @@ int enqueue_k256(Context& c, const uint8_t* d_tuples, size_t m, uint8_t* d_bitma
         sbv::GroupSync y = c.gsync;                 // second table stream: the context's own, when the caller's runs the step (enqueue() says why)
         if (y.tstreams > 1 && stream != c.stream) y.side_t = c.stream;
         else y.tstreams = 1;
+        if (c.k256pool.wtab && c.k256pool.kc.enabled) ++c.k256pool.hot_tick;     // the clock of the hot keys' decay
         const sbv::GroupBuffers bv = variant_view(c, m);
         note_grouped_launch(c, SBV_SCHEME_SECP256K1, m, bv, sbv::k256_group_step_sorted(y, bv));
         const hipError_t ge = sbv::launch_k256_verify_grouped(d_tuples, s, m, bv, c.k256pool, c.d_qtab, c.d_k256_gtab, c.d_k256_gcomb, c.k256_gbits, d_bitmap, stream, y, dom, dom_pairs);
         if (ge != hipSuccess) {
             (void)hipDeviceSynchronize();
             (void)key_cache_forget(c.k256pool.kc);
+            (void)k256_hot_forget(c.k256pool);
             return fail(SBV_EDEVICE, "launch_k256_verify_grouped", ge);
         }
         return SBV_OK;
@@ -2692,6 +2740,7 @@ extern "C" int sbv_key_cache(int scheme, int enabled, uint32_t capacity) {
             if (e == hipSuccess && !c.kc_on[scheme]) e = key_cache_forget(kc);   // switching it off forgets everything: the next "on" starts cold
             if (e == hipSuccess && !c.kc_on[scheme] && scheme == SBV_SCHEME_P256) e = hot_forget(c.grp);
             if (e == hipSuccess && !c.kc_on[scheme] && scheme == SBV_SCHEME_ED25519) e = ed_hot_forget(c.edgrp);
+            if (e == hipSuccess && !c.kc_on[scheme] && scheme == SBV_SCHEME_SECP256K1) e = k256_hot_forget(c.k256pool);
             if (e != hipSuccess) rc = fail(SBV_EDEVICE, "sbv_key_cache", e);
         }
     }
@@ -2884,6 +2933,69 @@ extern "C" int sbv_ed25519_hot_selfcheck(uint32_t index) {
     for (size_t e = 0; e < want.size(); ++e)
         if (memcmp(got.data() + e * SBV_ED_HOT_PITCH, &want[e], sizeof(sbv::aniels)) != 0) return 0;
     return 1;
+}
+
+// Hot keys of the secp256k1 scheme (k256_group.h): the pool of 16-bit combs of Q; off by default
+extern "C" int sbv_secp256k1_hot_keys(uint32_t max_keys, uint32_t min_hits) {
+    if (max_keys > 4096) return SBV_EINVAL;
+    {
+        std::lock_guard<std::mutex> lk(g_set_mu);
+        g_settings.k256_hot_keys = max_keys;
+        if (min_hits) g_settings.k256_hot_min_hits = min_hits;
+    }
+    int rc = SBV_OK;
+    for (Context* cp : live_contexts()) {
+        std::lock_guard<std::mutex> lk(cp->mu);
+        Context& c = *cp;
+        if (min_hits) c.k256_hot_min_hits = min_hits;
+        if (c.k256_hot_keys == max_keys) continue;
+        c.k256_hot_keys = max_keys;
+        if (!c.ready || !c.k256pool.ktab) continue;
+        // another pool size: this scheme's comb pool (with its cache) is rebuilt by the next grouped batch
+        hipError_t e = hipSetDevice(c.hip_dev);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) { rc = fail(SBV_EDEVICE, "sbv_secp256k1_hot_keys", e); continue; }
+        k256_pool_free(c.k256pool);
+    }
+    return rc;
+}
+
+extern "C" int sbv_secp256k1_hot_key_stats(uint32_t out[4]) {
+    SBV_ENTER(c);
+    if (!c.ready) return SBV_ENOTINIT;
+    if (!out) return SBV_EINVAL;
+    out[0] = out[2] = 0;
+    out[1] = c.k256pool.wide_cap;
+    out[3] = c.k256_hot_min_hits;
+    if (!c.k256pool.hot) return SBV_OK;
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+    uint32_t h[4];
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(h, c.k256pool.hot, sizeof h, hipMemcpyDeviceToHost));
+    out[0] = h[0] < c.k256pool.wide_cap ? h[0] : c.k256pool.wide_cap;
+    out[2] = h[2];
+    return SBV_OK;
+}
+
+// 1 = promoted comb `index` equals the host builder's comb of its owner's key, byte for byte (K256Reg::wide_matches' builder)
+extern "C" int sbv_secp256k1_hot_selfcheck(uint32_t index) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    sbv::KeyPool& kp = c.k256pool;
+    if (!kp.wtab || !kp.kwide || index >= kp.wide_cap) { g_err = "no such comb in the secp256k1 hot-key pool"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+    std::vector<u32> kw(kp.kc.cap);
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(kw.data(), kp.kwide, kw.size() * sizeof(u32), hipMemcpyDeviceToHost));
+    size_t slot = kw.size();
+    for (size_t i = 0; i < kw.size(); ++i) if (kw[i] == index) slot = i;
+    if (slot == kw.size()) { g_err = "sbv_secp256k1_hot_selfcheck: no promoted key has this index"; return SBV_EINVAL; }
+    uint8_t key[SBV_K256_KEY_BYTES];
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(key, kp.kc.keys + slot * 16, sizeof key, hipMemcpyDeviceToHost));
+    std::vector<sbv::kapt> want(SBV_K256_WIDE_ENTRIES), got(SBV_K256_WIDE_ENTRIES);
+    if (!sbv::host_build_k256_wide_comb(key, want.data())) return 0;        // only points are promoted
+    HIP_TRY(SBV_EDEVICE, hipMemcpy((void*)got.data(), reinterpret_cast<const sbv::kapt*>(kp.wtab) + (size_t)index * SBV_K256_WIDE_ENTRIES, SBV_K256_WIDE_COMB_BYTES, hipMemcpyDeviceToHost));
+    return memcmp((const void*)got.data(), (const void*)want.data(), SBV_K256_WIDE_COMB_BYTES) == 0 ? 1 : 0;
 }
 
 // Diagnostics (round 6): every promoted comb of context `device` against the host builder, and the consistency of kwide / wowner.

@@ -393,6 +393,21 @@ int sbv_p256_hot_selfcheck(uint32_t index);
 int sbv_ed25519_hot_keys(uint32_t max_keys, uint32_t min_hits);
 int sbv_ed25519_hot_key_stats(uint32_t out[4]);
 int sbv_ed25519_hot_selfcheck(uint32_t index);
+/* The same for the secp256k1 variant: a cache slot of that scheme whose count passes `min_hits` gets a 16-bit comb of Q (17 windows x
+ * 32 768 affine entries of 64 bytes = 35.7 MB, the layout of the registered path's widened slots), built on the device from the slot's
+ * 8-bit comb; later batches add u2 * Q for its tuples in 17 additions instead of 32.2, in one launch that needs no table of the batch.
+ * Same bookkeeping as above (counts per slot, decay, at most 64 promotions per batch, eviction with hysteresis).  OFF by default:
+ * sbv_secp256k1_hot_keys(max_keys, min_hits) switches the pool on with up to max_keys combs (at most 4096; fewer if the device lacks
+ * the room), max_keys = 0 switches it off and frees it; min_hits = 0 keeps the current value (default 4096); env SBV_K256_HOT_KEYS,
+ * SBV_K256_HOT_MIN_HITS.  Needs this scheme's key-table cache; forgotten whenever the cache is.  Verdicts never depend on it.  stats /
+ * selfcheck as for P-256: selfcheck(i) = 1 when promoted comb i equals the host builder's comb of its owner's key byte for byte.
+ * (The return types stand on lines of their own: the registered-key entries above are counted by their one-line form.) */
+int
+sbv_secp256k1_hot_keys(uint32_t max_keys, uint32_t min_hits);
+int
+sbv_secp256k1_hot_key_stats(uint32_t out[4]);
+int
+sbv_secp256k1_hot_selfcheck(uint32_t index);
 
 /* Page-locked host memory for the host-pointer entries.  Handing pageable memory to a 100 MB batch makes the HIP
  * runtime pin (or bounce) it inside the call — measured at 25 ms for a 550 000-signature replay batch whose kernels

@@ -8,6 +8,8 @@ checks on: an operand outside its bounds aborts the process).  No GPU needed.
   ed       the Ed25519 grouped step (key check over the ungrouped candidates, batched finish) against the oracle on seeded batches
   p256g    the P-256 grouped step (sorted / compaction order, 1-4 chunks, the one-launch latency form, key-table cache on / off; round 5: table classes — rows only / full / upgrade)
   k256g    the secp256k1 grouped step (1-3 chunks, stage-A chunking, its key-table cache on / off)
+  k256hot  the secp256k1 grouped step with its hot-key pool (tests/emul/k256_hot_emul.cc: class lane, wave rule, wide lane, tail) on a
+           persistent cache: three passes over a seeded batch against the oracle, the last promoted comb against the host builder
   one      the one-lane kernels of the three schemes (all-distinct keys / small batches: 256 doublings per signature)
 
 usage: fuzz_emul.py <minutes> [workers]      one JSON line per worker at the end; exit status 1 on any mismatch."""
@@ -15,6 +17,20 @@ import ctypes, json, multiprocessing as mp, os, random, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+
+
+HOT_SO = os.path.join(ROOT, "tests", "emul", "libsbv_k256_hot_emul.so")
+
+
+def build_hot_emul():
+    """tests/emul/k256_hot_emul.cc -> its library, when the library is missing or older than its source or a header of consensus_amd/csrc
+    (the rule of the CPU tier's fixture, tests/test_k256_hot_cpu.py); called once, before the workers are started"""
+    import subprocess
+    src = os.path.join(ROOT, "tests", "emul", "k256_hot_emul.cc")
+    csrc = os.path.join(ROOT, "consensus_amd", "csrc")
+    deps = [src] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
+    if not os.path.exists(HOT_SO) or any(os.path.getmtime(d) > os.path.getmtime(HOT_SO) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wno-misleading-indentation", src, "-o", HOT_SO])
 
 
 def worker(args):
@@ -49,6 +65,12 @@ def worker(args):
     emul.sbve_ed_hot_comb_mismatches.argtypes = [ctypes.c_uint32]
     emul.sbve_ed_hot_comb_mismatches.restype = ctypes.c_size_t
     oracle.sbvo_k256_gen_batch.argtypes = gen_args
+    khot = ctypes.CDLL(HOT_SO)                  # built before the workers were started (build_hot_emul)
+    if khot:
+        khot.sbvk256hot_reset.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+        khot.sbvk256hot_verify.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+        khot.sbvk256hot_comb_mismatches.argtypes = [ctypes.c_uint32]
+        khot.sbvk256hot_comb_mismatches.restype = ctypes.c_long
     rng = random.Random(0xF022 + wid)
     out = {"worker": wid, "wide_keys": 0, "keyed_tuples": 0, "ed_tuples": 0, "p256g_tuples": 0, "k256g_tuples": 0, "one_tuples": 0, "mismatches": 0}
     t_end = time.time() + 60 * minutes
@@ -169,6 +191,24 @@ def worker(args):
                 emul.sbve_key_cache(0, 64); emul.sbve_set_group_sort(1); emul.sbve_set_group_chunks(3); emul.sbve_set_group_coop(0)
             else:
                 emul.sbve_scheme_key_cache(1, 0, 64)
+            if not p256 and khot and rng.random() < 0.35:
+                # this scheme's hot keys: a pool of 1-3 combs (each costs the emulator about a second), promotion behind the first or the
+                # second pass; later passes serve the all-hot wavefronts from them
+                khot.sbvk256hot_reset(1024, rng.choice((1, 2, 3)), rng.choice((40, 150, 400)))
+                hs = (ctypes.c_uint32 * 8)()
+                for rep in range(3):
+                    bm = ctypes.create_string_buffer((n + 7) // 8)
+                    khot.sbvk256hot_verify(tup.raw, n, bm, hs)
+                    out["k256hot_tuples"] = out.get("k256hot_tuples", 0) + n
+                    if bm.raw != exp.raw:
+                        out["mismatches"] += 1
+                        out.setdefault("first", ["k256hot", seed, n, nkeys, rep])
+                out["k256hot_promotions"] = out.get("k256hot_promotions", 0) + hs[3]
+                out["k256hot_wide_tuples"] = out.get("k256hot_wide_tuples", 0) + hs[2]
+                if hs[3] and khot.sbvk256hot_comb_mismatches(hs[3] - 1) != 0:
+                    out["mismatches"] += 1
+                    out.setdefault("first", ["k256hot comb", seed, n, nkeys])
+                khot.sbvk256hot_reset(0, 0, 0)
         else:
             n, nkeys = rng.choice((300, 700, 1100)), rng.choice((3, 7, 20))
             seed = rng.randrange(1 << 32)
@@ -223,6 +263,7 @@ def worker(args):
 if __name__ == "__main__":
     minutes = float(sys.argv[1]) if len(sys.argv) > 1 else 1.0
     workers = int(sys.argv[2]) if len(sys.argv) > 2 else 8
+    build_hot_emul()
     with mp.Pool(workers) as pool:
         res = pool.map(worker, [(w, minutes) for w in range(workers)])
     for r in res:
