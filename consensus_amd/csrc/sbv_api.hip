@@ -3416,6 +3416,9 @@ int part_enqueue(Context& c, const uint8_t* d_tuples, size_t n, u32 part, u32 pa
         int rc = ensure_part_buffers(c, pb, m);
         if (rc != SBV_OK) return rc;
         const uint8_t* src = d_tuples + off * SBV_TUPLE_BYTES;
+        // the staging (member list, dense tuples, dense verdicts) is single-flight like the scratch: the part before this one, queued on
+        // another stream, reads it until its scatter is through — c.busy is recorded behind that
+        if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(stream, c.busy, 0));
         HIP_TRY(SBV_EDEVICE, hipMemsetAsync(pb.d_count, 0, sizeof(u32), stream));
         hipLaunchKernelGGL(k_part_select, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, src, m, part, parts, pb.d_idx, pb.d_count);
         HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(pb.h_count, pb.d_count, sizeof(u32), hipMemcpyDeviceToHost, stream));
@@ -3424,14 +3427,15 @@ int part_enqueue(Context& c, const uint8_t* d_tuples, size_t n, u32 part, u32 pa
         HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(stream));
         const size_t members = *pb.h_count;
         total += members;
-        if (members == 0) continue;
+        if (members == 0) continue;          // no busy to record: the select is the only user of the staging so far, and the stream was just synchronised
         hipLaunchKernelGGL(k_part_gather, dim3((unsigned)((members * 10 + 255) / 256)), dim3(256), 0, stream, src, pb.d_idx, members, pb.d_dense);
         if ((rc = ensure_capacity(c, members)) != SBV_OK) return rc;
         if (c.busy_valid) HIP_TRY(SBV_EDEVICE, hipStreamWaitEvent(stream, c.busy, 0));
         rc = enqueue(c, pb.d_dense, members, pb.d_bits, stream, nullptr, nullptr, nullptr, n);
+        if (rc == SBV_OK) hipLaunchKernelGGL(k_part_scatter, dim3((unsigned)((members + 255) / 256)), dim3(256), 0, stream, pb.d_bits, pb.d_idx, members, d_out_words + off / 32);
+        // behind the scatter, the last reader of the staging; also on failure: part of the step may be enqueued
         if (hipEventRecord(c.busy, stream) == hipSuccess) c.busy_valid = true;
         if (rc != SBV_OK) return rc;
-        hipLaunchKernelGGL(k_part_scatter, dim3((unsigned)((members + 255) / 256)), dim3(256), 0, stream, pb.d_bits, pb.d_idx, members, d_out_words + off / 32);
         HIP_TRY(SBV_EDEVICE, hipGetLastError());
         if (off + kMaxChunk < n) HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(stream));       // the staging buffers are reused by the next chunk
     }

@@ -108,7 +108,20 @@ int sbv_key_cache_stats(int scheme, uint32_t out[4]);
 
 /* Same, on device-resident buffers, asynchronous on `hip_stream` (a hipStream_t; NULL = the
  * default stream).  d_tuples: n*160 bytes, 16-byte aligned.  d_bitmap: ceil(n/8) bytes.
- * The caller synchronises the stream.  Used by bench.py / multi-GPU shards. */
+ * The caller synchronises the stream.  Used by bench.py / multi-GPU shards.
+ * The stream contract of this and every other `_dev` / `_dev_part` entry (tests/test_gpu_stream_order.py):
+ *   - work queued on `hip_stream` BEFORE the call is seen: a kernel or copy that produces the inputs there needs no synchronisation
+ *     in front of the call, although the library reads them on streams of its own as well;
+ *   - work queued on `hip_stream` AFTER the call sees the complete output and may overwrite the inputs at once: every reader the
+ *     library started on another stream is joined back into `hip_stream` inside the call;
+ *   - any OTHER stream of the caller's that produces the inputs or consumes the output needs an event of the caller's between it
+ *     and `hip_stream`, as for any other stream-ordered work;
+ *   - the buffers must stay allocated until `hip_stream` has passed the call (the library keeps no reference beyond that point; a
+ *     hipFree in front of it is the caller's error);
+ *   - calls from different streams and from different host threads, of any scheme, host-pointer entries and setters included, are
+ *     ordered against each other by the library: it shares scratch, grouping arrays and table pools between them and asks no
+ *     event of the caller for that.  A call that has to grow a buffer, and every setter that frees or rewrites device state,
+ *     waits on the host for the calls queued before it; an entry that says so (`_dev_part`) waits for its own stream once. */
 int sbv_p256_verify_batch_dev(const void* d_tuples, size_t n, void* d_bitmap, void* hip_stream);
 
 /* ---- registered public keys ---------------------------------------------------------------------
