@@ -476,6 +476,72 @@ def sign_batch_dev(d_keys_ptr: int, n_keys: int, d_index_ptr: int, d_digests_ptr
     _check(lib.sbv_p256_sign_batch_dev(d_keys_ptr, n_keys, d_index_ptr or None, d_digests_ptr, n, d_sigs_ptr, d_ok_ptr, stream or None))
 
 
+def ed25519_expand_keys(seeds):
+    """sbv_ed25519_expand_keys: 32-byte seeds (a list, or their concatenation) -> (expanded, pks): the 96-byte expanded records
+    (a mod L | prefix | A_enc, as secret as the seeds) in one bytes object, and the list of 32-byte public keys."""
+    lib = load()
+    blob = seeds if isinstance(seeds, (bytes, bytearray)) else b"".join(seeds)
+    if len(blob) % 32:
+        raise ValueError("seeds are 32 bytes each")
+    m = len(blob) // 32
+    lib.sbv_ed25519_expand_keys.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p]
+    exp, pks = ctypes.create_string_buffer(max(1, 96 * m)), ctypes.create_string_buffer(max(1, 32 * m))
+    _check(lib.sbv_ed25519_expand_keys(bytes(blob), m, exp, pks))
+    return exp.raw[:96 * m], [pks.raw[32 * i:32 * i + 32] for i in range(m)]
+
+
+def ed25519_sign_msgs(expanded: bytes, msgs, key_index=None):
+    """sbv_ed25519_sign_msgs: RFC 8032 signatures (R | S, 64 bytes each) of the messages under the expanded records
+    (key_index[i], default i % n_keys).  Returns (sigs, ok): a list of signatures and ok[i] = 1 per produced one (an index out of
+    range gives ok[i] = 0 and 64 zero bytes).  NOT constant-time: see include/sbv.h."""
+    lib = load()
+    n, nk = len(msgs), len(expanded) // 96
+    offs = (ctypes.c_uint64 * (n + 1))()
+    acc = 0
+    for i, m in enumerate(msgs):
+        offs[i] = acc
+        acc += len(m)
+    offs[n] = acc
+    lib.sbv_ed25519_sign_msgs.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64),
+                                          ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p]
+    sigs, ok = ctypes.create_string_buffer(max(1, 64 * n)), ctypes.create_string_buffer(max(1, n))
+    idx = None if key_index is None else (ctypes.c_uint32 * n)(*key_index)
+    _check(lib.sbv_ed25519_sign_msgs(expanded, nk, idx, b"".join(msgs), offs, n, sigs, ok))
+    return [sigs.raw[64 * i:64 * i + 64] for i in range(n)], ok.raw[:n]
+
+
+def ed25519_sign(seeds, msgs, key_index=None):
+    """expand the seeds, then sign: (sigs, ok) as ed25519_sign_msgs returns them"""
+    expanded, _ = ed25519_expand_keys(seeds)
+    return ed25519_sign_msgs(expanded, msgs, key_index)
+
+
+def ed25519_expand_keys_stream(d_seeds_ptr: int, m: int, d_expanded_ptr: int, d_pks_ptr: int = 0, stream: int = 0) -> None:
+    lib = load()
+    lib.sbv_ed25519_expand_keys_stream.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib.sbv_ed25519_expand_keys_stream(d_seeds_ptr, m, d_expanded_ptr, d_pks_ptr or None, stream or None))
+
+
+def ed25519_sign_msgs_stream(d_expanded_ptr: int, n_keys: int, d_index_ptr: int, d_msgs_ptr: int, d_offsets_ptr: int, n: int,
+                             d_sigs_ptr: int, d_ok_ptr: int, stream: int = 0) -> None:
+    """device pointers; asynchronous on `stream` under the stream contract of the _dev entries (include/sbv.h)"""
+    lib = load()
+    lib.sbv_ed25519_sign_msgs_stream.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib.sbv_ed25519_sign_msgs_stream(d_expanded_ptr, n_keys, d_index_ptr or None, d_msgs_ptr or None, d_offsets_ptr, n, d_sigs_ptr,
+                                            d_ok_ptr, stream or None))
+
+
+def debug_ed25519_sign_op(op: int, blobs):
+    """sbv_debug_ed25519_sign_op (test only): one case per lane; op 0 takes 96-byte inputs, ops 1 and 2 32-byte ones -> 32-byte outputs"""
+    lib = load()
+    n = len(blobs)
+    lib.sbv_debug_ed25519_sign_op.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+    out = ctypes.create_string_buffer(max(1, 32 * n))
+    _check(lib.sbv_debug_ed25519_sign_op(op, b"".join(blobs), out, n))
+    return [out.raw[32 * i:32 * i + 32] for i in range(n)]
+
+
 def key_cache_stats(scheme: int = SCHEME_P256):
     """(cached keys, groups of the last grouped batch that hit, that missed, capacity)"""
     out = (ctypes.c_uint32 * 4)()

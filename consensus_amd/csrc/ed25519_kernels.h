@@ -57,7 +57,15 @@ hipError_t launch_ed25519_verify_keyed(const uint8_t* d_tuples, const u32* d_slo
                                        u32* d_gacc, uint8_t* d_okb, uint8_t* d_acc, uint8_t* d_bitmap, hipStream_t stream);
 // 16-bit combs of `count` slots from their 8-bit combs: plist = (slot, comb index) pairs; tmp = blocks x 64 x SBV_ED_HOT_TMP_WORDS words
 hipError_t launch_ed_keyed_widen(const u32* d_plist, u32 count, const aniels* d_ktab, u32* d_tmp, u32 blocks, uint8_t* d_wtab, hipStream_t stream);
-#define SBV_ED_KEYTAB_ENTRIES_PER_KEY 4096   // 32 windows x 128 entries (ed25519_group.h)
+// Batch signing (ed25519_sign.h, ed25519_sign_kernels.hip).  btab = the 16-bit comb of B of the one-lane kernel (host_build_ed_b16).
+// seeds m x 32 -> expanded m x 96 (a mod L | prefix | A_enc) and, unless null, pks m x 32
+hipError_t launch_ed_sign_expand(const uint8_t* d_seeds, size_t m, const aniels* d_btab, uint8_t* d_expanded, uint8_t* d_pks, hipStream_t stream);
+// signature i = sign(expanded[key_index[i]] or, with a null index, expanded[i % n_keys]; msgs[moff[i] .. moff[i+1])): sigs n x 64, ok n bytes
+hipError_t launch_ed_sign(const uint8_t* d_expanded, u32 n_keys, const u32* d_key_index, const uint8_t* d_msgs, const u64* d_moff, size_t n,
+                          const aniels* d_btab, uint8_t* d_sigs, uint8_t* d_ok, hipStream_t stream);
+// test only: one case of unit operation `op` per lane (sbv_debug_ed25519_sign_op)
+hipError_t launch_ed_sign_op(int op, const uint8_t* d_in, uint8_t* d_out, size_t n, const aniels* d_btab, hipStream_t stream);
+#define SBV_ED_KEYTAB_ENTRIES_PER_KEY 4096  // 32 windows x 128 entries (ed25519_group.h)
 void host_build_ed_b16(aniels* out);      // 16 x 32768 affine-Niels multiples of B: the comb of the one-lane kernel
 void host_build_ed_bcomb(int bits, aniels* out);   // edcomb_entries(bits) entries: the grouped step's comb (SBV_ED_B_BITS, default 20), one host thread per window
 }  // namespace sbv

@@ -2671,6 +2671,150 @@ extern "C" int sbv_p256_sign_batch(const uint8_t* keys, uint32_t n_keys, const u
     return rc;
 }
 
+// ---- Ed25519 batch signing (ed25519_sign.h, ed25519_sign_kernels.hip) -------------------------------------------------------
+// Stateless apart from the read-only comb of B (ensure_ed_table).  The _stream forms read and write only buffers of the caller's, on
+// the caller's stream: nothing of the library's is shared between two calls, so there is nothing to order and nothing to join back.
+extern "C" int sbv_ed25519_expand_keys_stream(const void* d_seeds, size_t m, void* d_expanded, void* d_pks, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!d_seeds || !d_expanded) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (m > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(d_seeds) | reinterpret_cast<uintptr_t>(d_expanded) | reinterpret_cast<uintptr_t>(d_pks)) & 3) {
+        g_err = "misaligned device pointer";
+        return SBV_EINVAL;
+    }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const int rc = ensure_ed_table(c);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, sbv::launch_ed_sign_expand(static_cast<const uint8_t*>(d_seeds), m, c.d_btab, static_cast<uint8_t*>(d_expanded),
+                                                    static_cast<uint8_t*>(d_pks), static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_ed25519_sign_msgs_stream(const void* d_expanded, uint32_t n_keys, const void* d_key_index, const void* d_msgs,
+                                            const void* d_msg_offsets, size_t n, void* d_sigs, void* d_ok, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!d_expanded || !d_msg_offsets || !d_sigs || !d_ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
+    if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
+    if (((reinterpret_cast<uintptr_t>(d_expanded) | reinterpret_cast<uintptr_t>(d_key_index) | reinterpret_cast<uintptr_t>(d_sigs)) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_msg_offsets) & 7)) {
+        g_err = "misaligned device pointer";
+        return SBV_EINVAL;
+    }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const int rc = ensure_ed_table(c);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, sbv::launch_ed_sign(static_cast<const uint8_t*>(d_expanded), n_keys, static_cast<const u32*>(d_key_index),
+                                             static_cast<const uint8_t*>(d_msgs), static_cast<const uint64_t*>(d_msg_offsets), n, c.d_btab,
+                                             static_cast<uint8_t*>(d_sigs), static_cast<uint8_t*>(d_ok), static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_ed25519_expand_keys(const uint8_t* seeds, size_t m, uint8_t* expanded, uint8_t* pks) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!seeds || !expanded) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (m > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_ed_table(c);
+    if (rc != SBV_OK) return rc;
+    // not a hot path: buffers of the call's own size, zeroed and released before returning (seeds and records do not linger in a pool)
+    uint8_t *d_seeds = nullptr, *d_exp = nullptr, *d_pks = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_seeds, m * 32))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_exp, m * 96))) break;
+        if (pks && fail(SBV_ENOMEM, hipMalloc(&d_pks, m * 32))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_seeds, seeds, m * 32, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_ed_sign_expand(d_seeds, m, c.d_btab, d_exp, d_pks, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(expanded, d_exp, m * 96, hipMemcpyDeviceToHost, c.stream))) break;
+        if (pks && fail(SBV_EDEVICE, hipMemcpyAsync(pks, d_pks, m * 32, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (d_seeds) (void)hipMemsetAsync(d_seeds, 0, m * 32, c.stream);
+    if (d_exp) (void)hipMemsetAsync(d_exp, 0, m * 96, c.stream);
+    (void)hipStreamSynchronize(c.stream);
+    if (d_seeds) (void)hipFree(d_seeds);
+    if (d_exp) (void)hipFree(d_exp);
+    if (d_pks) (void)hipFree(d_pks);
+    return rc;
+}
+
+extern "C" int sbv_ed25519_sign_msgs(const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs,
+                                     const uint64_t* msg_offsets, size_t n, uint8_t* sigs, uint8_t* ok) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!expanded || !msg_offsets || !sigs || !ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
+    if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
+    size_t mbytes = 0;
+    int rc = check_offsets(msg_offsets, n, msgs, mbytes);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    if ((rc = ensure_ed_table(c)) != SBV_OK) return rc;
+    uint8_t *d_exp = nullptr, *d_msgs = nullptr, *d_sig = nullptr, *d_ok = nullptr;
+    uint64_t* d_moff = nullptr;
+    u32* d_idx = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_exp, (size_t)n_keys * 96))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_msgs, mbytes + 16))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_moff, (n + 1) * sizeof(uint64_t)))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
+        if (key_index && fail(SBV_ENOMEM, hipMalloc(&d_idx, n * sizeof(u32)))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_exp, expanded, (size_t)n_keys * 96, hipMemcpyHostToDevice, c.stream))) break;
+        if (mbytes && fail(SBV_EDEVICE, hipMemcpyAsync(d_msgs, msgs, mbytes, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_moff, msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream))) break;
+        if (key_index && fail(SBV_EDEVICE, hipMemcpyAsync(d_idx, key_index, n * sizeof(u32), hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_ed_sign(d_exp, n_keys, d_idx, d_msgs, d_moff, n, c.d_btab, d_sig, d_ok, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(sigs, d_sig, n * 64, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (d_exp) {
+        (void)hipMemsetAsync(d_exp, 0, (size_t)n_keys * 96, c.stream);
+        (void)hipStreamSynchronize(c.stream);
+    }
+    if (d_exp) (void)hipFree(d_exp);
+    if (d_msgs) (void)hipFree(d_msgs);
+    if (d_moff) (void)hipFree(d_moff);
+    if (d_sig) (void)hipFree(d_sig);
+    if (d_ok) (void)hipFree(d_ok);
+    if (d_idx) (void)hipFree(d_idx);
+    return rc;
+}
+
+// Test only (include/sbv.h): one case of a unit operation of the signer per lane.
+extern "C" int sbv_debug_ed25519_sign_op(int op, const uint8_t* in, uint8_t* out, size_t n) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (op < 0 || op > 2) { g_err = "unknown operation"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!in || !out || n > kMaxChunk) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_ed_table(c);
+    if (rc != SBV_OK) return rc;
+    const size_t in_bytes = n * (op == 0 ? 96 : 32);
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_in, in_bytes))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_out, n * 32))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_ed_sign_op(op, d_in, d_out, n, c.d_btab, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    return rc;
+}
+
 extern "C" void* sbv_host_alloc(size_t bytes) {
     SBV_ENTER(c);
     if (!c.ready || bytes == 0) return nullptr;

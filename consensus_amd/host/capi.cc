@@ -244,6 +244,17 @@ void* sbvh_signer_new_scheme(int scheme, uint64_t id, const uint8_t sk[32]) { re
 void sbvh_signer_free(void* s) { delete (Signer*)s; }
 void sbvh_signer_public_key(void* s, uint8_t q[64]) { memcpy(q, ((Signer*)s)->public_key(), 64); }
 size_t sbvh_sign(void* s, const void* msg, size_t n, void* out, size_t cap) { return put(((Signer*)s)->Sign(B(msg, n)), out, cap); }
+// Signer::SignBatch: message i = msgs[offsets[i] .. offsets[i+1]); signature i goes to out + i * stride (at most `stride` bytes of it:
+// 64 for Ed25519, up to 72 of DER otherwise).  Returns how many signatures were produced and fit.
+size_t sbvh_sign_batch(void* s, const void* msgs, const uint64_t* offsets, size_t n, void* out, size_t stride) {
+    std::vector<bytes> in(n);
+    for (size_t i = 0; i < n; ++i) in[i] = B((const char*)msgs + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    const std::vector<bytes> sigs = ((Signer*)s)->SignBatch(in);
+    size_t done = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (!sigs[i].empty() && put(sigs[i], (char*)out + i * stride, stride) == sigs[i].size() && sigs[i].size() <= stride) ++done;
+    return done;
+}
 void sbvh_sign_proposal(void* s, const void* payload, size_t pl, const void* header, size_t hl, const void* meta, size_t ml,
                         int64_t vseq, const void* aux, size_t al, void* msg_out, size_t msg_cap, size_t* msg_len,
                         void* val_out, size_t val_cap, size_t* val_len) {

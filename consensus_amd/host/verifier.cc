@@ -1361,6 +1361,30 @@ bytes Signer::Sign(const bytes& msg) {
     if (!(scheme_ == Scheme::SECP256K1 ? k256_sign_rfc6979(d_, h, rs) : sign_rfc6979(d_, h, rs))) return bytes();
     return der_encode_sig(rs);
 }
+// The batch form.  Under Scheme::ED25519, when the process has a device initialised (a GPU backend exists: make_sbv_backend, or the
+// caller's own sbv_init), the whole batch is one sbv_ed25519_sign_msgs call under this signer's expanded record, which the device
+// derives from the seed on the first batch; byte-identical to Sign (the scheme is deterministic).  Otherwise a loop over Sign.
+// A device error gives empty signatures, as a failed Sign does.  NOT constant-time on the device: see include/sbv.h.
+std::vector<bytes> Signer::SignBatch(const std::vector<bytes>& msgs) {
+    std::vector<bytes> out(msgs.size());
+    if (msgs.empty()) return out;
+    if (scheme_ == Scheme::ED25519 && msgs.size() <= ((size_t)1 << 21) && sbv_initialised_devices(nullptr, 0) > 0) {
+        int rc = SBV_OK;
+        if (!ed_rec_ready_ && (rc = sbv_ed25519_expand_keys(d_, 1, ed_rec_, nullptr)) == SBV_OK) ed_rec_ready_ = true;
+        if (rc == SBV_OK) {
+            std::vector<uint64_t> off(msgs.size() + 1, 0);
+            for (size_t i = 0; i < msgs.size(); ++i) off[i + 1] = off[i] + msgs[i].size();
+            std::vector<uint8_t> payload((size_t)off.back() + 1), sigs(64 * msgs.size()), ok(msgs.size());
+            for (size_t i = 0; i < msgs.size(); ++i) memcpy(payload.data() + off[i], msgs[i].data(), msgs[i].size());
+            rc = sbv_ed25519_sign_msgs(ed_rec_, 1, nullptr, payload.data(), off.data(), msgs.size(), sigs.data(), ok.data());
+            for (size_t i = 0; rc == SBV_OK && i < msgs.size(); ++i)
+                if (ok[i]) out[i] = bytes((const char*)&sigs[64 * i], 64);
+        }
+        if (rc != SBV_ENOTINIT) return out;          // SBV_ENOTINIT: the initialised device is not the default context's: the host signs
+    }
+    for (size_t i = 0; i < msgs.size(); ++i) out[i] = Sign(msgs[i]);
+    return out;
+}
 Signature Signer::SignProposal(const Proposal& proposal, const bytes& auxiliary_input) {    // view.go:481
     Signature s;
     s.id = id_;

@@ -282,12 +282,17 @@ class Signer {
     uint64_t id() const { return id_; }
     const uint8_t* public_key() const { return q_; }                        // 64 bytes Qx|Qy, or 32 bytes A_enc (+ 32 zero bytes)
     bytes Sign(const bytes& msg);                                           // DER over SHA-256(msg), or the 64-byte Ed25519 R|S
+    // one signature per message, equal to Sign of each; Ed25519 with a device initialised: one sbv_ed25519_sign_msgs call (verifier.cc)
+    std::vector<bytes> SignBatch(const std::vector<bytes>& msgs);
     Signature SignProposal(const Proposal& proposal, const bytes& auxiliary_input);
+    ~Signer() { volatile uint8_t* p = ed_rec_; for (int i = 0; i < 96; ++i) p[i] = 0; }
 
  private:
     uint64_t id_;
     Scheme scheme_;
     uint8_t d_[32], q_[64];
+    uint8_t ed_rec_[96] = {0};          // Ed25519: the expanded record of sbv_ed25519_expand_keys (a mod L | prefix | A_enc), from the first SignBatch on
+    bool ed_rec_ready_ = false;
 };
 
 // f = (n-1)/3, q = ceil((n+f+1)/2)   internal/bft/util.go:183-187

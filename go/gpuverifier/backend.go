@@ -80,6 +80,15 @@ type K256KeyRegistry interface {
 	WidenKeySecp256k1(slot int32)
 }
 
+// EdBatchSigner is the Ed25519 batch signer of a backend (sbv_ed25519_expand_keys + sbv_ed25519_sign_msgs: RFC 8032, so the
+// signatures equal crypto/ed25519.Sign's byte for byte): signature i = Ed25519(seeds[keyIndex[i]], msgs[i]) as R|S, 64 bytes;
+// ok[i] = false when the index is out of range.  It stands beside Backend.SignBatch as an optional interface, like the key
+// registries above, so that a Backend written before it needs no change; a backend without a device signer returns
+// ErrNoBatchSigner and the caller signs one by one with crypto/ed25519.  NOT constant-time on the device (include/sbv.h).
+type EdBatchSigner interface {
+	SignBatchEd25519(seeds [][32]byte, keyIndex []uint32, msgs [][]byte) (sigs [][64]byte, ok []bool, err error)
+}
+
 // ErrNoBatchSigner: the backend has no batch signing entry (the pure-Go backend).
 var ErrNoBatchSigner = errors.New("gpuverifier: backend has no batch signer")
 
@@ -127,6 +136,9 @@ func (cpuBackend) Verify(scheme Scheme, items []Item) ([]bool, error) {
 func (cpuBackend) RegisterKey(*ecdsa.PublicKey) int32 { return -1 }
 func (cpuBackend) WidenKey(int32)                      {}
 func (cpuBackend) SignBatch([][32]byte, []uint32, [][32]byte) ([][64]byte, []bool, error) {
+	return nil, nil, ErrNoBatchSigner
+}
+func (cpuBackend) SignBatchEd25519([][32]byte, []uint32, [][]byte) ([][64]byte, []bool, error) {
 	return nil, nil, ErrNoBatchSigner
 }
 func (cpuBackend) Close() {}

@@ -551,4 +551,47 @@ func (b *gpuBackend) SignBatch(keys [][32]byte, keyIndex []uint32, digests [][32
 	return sigs, ok, nil
 }
 
+// SignBatchEd25519: sbv_ed25519_expand_keys, then sbv_ed25519_sign_msgs under the records just expanded (RFC 8032 on the device;
+// not constant-time — see include/sbv.h).  The records are as secret as the seeds and are zeroed before returning.
+func (b *gpuBackend) SignBatchEd25519(seeds [][32]byte, keyIndex []uint32, msgs [][]byte) (sigs [][64]byte, ok []bool, err error) {
+	n := len(msgs)
+	if n == 0 || len(seeds) == 0 || len(keyIndex) != n {
+		return nil, nil, errors.New("gpuverifier: SignBatchEd25519 needs seeds and one key index per message")
+	}
+	sb := make([]byte, 32*len(seeds))
+	for i := range seeds {
+		copy(sb[32*i:], seeds[i][:])
+	}
+	expanded := make([]byte, 96*len(seeds))
+	packed, moff := packMsgs(func(i int) []byte { return msgs[i] }, n)
+	out := make([]byte, 64*n)
+	flags := make([]byte, n)
+	b.on(func() {
+		rc := C.sbv_ed25519_expand_keys(u8(sb), C.size_t(len(seeds)), u8(expanded), nil)
+		if rc == 0 {
+			rc = C.sbv_ed25519_sign_msgs(u8(expanded), C.uint32_t(len(seeds)), (*C.uint32_t)(unsafe.Pointer(&keyIndex[0])), u8(packed),
+				(*C.uint64_t)(unsafe.Pointer(&moff[0])), C.size_t(n), u8(out), u8(flags))
+		}
+		if rc != 0 {
+			err = lastError()
+		}
+	})
+	for i := range sb {
+		sb[i] = 0
+	}
+	for i := range expanded {
+		expanded[i] = 0
+	}
+	if err != nil {
+		return nil, nil, err
+	}
+	sigs = make([][64]byte, n)
+	ok = make([]bool, n)
+	for i := 0; i < n; i++ {
+		copy(sigs[i][:], out[64*i:64*i+64])
+		ok[i] = flags[i] != 0
+	}
+	return sigs, ok, nil
+}
+
 func (b *gpuBackend) Close() { close(b.jobs) }

@@ -3,6 +3,7 @@
 package gpuverifier
 
 import (
+	"crypto/ed25519"
 	"crypto/sha256"
 	"encoding/asn1"
 	"math/big"
@@ -12,7 +13,48 @@ import (
 // build with -tags sbv_loadgen contains, because sbv_p256_sign_batch is NOT constant-time (secret-indexed table lookups in
 // HBM, include/sbv.h): a consensus node's long-term key must not be able to reach it by accident, so the production Signer
 // has no such method.  For load generators and replay tools over throw-away keys.
-type LoadgenSigner struct{ Signer }
+//
+// Scheme selects the signer: SchemeP256 (the zero value) signs with Signer.Key; SchemeEd25519 signs with EdSeed, the 32-byte
+// RFC 8032 private key, through sbv_ed25519_expand_keys / sbv_ed25519_sign_msgs — just as little constant-time.
+type LoadgenSigner struct {
+	Signer
+	Scheme Scheme
+	EdSeed []byte
+}
+
+// signBatchEd25519: every message under EdSeed through the backend's EdBatchSigner; what the device did not sign (no such
+// backend, a fault) is signed by crypto/ed25519 — the same bytes, RFC 8032 being deterministic.
+func (s *LoadgenSigner) signBatchEd25519(be Backend, msgs [][]byte) [][]byte {
+	out := make([][]byte, len(msgs))
+	if len(s.EdSeed) != ed25519.SeedSize {
+		panic("gpuverifier: LoadgenSigner under SchemeEd25519 needs a 32-byte EdSeed")
+	}
+	if eb, has := be.(EdBatchSigner); has && len(msgs) > 0 {
+		var seed [32]byte
+		copy(seed[:], s.EdSeed)
+		sigs, ok, err := eb.SignBatchEd25519([][32]byte{seed}, make([]uint32, len(msgs)), msgs)
+		for i := range seed {
+			seed[i] = 0
+		}
+		if err == nil && len(sigs) == len(msgs) {
+			for i := range msgs {
+				if ok[i] {
+					out[i] = append([]byte(nil), sigs[i][:]...)
+				}
+			}
+		}
+	}
+	var key ed25519.PrivateKey
+	for i, m := range msgs {
+		if out[i] == nil {
+			if key == nil {
+				key = ed25519.NewKeyFromSeed(s.EdSeed)
+			}
+			out[i] = ed25519.Sign(key, m)
+		}
+	}
+	return out
+}
 
 // SignBatch is the batch form of Sign (a consensus node signs once per sequence and
 // has no use for it): every message is signed with this key through the backend's batch signer
@@ -20,6 +62,9 @@ type LoadgenSigner struct{ Signer }
 // unusable key sends the affected messages through Sign.  Counterpart: consensus_amd/host (Signer over p256_host.cc) and
 // the device entry it is tested against (tests/test_gpu_sign.py).
 func (s *LoadgenSigner) SignBatch(be Backend, msgs [][]byte) [][]byte {
+	if s.Scheme == SchemeEd25519 {
+		return s.signBatchEd25519(be, msgs)
+	}
 	out := make([][]byte, len(msgs))
 	if be != nil && len(msgs) > 0 && s.Key != nil && s.Key.D != nil && s.Key.D.Sign() > 0 && s.Key.D.BitLen() <= 256 {
 		var key [32]byte

@@ -178,6 +178,45 @@ int sbv_p256_sign_batch(const uint8_t* keys, uint32_t n_keys, const uint32_t* ke
 int sbv_p256_sign_batch_dev(const void* d_keys, uint32_t n_keys, const void* d_key_index, const void* d_digests, size_t n,
                             void* d_sigs, void* d_ok, void* hip_stream);
 
+/* Ed25519 batch signing (RFC 8032 section 5.1.6, pure Ed25519): the batch form of api.Signer.Sign for the Ed25519 variant, in two
+ * steps so that a key is expanded once and not once per signature.  Signatures and public keys are byte-identical to RFC 8032,
+ * Go's crypto/ed25519 and consensus_amd/host's Signer (the scheme is deterministic: tests compare every byte).
+ *   sbv_ed25519_expand_keys   seeds: m x 32 bytes (the RFC 8032 private key).  expanded: m x 96 bytes, one EXPANDED RECORD per key:
+ *                                 bytes  0..31  a mod L   the clamped secret scalar, reduced mod the group order L, little-endian
+ *                                 bytes 32..63  prefix    the upper half of SHA-512(seed)
+ *                                 bytes 64..95  A_enc     the public key
+ *                             (a mod L and not a: the comb walker takes scalars below 2^253; B has order L, so [a mod L]B = A and
+ *                             S = r + k (a mod L) mod L is the same S.)  pks: m x 32 bytes, or NULL when only the records are wanted.
+ *                             A record is as secret as its seed.
+ *   sbv_ed25519_sign_msgs     signature i = Ed25519(expanded[key_index[i]], msgs[msg_offsets[i] .. msg_offsets[i+1])); key_index == NULL
+ *                             means key i % n_keys.  sigs: n x 64 bytes R | S; ok[i] = 1, or 0 with 64 zero bytes where key_index[i] >=
+ *                             n_keys.  SBV_EINVAL: a null pointer (msgs may be null when every message is empty), n_keys == 0,
+ *                             n > 2^21, an offset table that does not start at 0 or that decreases (the rule of
+ *                             sbv_ed25519_verify_msgs).  n == 0 (m == 0) is SBV_OK and writes nothing.
+ * The host-pointer forms use device buffers of the call's own size, wait for the result and zero the device copies of seeds and
+ * records before they free them.
+ * The `_stream` forms take device pointers (d_seeds, d_expanded, d_pks, d_key_index, d_sigs: 4-byte aligned; d_msg_offsets: n + 1
+ * uint64, 8-byte aligned), launch on `hip_stream` and return without synchronising, under the stream contract of the `_dev` entries
+ * above for every buffer they name.  They own no mutable device state — two calls on two streams share
+ * nothing but the read-only comb of B, uploaded on the first Ed25519 call of the process — and they read only `hip_stream`-ordered
+ * inputs, so nothing has to be joined back.  The device cannot refuse a whole call: a lane whose offset pair decreases answers
+ * ok[i] = 0 and 64 zero bytes and reads nothing of the messages, like a lane with an unknown key; offsets beyond the message
+ * buffer are the caller's error.  They are named `_stream` and not `_dev` because the schedules every `_dev` entry is run under are
+ * a fixed table in tests/test_gpu_stream_order.py; the schedules of these two (late producer, early overwriter, X-Y-X) are in
+ * tests/test_gpu_ed25519_sign.py.
+ * NOT constant-time: the comb of B is indexed by digits of the secret scalars a and r and lives in HBM.  For load generation, test
+ * traffic and trusted single-tenant hosts; see consensus_amd/csrc/ed25519_sign.h. */
+int sbv_ed25519_expand_keys(const uint8_t* seeds, size_t m, uint8_t* expanded, uint8_t* pks);
+int sbv_ed25519_sign_msgs(const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs,
+                          const uint64_t* msg_offsets, size_t n, uint8_t* sigs, uint8_t* ok);
+int sbv_ed25519_expand_keys_stream(const void* d_seeds, size_t m, void* d_expanded, void* d_pks, void* hip_stream);
+int sbv_ed25519_sign_msgs_stream(const void* d_expanded, uint32_t n_keys, const void* d_key_index, const void* d_msgs,
+                                 const void* d_msg_offsets, size_t n, void* d_sigs, void* d_ok, void* hip_stream);
+/* Test only: one case of a unit operation of the signer per lane on the device, host pointers, 32 bytes out per case.
+ * op 0: sc25519_muladd, in = k | a | r (96 bytes, each < L) -> (k a + r) mod L;  op 1: sc25519_reduce256, in = 32 bytes -> mod L;
+ * op 2: in = a scalar s < L -> encode([s]B) through the comb walker and ed_encode.  Any other op is SBV_EINVAL. */
+int sbv_debug_ed25519_sign_op(int op, const uint8_t* in, uint8_t* out, size_t n);
+
 /* Message front end on the device: SHA-256 of each message and the strict DER
  * parse of each signature run as a kernel in front of the registered-key verification, so the host
  * only concatenates bytes.  msg i = msgs[msg_offsets[i] .. msg_offsets[i+1]), signature i (ASN.1 DER,
