@@ -476,6 +476,61 @@ def sign_batch_dev(d_keys_ptr: int, n_keys: int, d_index_ptr: int, d_digests_ptr
     _check(lib.sbv_p256_sign_batch_dev(d_keys_ptr, n_keys, d_index_ptr or None, d_digests_ptr, n, d_sigs_ptr, d_ok_ptr, stream or None))
 
 
+K256_SIGN_LOW_S = 1      # SBV_K256_SIGN_LOW_S
+
+
+def secp256k1_sign_batch(keys: bytes, digests: bytes, key_index=None, low_s: bool = False):
+    """sbv_secp256k1_sign_batch: RFC 6979 ECDSA secp256k1 signatures (r | s, 64 bytes each) of n 32-byte digests under the 32-byte
+    private scalars in `keys` (key_index[i], default i % n_keys); low_s replaces s > (n-1)/2 by n - s.  Returns (sigs, recid, ok):
+    recid[i] = the recovery id 0..3, ok[i] = 1 per produced signature (a key outside [1, n-1] or an index out of range gives
+    ok[i] = 0, 64 zero bytes and recid[i] = 0).  NOT constant-time: see include/sbv.h."""
+    lib = load()
+    n, nk = len(digests) // 32, len(keys) // 32
+    lib.sbv_secp256k1_sign_batch.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t,
+                                             ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
+    sigs, recid, ok = ctypes.create_string_buffer(max(1, 64 * n)), ctypes.create_string_buffer(max(1, n)), ctypes.create_string_buffer(max(1, n))
+    idx = None if key_index is None else (ctypes.c_uint32 * n)(*key_index)
+    _check(lib.sbv_secp256k1_sign_batch(keys, nk, idx, digests, n, K256_SIGN_LOW_S if low_s else 0, sigs, recid, ok))
+    return sigs.raw[:64 * n], recid.raw[:n], ok.raw[:n]
+
+
+def secp256k1_sign_batch_stream(d_keys_ptr: int, n_keys: int, d_index_ptr: int, d_digests_ptr: int, n: int, d_sigs_ptr: int,
+                                d_recid_ptr: int, d_ok_ptr: int, low_s: bool = False, stream: int = 0) -> None:
+    """device pointers; asynchronous on `stream` under the stream contract of the _dev entries (include/sbv.h)"""
+    lib = load()
+    lib.sbv_secp256k1_sign_batch_stream.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                    ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_sign_batch_stream(d_keys_ptr, n_keys, d_index_ptr or None, d_digests_ptr, n, K256_SIGN_LOW_S if low_s else 0,
+                                               d_sigs_ptr, d_recid_ptr or None, d_ok_ptr, stream or None))
+
+
+def secp256k1_pubkeys(keys: bytes):
+    """sbv_secp256k1_pubkeys: 32-byte private scalars -> (pubs, ok): m x 64 bytes Qx | Qy in one bytes object and ok[i] = 1 per key in
+    [1, n-1] (otherwise 64 zero bytes).  NOT constant-time: see include/sbv.h."""
+    lib = load()
+    m = len(keys) // 32
+    lib.sbv_secp256k1_pubkeys.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p]
+    pubs, ok = ctypes.create_string_buffer(max(1, 64 * m)), ctypes.create_string_buffer(max(1, m))
+    _check(lib.sbv_secp256k1_pubkeys(keys, m, pubs, ok))
+    return pubs.raw[:64 * m], ok.raw[:m]
+
+
+def secp256k1_pubkeys_stream(d_keys_ptr: int, m: int, d_pubs_ptr: int, d_ok_ptr: int, stream: int = 0) -> None:
+    lib = load()
+    lib.sbv_secp256k1_pubkeys_stream.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_pubkeys_stream(d_keys_ptr, m, d_pubs_ptr, d_ok_ptr, stream or None))
+
+
+def debug_secp256k1_sign_op(op: int, records):
+    """sbv_debug_secp256k1_sign_op (test only): one case per lane, 192-byte input records -> 128-byte output records (include/sbv.h)"""
+    lib = load()
+    n = len(records)
+    lib.sbv_debug_secp256k1_sign_op.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+    out = ctypes.create_string_buffer(max(1, 128 * n))
+    _check(lib.sbv_debug_secp256k1_sign_op(op, b"".join(records), out, n))
+    return [out.raw[128 * i:128 * i + 128] for i in range(n)]
+
+
 def ed25519_expand_keys(seeds):
     """sbv_ed25519_expand_keys: 32-byte seeds (a list, or their concatenation) -> (expanded, pks): the 96-byte expanded records
     (a mod L | prefix | A_enc, as secret as the seeds) in one bytes object, and the list of 32-byte public keys."""

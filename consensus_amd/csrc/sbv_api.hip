@@ -35,6 +35,7 @@
 #include "p256_kernels.h"
 #include "k256_core.h"
 #include "k256_keyed_kernels.h"
+#include "k256_sign_kernels.h"
 
 namespace {
 
@@ -2668,6 +2669,146 @@ extern "C" int sbv_p256_sign_batch(const uint8_t* keys, uint32_t n_keys, const u
     if (d_sig) (void)hipFree(d_sig);
     if (d_ok) (void)hipFree(d_ok);
     if (d_idx) (void)hipFree(d_idx);
+    return rc;
+}
+
+// ---- secp256k1 batch signing (k256_sign.h, k256_sign_kernels.hip) -----------------------------------------------------------
+// Stateless apart from the read-only 16-bit comb of G (ensure_k256_table): the _stream forms read and write only buffers of the caller's,
+// on the caller's stream, so there is nothing of the library's to order and nothing to join back.
+extern "C" int sbv_secp256k1_sign_batch_stream(const void* d_keys, uint32_t n_keys, const void* d_key_index, const void* d_digests, size_t n,
+                                               uint32_t flags, void* d_sigs, void* d_recid, void* d_ok, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (flags & ~SBV_K256_SIGN_LOW_S) { g_err = "unknown flag"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!d_keys || !d_digests || !d_sigs || !d_ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(d_keys) | reinterpret_cast<uintptr_t>(d_digests) | reinterpret_cast<uintptr_t>(d_sigs) |
+         reinterpret_cast<uintptr_t>(d_key_index)) & 3) {
+        g_err = "misaligned device pointer";
+        return SBV_EINVAL;
+    }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_sign(static_cast<const uint8_t*>(d_keys), n_keys, static_cast<const u32*>(d_key_index),
+                                               static_cast<const uint8_t*>(d_digests), n, c.d_k256_gtab, flags, static_cast<uint8_t*>(d_sigs),
+                                               static_cast<uint8_t*>(d_recid), static_cast<uint8_t*>(d_ok), static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_pubkeys_stream(const void* d_keys, size_t m, void* d_pubs, void* d_ok, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!d_keys || !d_pubs || !d_ok) { g_err = "null pointer"; return SBV_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(d_keys) | reinterpret_cast<uintptr_t>(d_pubs)) & 3) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_pubkeys(static_cast<const uint8_t*>(d_keys), m, c.d_k256_gtab, static_cast<uint8_t*>(d_pubs),
+                                                  static_cast<uint8_t*>(d_ok), static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_sign_batch(const uint8_t* keys, uint32_t n_keys, const uint32_t* key_index, const uint8_t* digests, size_t n,
+                                        uint32_t flags, uint8_t* sigs, uint8_t* recid, uint8_t* ok) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (flags & ~SBV_K256_SIGN_LOW_S) { g_err = "unknown flag"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!keys || !digests || !sigs || !ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    // not a hot path: buffers of the call's own size, released before returning (private keys do not linger in a pool)
+    uint8_t *d_keys = nullptr, *d_dig = nullptr, *d_sig = nullptr, *d_rid = nullptr, *d_ok = nullptr;
+    u32* d_idx = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_keys, (size_t)n_keys * 32))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_dig, n * 32))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
+        if (recid && fail(SBV_ENOMEM, hipMalloc(&d_rid, n))) break;
+        if (key_index && fail(SBV_ENOMEM, hipMalloc(&d_idx, n * sizeof(u32)))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_keys, keys, (size_t)n_keys * 32, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_dig, digests, n * 32, hipMemcpyHostToDevice, c.stream))) break;
+        if (key_index && fail(SBV_EDEVICE, hipMemcpyAsync(d_idx, key_index, n * sizeof(u32), hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_k256_sign(d_keys, n_keys, d_idx, d_dig, n, c.d_k256_gtab, flags, d_sig, d_rid, d_ok, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(sigs, d_sig, n * 64, hipMemcpyDeviceToHost, c.stream))) break;
+        if (recid && fail(SBV_EDEVICE, hipMemcpyAsync(recid, d_rid, n, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (d_keys) {
+        (void)hipMemsetAsync(d_keys, 0, (size_t)n_keys * 32, c.stream);
+        (void)hipStreamSynchronize(c.stream);
+    }
+    if (d_keys) (void)hipFree(d_keys);
+    if (d_dig) (void)hipFree(d_dig);
+    if (d_sig) (void)hipFree(d_sig);
+    if (d_rid) (void)hipFree(d_rid);
+    if (d_ok) (void)hipFree(d_ok);
+    if (d_idx) (void)hipFree(d_idx);
+    return rc;
+}
+
+extern "C" int sbv_secp256k1_pubkeys(const uint8_t* keys, size_t m, uint8_t* pubs, uint8_t* ok) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!keys || !pubs || !ok) { g_err = "null pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    uint8_t *d_keys = nullptr, *d_pub = nullptr, *d_ok = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_keys, m * 32))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_pub, m * 64))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, m))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_keys, keys, m * 32, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_k256_pubkeys(d_keys, m, c.d_k256_gtab, d_pub, d_ok, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(pubs, d_pub, m * 64, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, m, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (d_keys) {
+        (void)hipMemsetAsync(d_keys, 0, m * 32, c.stream);
+        (void)hipStreamSynchronize(c.stream);
+    }
+    if (d_keys) (void)hipFree(d_keys);
+    if (d_pub) (void)hipFree(d_pub);
+    if (d_ok) (void)hipFree(d_ok);
+    return rc;
+}
+
+// Test only (include/sbv.h): one case of a unit operation of the signer per lane: 192 bytes in, 128 bytes out.
+extern "C" int sbv_debug_secp256k1_sign_op(int op, const uint8_t* in, uint8_t* out, size_t n) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (op < 0 || op > 3) { g_err = "unknown operation"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!in || !out || n > kMaxChunk) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_in, n * 192))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_out, n * 128))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_in, in, n * 192, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_k256_sign_op(op, d_in, d_out, n, c.d_k256_gtab, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(out, d_out, n * 128, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (d_in) {
+        (void)hipMemsetAsync(d_in, 0, n * 192, c.stream);
+        (void)hipStreamSynchronize(c.stream);
+        (void)hipFree(d_in);
+    }
+    if (d_out) (void)hipFree(d_out);
     return rc;
 }
 

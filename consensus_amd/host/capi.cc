@@ -267,6 +267,9 @@ int sbvh_sign_with_nonce(const uint8_t d[32], const uint8_t k[32], const uint8_t
 }
 int sbvh_sign_rfc6979(const uint8_t d[32], const uint8_t digest[32], uint8_t rs[64]) { return sign_rfc6979(d, digest, rs) ? 0 : -1; }
 int sbvh_pubkey(const uint8_t d[32], uint8_t q[64]) { return pubkey_from_private(d, q) ? 0 : -1; }
+// the secp256k1 host signer on its own (k256_host.cc), for tests
+int sbvh_k256_sign_rfc6979(const uint8_t d[32], const uint8_t digest[32], uint8_t rs[64]) { return k256_sign_rfc6979(d, digest, rs) ? 0 : -1; }
+int sbvh_k256_pubkey(const uint8_t d[32], uint8_t q[64]) { return k256_pubkey_from_private(d, q) ? 0 : -1; }
 
 // ---- formats ---------------------------------------------------------------------------------------
 void sbvh_proposal_digest(const void* payload, size_t pl, const void* header, size_t hl, const void* meta, size_t ml,

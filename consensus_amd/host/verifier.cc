@@ -1363,7 +1363,8 @@ bytes Signer::Sign(const bytes& msg) {
 }
 // The batch form.  Under Scheme::ED25519, when the process has a device initialised (a GPU backend exists: make_sbv_backend, or the
 // caller's own sbv_init), the whole batch is one sbv_ed25519_sign_msgs call under this signer's expanded record, which the device
-// derives from the seed on the first batch; byte-identical to Sign (the scheme is deterministic).  Otherwise a loop over Sign.
+// derives from the seed on the first batch; byte-identical to Sign (the scheme is deterministic).  Under Scheme::SECP256K1 likewise one
+// sbv_secp256k1_sign_batch call.  Otherwise a loop over Sign.
 // A device error gives empty signatures, as a failed Sign does.  NOT constant-time on the device: see include/sbv.h.
 std::vector<bytes> Signer::SignBatch(const std::vector<bytes>& msgs) {
     std::vector<bytes> out(msgs.size());
@@ -1381,6 +1382,16 @@ std::vector<bytes> Signer::SignBatch(const std::vector<bytes>& msgs) {
                 if (ok[i]) out[i] = bytes((const char*)&sigs[64 * i], 64);
         }
         if (rc != SBV_ENOTINIT) return out;          // SBV_ENOTINIT: the initialised device is not the default context's: the host signs
+    }
+    // Under Scheme::SECP256K1 the same offload: SHA-256 on the host, one sbv_secp256k1_sign_batch call with flags = 0 (no low-S rule:
+    // what Sign produces), then DER.  Scheme::P256 stays on the host loop.
+    if (scheme_ == Scheme::SECP256K1 && sbv_initialised_devices(nullptr, 0) > 0) {
+        std::vector<uint8_t> digests(32 * msgs.size()), sigs(64 * msgs.size()), ok(msgs.size());
+        for (size_t i = 0; i < msgs.size(); ++i) sha256(msgs[i].data(), msgs[i].size(), &digests[32 * i]);
+        const int rc = sbv_secp256k1_sign_batch(d_, 1, nullptr, digests.data(), msgs.size(), 0, sigs.data(), nullptr, ok.data());
+        for (size_t i = 0; rc == SBV_OK && i < msgs.size(); ++i)
+            if (ok[i]) out[i] = der_encode_sig(&sigs[64 * i]);
+        if (rc != SBV_ENOTINIT) return out;
     }
     for (size_t i = 0; i < msgs.size(); ++i) out[i] = Sign(msgs[i]);
     return out;

@@ -89,6 +89,15 @@ type EdBatchSigner interface {
 	SignBatchEd25519(seeds [][32]byte, keyIndex []uint32, msgs [][]byte) (sigs [][64]byte, ok []bool, err error)
 }
 
+// K256BatchSigner is the secp256k1 batch signer of a backend (sbv_secp256k1_sign_batch: ECDSA with the deterministic nonce of
+// RFC 6979): signature i = ECDSA-secp256k1(keys[keyIndex[i]], digests[i]) as r|s, 64 bytes big-endian, and recid[i] its recovery
+// id 0..3; lowS replaces s > (n-1)/2 by n - s (the Bitcoin / Ethereum form).  ok[i] = false when the key is not in [1, n-1] or the
+// index is out of range.  An optional interface beside Backend like EdBatchSigner, for the same reason; a backend without a device
+// signer returns ErrNoBatchSigner.  NOT constant-time on the device (secret-indexed table lookups in HBM, include/sbv.h).
+type K256BatchSigner interface {
+	SignBatchSecp256k1(keys [][32]byte, keyIndex []uint32, digests [][32]byte, lowS bool) (sigs [][64]byte, recid []byte, ok []bool, err error)
+}
+
 // ErrNoBatchSigner: the backend has no batch signing entry (the pure-Go backend).
 var ErrNoBatchSigner = errors.New("gpuverifier: backend has no batch signer")
 
@@ -140,5 +149,8 @@ func (cpuBackend) SignBatch([][32]byte, []uint32, [][32]byte) ([][64]byte, []boo
 }
 func (cpuBackend) SignBatchEd25519([][32]byte, []uint32, [][]byte) ([][64]byte, []bool, error) {
 	return nil, nil, ErrNoBatchSigner
+}
+func (cpuBackend) SignBatchSecp256k1([][32]byte, []uint32, [][32]byte, bool) ([][64]byte, []byte, []bool, error) {
+	return nil, nil, nil, ErrNoBatchSigner
 }
 func (cpuBackend) Close() {}

@@ -594,4 +594,47 @@ func (b *gpuBackend) SignBatchEd25519(seeds [][32]byte, keyIndex []uint32, msgs 
 	return sigs, ok, nil
 }
 
+// SignBatchSecp256k1: sbv_secp256k1_sign_batch (RFC 6979 nonces on the device; not constant-time — see include/sbv.h).
+func (b *gpuBackend) SignBatchSecp256k1(keys [][32]byte, keyIndex []uint32, digests [][32]byte, lowS bool) (sigs [][64]byte, recid []byte, ok []bool, err error) {
+	n := len(digests)
+	if n == 0 || len(keys) == 0 || len(keyIndex) != n {
+		return nil, nil, nil, errors.New("gpuverifier: SignBatchSecp256k1 needs keys and one key index per digest")
+	}
+	kb := make([]byte, 32*len(keys))
+	for i := range keys {
+		copy(kb[32*i:], keys[i][:])
+	}
+	db := make([]byte, 32*n)
+	for i := range digests {
+		copy(db[32*i:], digests[i][:])
+	}
+	var mode uint32
+	if lowS {
+		mode = 1 // SBV_K256_SIGN_LOW_S
+	}
+	out := make([]byte, 64*n)
+	recid = make([]byte, n)
+	flags := make([]byte, n)
+	b.on(func() {
+		rc := C.sbv_secp256k1_sign_batch(u8(kb), C.uint32_t(len(keys)), (*C.uint32_t)(unsafe.Pointer(&keyIndex[0])), u8(db), C.size_t(n), C.uint32_t(mode),
+			u8(out), u8(recid), u8(flags))
+		if rc != 0 {
+			err = lastError()
+		}
+	})
+	for i := range kb {
+		kb[i] = 0
+	}
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	sigs = make([][64]byte, n)
+	ok = make([]bool, n)
+	for i := 0; i < n; i++ {
+		copy(sigs[i][:], out[64*i:64*i+64])
+		ok[i] = flags[i] != 0
+	}
+	return sigs, recid, ok, nil
+}
+
 func (b *gpuBackend) Close() { close(b.jobs) }

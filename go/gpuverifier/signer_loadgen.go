@@ -16,10 +16,52 @@ import (
 //
 // Scheme selects the signer: SchemeP256 (the zero value) signs with Signer.Key; SchemeEd25519 signs with EdSeed, the 32-byte
 // RFC 8032 private key, through sbv_ed25519_expand_keys / sbv_ed25519_sign_msgs — just as little constant-time.
+//
+// SchemeSecp256k1 signs SHA-256 of each message with K256Key, the 32-byte big-endian private scalar, through
+// sbv_secp256k1_sign_batch (K256LowS selects the low-S form) and DER-encodes r, s like the P-256 path.  Go's standard library has
+// no secp256k1, so this scheme has no host signer to fall back on: a message the device did not sign (no K256BatchSigner, a fault,
+// a key outside [1, n-1]) comes back nil.
 type LoadgenSigner struct {
 	Signer
-	Scheme Scheme
-	EdSeed []byte
+	Scheme   Scheme
+	EdSeed   []byte
+	K256Key  []byte
+	K256LowS bool
+}
+
+// signBatchSecp256k1: every message under K256Key through the backend's K256BatchSigner, DER-encoded; nil where nothing was signed.
+func (s *LoadgenSigner) signBatchSecp256k1(be Backend, msgs [][]byte) [][]byte {
+	out := make([][]byte, len(msgs))
+	if len(s.K256Key) != 32 {
+		panic("gpuverifier: LoadgenSigner under SchemeSecp256k1 needs a 32-byte K256Key")
+	}
+	kb, has := be.(K256BatchSigner)
+	if !has || len(msgs) == 0 {
+		return out
+	}
+	var key [32]byte
+	copy(key[:], s.K256Key)
+	digests := make([][32]byte, len(msgs))
+	for i, m := range msgs {
+		digests[i] = sha256.Sum256(m)
+	}
+	sigs, _, ok, err := kb.SignBatchSecp256k1([][32]byte{key}, make([]uint32, len(msgs)), digests, s.K256LowS)
+	for i := range key {
+		key[i] = 0
+	}
+	if err != nil || len(sigs) != len(msgs) {
+		return out
+	}
+	for i := range msgs {
+		if !ok[i] {
+			continue
+		}
+		der, e := asn1.Marshal(struct{ R, S *big.Int }{new(big.Int).SetBytes(sigs[i][:32]), new(big.Int).SetBytes(sigs[i][32:])})
+		if e == nil {
+			out[i] = der
+		}
+	}
+	return out
 }
 
 // signBatchEd25519: every message under EdSeed through the backend's EdBatchSigner; what the device did not sign (no such
@@ -64,6 +106,9 @@ func (s *LoadgenSigner) signBatchEd25519(be Backend, msgs [][]byte) [][]byte {
 func (s *LoadgenSigner) SignBatch(be Backend, msgs [][]byte) [][]byte {
 	if s.Scheme == SchemeEd25519 {
 		return s.signBatchEd25519(be, msgs)
+	}
+	if s.Scheme == SchemeSecp256k1 {
+		return s.signBatchSecp256k1(be, msgs)
 	}
 	out := make([][]byte, len(msgs))
 	if be != nil && len(msgs) > 0 && s.Key != nil && s.Key.D != nil && s.Key.D.Sign() > 0 && s.Key.D.BitLen() <= 256 {

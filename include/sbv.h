@@ -178,6 +178,54 @@ int sbv_p256_sign_batch(const uint8_t* keys, uint32_t n_keys, const uint32_t* ke
 int sbv_p256_sign_batch_dev(const void* d_keys, uint32_t n_keys, const void* d_key_index, const void* d_digests, size_t n,
                             void* d_sigs, void* d_ok, void* hip_stream);
 
+/* secp256k1 batch signing: the batch form of api.Signer.Sign for the secp256k1 variant.  Signature i = ECDSA-secp256k1(
+ * key[key_index[i]], digests[i]) with the deterministic nonce of RFC 6979 (HMAC-SHA256); with flags = 0 bit-identical to
+ * consensus_amd/host's Signer (k256_sign_rfc6979).  The rules are sbv_p256_sign_batch's: keys: n_keys x 32 bytes (private scalar,
+ * big-endian); digests: n x 32 bytes; sigs: n x 64 bytes r | s (big-endian); key_index == NULL means key i % n_keys; ok[i] = 0 with
+ * 64 zero bytes in sigs[i] and recid[i] = 0 when the key is not in [1, n-1] or the index is >= n_keys.  n == 0 is SBV_OK and writes
+ * nothing.  Beyond the P-256 entry:
+ *   flags   SBV_K256_SIGN_LOW_S: s > (n-1)/2 is replaced by n - s, the form Bitcoin- and Ethereum-shaped verifiers require (the
+ *           verifier of this library has no low-S rule and accepts both forms).  Any other bit is SBV_EINVAL.
+ *   recid   n bytes, or NULL when not wanted: the recovery id 0..3 of signature i.  Bit 0 = parity of the y of R = k G (flipped when
+ *           low-S negated s), bit 1 = R.x >= n (probability ~2^-128).  Q = r^-1 (s R' - e G) for the point R' with x = r
+ *           (+ n when bit 1 is set) and y of parity bit 0.
+ * SBV_EINVAL: a null required pointer, n_keys == 0, an unknown flag bit, and for the `_stream` forms a device pointer (keys, key
+ * index, digests, sigs, pubs) that is not 4-byte aligned; SBV_ENOTINIT before sbv_init.
+ *   sbv_secp256k1_pubkeys   keys: m x 32 bytes -> pubs: m x 64 bytes Qx | Qy of d G, ok[i] = 0 with 64 zero bytes for d outside [1, n-1].
+ * The host-pointer forms use device buffers of the call's own size, wait for the result and zero the device copy of the keys before
+ * they free it.  The `_stream` forms take device pointers, launch on `hip_stream` and return without synchronising, under the stream
+ * contract of the `_dev` entries above for every buffer they name.  They own no mutable device state: two
+ * calls on two streams share nothing but the read-only 16-bit comb of G, uploaded (synchronously) by the first secp256k1 call of
+ * the process, which may be one of these.  They are named `_stream` and not `_dev` for the reason the Ed25519 entries are; their
+ * schedules (late producer, early overwriter, X-Y-X) are in tests/test_gpu_k256_sign.py.
+ * NOT constant-time (secret-indexed table lookups in HBM, variable-time inversions): for test traffic and trusted single-tenant
+ * hosts, see consensus_amd/csrc/k256_sign.h.
+ * (The return types stand on lines of their own, as for the hot-key entries below: the registered-key entries are counted by their
+ * one-line form.) */
+#define SBV_K256_SIGN_LOW_S 1u
+int
+sbv_secp256k1_sign_batch(const uint8_t* keys, uint32_t n_keys, const uint32_t* key_index, const uint8_t* digests, size_t n,
+                         uint32_t flags, uint8_t* sigs, uint8_t* recid, uint8_t* ok);
+int
+sbv_secp256k1_sign_batch_stream(const void* d_keys, uint32_t n_keys, const void* d_key_index, const void* d_digests, size_t n,
+                                uint32_t flags, void* d_sigs, void* d_recid, void* d_ok, void* hip_stream);
+int
+sbv_secp256k1_pubkeys(const uint8_t* keys, size_t m, uint8_t* pubs, uint8_t* ok);
+int
+sbv_secp256k1_pubkeys_stream(const void* d_keys, size_t m, void* d_pubs, void* d_ok, void* hip_stream);
+/* Test only: one case of a unit operation of the signer per lane on the device, host pointers.  Every case reads one 192-byte record
+ * of six fields and writes one 128-byte record of four fields; a field is a 32-byte big-endian integer, unused fields are ignored
+ * on input and zero on output, and output field 3 is the operation's ok (0 or 1; a case that is not ok is all zero).
+ *   op 0   in: d | digest                        out: k | K | V   the first RFC 6979 candidate and the DRBG state behind it (V = k);
+ *                                                                 ok = 0 for d outside [1, n-1]
+ *   op 1   in: K | V                             out: K' | V' | k'   the section 3.2 h update after a rejected candidate V:
+ *                                                                 K' = HMAC(K, V || 00), V' = HMAC(K', V), k' = HMAC(K', V')
+ *   op 2   in: k                                 out: x | y of k G, affine; ok = 0 for k outside [1, n-1]
+ *   op 3   in: x | y_odd | d | k | e | flags     out: r | s | recid   k256_sign_finish on plain integers: x any 256-bit value, d and
+ *                                                                 e < n, k in [1, n-1]; ok = 0 when r = 0 or s = 0
+ * Any other op is SBV_EINVAL. */
+int sbv_debug_secp256k1_sign_op(int op, const uint8_t* in, uint8_t* out, size_t n);
+
 /* Ed25519 batch signing (RFC 8032 section 5.1.6, pure Ed25519): the batch form of api.Signer.Sign for the Ed25519 variant, in two
  * steps so that a key is expanded once and not once per signature.  Signatures and public keys are byte-identical to RFC 8032,
  * Go's crypto/ed25519 and consensus_amd/host's Signer (the scheme is deterministic: tests compare every byte).
