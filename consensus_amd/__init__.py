@@ -531,6 +531,55 @@ def debug_secp256k1_sign_op(op: int, records):
     return [out.raw[128 * i:128 * i + 128] for i in range(n)]
 
 
+K256_RECOVER_LOW_S = 1   # SBV_K256_RECOVER_LOW_S
+
+
+def secp256k1_recover(sigs: bytes, recid: bytes, digests: bytes, low_s: bool = False):
+    """sbv_secp256k1_recover: the signers' public keys of n signatures (r | s, 64 bytes each) with their recovery ids (n bytes, 0..3) and
+    32-byte digests: exactly the arrays secp256k1_sign_batch returns.  Returns (pubs, ok): n x 64 bytes Qx | Qy in one bytes object and
+    ok[i] = 1 per recovered key; a refused input (include/sbv.h has the rules) gives ok[i] = 0 and 64 zero bytes.  low_s also refuses
+    s > (n-1)/2."""
+    lib = load()
+    n = len(recid)
+    if len(sigs) != 64 * n or len(digests) != 32 * n:
+        raise ValueError("secp256k1_recover: sigs, recid and digests disagree about n")
+    lib.sbv_secp256k1_recover.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32,
+                                          ctypes.c_char_p, ctypes.c_char_p]
+    pubs, ok = ctypes.create_string_buffer(max(1, 64 * n)), ctypes.create_string_buffer(max(1, n))
+    _check(lib.sbv_secp256k1_recover(bytes(sigs), bytes(recid), bytes(digests), n, K256_RECOVER_LOW_S if low_s else 0, pubs, ok))
+    return pubs.raw[:64 * n], ok.raw[:n]
+
+
+def secp256k1_recover_workspace(n: int) -> int:
+    """sbv_secp256k1_recover_workspace: the bytes of device workspace secp256k1_recover_stream needs for n signatures"""
+    lib = load()
+    lib.sbv_secp256k1_recover_workspace.argtypes = [ctypes.c_size_t]
+    lib.sbv_secp256k1_recover_workspace.restype = ctypes.c_size_t
+    return int(lib.sbv_secp256k1_recover_workspace(n))
+
+
+def secp256k1_recover_stream(d_sigs_ptr: int, d_recid_ptr: int, d_digests_ptr: int, n: int, d_pubs_ptr: int, d_ok_ptr: int,
+                             d_work_ptr: int, work_bytes: int, low_s: bool = False, stream: int = 0, flags=None) -> None:
+    """device pointers and the caller's workspace (16-byte aligned, secp256k1_recover_workspace(n) bytes); asynchronous on `stream`
+    under the stream contract of the _dev entries (include/sbv.h).  `flags` overrides low_s with a raw flag word."""
+    lib = load()
+    lib.sbv_secp256k1_recover_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    f = (K256_RECOVER_LOW_S if low_s else 0) if flags is None else flags
+    _check(lib.sbv_secp256k1_recover_stream(d_sigs_ptr or None, d_recid_ptr or None, d_digests_ptr or None, n, f, d_pubs_ptr or None,
+                                            d_ok_ptr or None, d_work_ptr or None, work_bytes, stream or None))
+
+
+def debug_secp256k1_recover_op(op: int, records):
+    """sbv_debug_secp256k1_recover_op (test only): one case per lane, 192-byte input records -> 128-byte output records (include/sbv.h)"""
+    lib = load()
+    n = len(records)
+    lib.sbv_debug_secp256k1_recover_op.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+    out = ctypes.create_string_buffer(max(1, 128 * n))
+    _check(lib.sbv_debug_secp256k1_recover_op(op, b"".join(records), out, n))
+    return [out.raw[128 * i:128 * i + 128] for i in range(n)]
+
+
 def ed25519_expand_keys(seeds):
     """sbv_ed25519_expand_keys: 32-byte seeds (a list, or their concatenation) -> (expanded, pks): the 96-byte expanded records
     (a mod L | prefix | A_enc, as secret as the seeds) in one bytes object, and the list of 32-byte public keys."""

@@ -36,6 +36,7 @@
 #include "k256_core.h"
 #include "k256_keyed_kernels.h"
 #include "k256_sign_kernels.h"
+#include "k256_recover_kernels.h"
 
 namespace {
 
@@ -2809,6 +2810,104 @@ extern "C" int sbv_debug_secp256k1_sign_op(int op, const uint8_t* in, uint8_t* o
         (void)hipFree(d_in);
     }
     if (d_out) (void)hipFree(d_out);
+    return rc;
+}
+
+// ---- secp256k1 public-key recovery (k256_recover.h, k256_recover_kernels.hip) --------------------------------------------------
+// Stateless apart from the read-only 16-bit comb of G (ensure_k256_table): the _stream form reads and writes only buffers of the
+// caller's, the workspace of table strips included, on the caller's stream: nothing of the library's to order, nothing to join back.
+extern "C" size_t sbv_secp256k1_recover_workspace(size_t n) {
+    const size_t lanes = n < (size_t)SBV_K256_RECOVER_LANES ? n : (size_t)SBV_K256_RECOVER_LANES;
+    return lanes * sbv::k256_recover_strip_bytes();
+}
+
+extern "C" int sbv_secp256k1_recover_stream(const void* d_sigs, const void* d_recid, const void* d_digests, size_t n, uint32_t flags, void* d_pubs,
+                                            void* d_ok, void* d_work, size_t work_bytes, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (flags & ~SBV_K256_RECOVER_LOW_S) { g_err = "unknown flag"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!d_sigs || !d_recid || !d_digests || !d_pubs || !d_ok || !d_work) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (((reinterpret_cast<uintptr_t>(d_sigs) | reinterpret_cast<uintptr_t>(d_digests) | reinterpret_cast<uintptr_t>(d_pubs)) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_work) & 15)) {
+        g_err = "misaligned device pointer";
+        return SBV_EINVAL;
+    }
+    if (work_bytes < sbv_secp256k1_recover_workspace(n)) { g_err = "workspace too small"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_recover(static_cast<const uint8_t*>(d_sigs), static_cast<const uint8_t*>(d_recid),
+                                                  static_cast<const uint8_t*>(d_digests), n, flags, c.d_k256_gtab, static_cast<u32*>(d_work),
+                                                  static_cast<uint8_t*>(d_pubs), static_cast<uint8_t*>(d_ok), static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_recover(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint32_t flags, uint8_t* pubs,
+                                     uint8_t* ok) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (flags & ~SBV_K256_RECOVER_LOW_S) { g_err = "unknown flag"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!sigs || !recid || !digests || !pubs || !ok) { g_err = "null pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    // not a hot path: buffers and a workspace of the call's own size, released before returning
+    uint8_t *d_sig = nullptr, *d_rid = nullptr, *d_dig = nullptr, *d_pub = nullptr, *d_ok = nullptr;
+    u32* d_work = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_rid, n))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_dig, n * 32))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_pub, n * 64))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_work, sbv_secp256k1_recover_workspace(n)))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_sig, sigs, n * 64, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_rid, recid, n, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_dig, digests, n * 32, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_k256_recover(d_sig, d_rid, d_dig, n, flags, c.d_k256_gtab, d_work, d_pub, d_ok, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(pubs, d_pub, n * 64, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);       // nothing of this call is in flight when its buffers go
+    if (d_sig) (void)hipFree(d_sig);
+    if (d_rid) (void)hipFree(d_rid);
+    if (d_dig) (void)hipFree(d_dig);
+    if (d_pub) (void)hipFree(d_pub);
+    if (d_ok) (void)hipFree(d_ok);
+    if (d_work) (void)hipFree(d_work);
+    return rc;
+}
+
+// Test only (include/sbv.h): one case of a unit operation of the recovery per lane: 192 bytes in, 128 bytes out, one strip per case.
+extern "C" int sbv_debug_secp256k1_recover_op(int op, const uint8_t* in, uint8_t* out, size_t n) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (op < 0 || op > 2) { g_err = "unknown operation"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!in || !out || n > 65536) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    u32* d_work = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_in, n * 192))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_out, n * 128))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_work, n * sbv::k256_recover_strip_bytes()))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_in, in, n * 192, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_k256_recover_op(op, d_in, d_out, n, c.d_k256_gtab, d_work, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(out, d_out, n * 128, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (d_work) (void)hipFree(d_work);
     return rc;
 }
 

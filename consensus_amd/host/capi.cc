@@ -84,6 +84,10 @@ size_t sbvh_backend_last_k256_slots(void* h, uint32_t* out, size_t cap) {
     for (size_t i = 0; i < s.size() && i < cap; ++i) out[i] = s[i];
     return s.size();
 }
+// Verifier::RecoverSigners: n x 65 bytes r | s | v + n x 32 bytes -> n x 64 bytes + n bytes; returns the status code
+int sbvh_recover_signers(void* h, const uint8_t* sigs65, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) {
+    return ((VHandle*)h)->v->RecoverSigners(sigs65, digests, n, pubs, ok).code;
+}
 void sbvh_register_consenter(void* h, uint64_t id, const uint8_t q[64]) { ((VHandle*)h)->v->RegisterConsenter(id, q); }
 void sbvh_register_client(void* h, const char* client, const uint8_t q[64]) { ((VHandle*)h)->v->RegisterClient(client, q); }
 // 0: clients registered from now on get no comb slot on the device (their request signatures go as generic tuples)
@@ -270,6 +274,8 @@ int sbvh_pubkey(const uint8_t d[32], uint8_t q[64]) { return pubkey_from_private
 // the secp256k1 host signer on its own (k256_host.cc), for tests
 int sbvh_k256_sign_rfc6979(const uint8_t d[32], const uint8_t digest[32], uint8_t rs[64]) { return k256_sign_rfc6979(d, digest, rs) ? 0 : -1; }
 int sbvh_k256_pubkey(const uint8_t d[32], uint8_t q[64]) { return k256_pubkey_from_private(d, q) ? 0 : -1; }
+// the secp256k1 host recovery on its own (k256_host.cc): 0 and the key, or -1 and 64 zero bytes
+int sbvh_k256_recover(const uint8_t rs[64], uint8_t recid, const uint8_t digest[32], uint8_t q[64]) { return k256_recover(rs, recid, digest, q) ? 0 : -1; }
 
 // ---- formats ---------------------------------------------------------------------------------------
 void sbvh_proposal_digest(const void* payload, size_t pl, const void* header, size_t hl, const void* meta, size_t ml,

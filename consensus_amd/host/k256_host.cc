@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../csrc/k256_core.h"
+#include "../csrc/k256_recover.h"
 #include "p256_host.h"
 
 namespace sbvhost {
@@ -36,13 +37,11 @@ const kapt* gtable8() {
     return tab.data();
 }
 
-// affine k * G, k in [1, n - 1]: 33 exact mixed additions from the comb (k + 0x80..80: byte j minus 128 is the digit of window j)
-void base_mul_affine(const u256& k, u256& x, u256& y) {
+// R += k * G, k < n: 33 exact mixed additions from the comb (k + 0x80..80: byte j minus 128 is the digit of window j)
+void comb8_add(kjpt& R, const u256& k) {
     const kapt* gt = gtable8();
     u256 kk;
     const u32 top = add_const_limbs(kk, k, 0x80808080u);
-    kjpt R;
-    kpt_set_inf(R);
     for (int j = 0; j < 33; ++j) {
         int idx; bool neg, skip;
         comb_digit(kk, top, j, idx, neg, skip);
@@ -50,6 +49,13 @@ void base_mul_affine(const u256& k, u256& x, u256& y) {
         kapt_load(ex, ey, gt + (size_t)j * 128 + idx);
         kpt_madd(R, R, ex, ey, neg, skip);
     }
+}
+
+// affine k * G, k in [1, n - 1]
+void base_mul_affine(const u256& k, u256& x, u256& y) {
+    kjpt R;
+    kpt_set_inf(R);
+    comb8_add(R, k);
     kfe zi, zi2, zi3, ax, ay;
     kfe_inv(zi, R.Z);
     kfe_sqr(zi2, zi);
@@ -136,6 +142,23 @@ bool k256_sign_rfc6979(const uint8_t d_be[32], const uint8_t digest[32], uint8_t
         hmac_sha256(K, m, K);
         hmac_sha256(K, bytes((const char*)V, 32), V);
     }
+}
+
+bool k256_recover(const uint8_t rs[64], uint8_t recid, const uint8_t digest[32], uint8_t q[64]) {
+    memset(q, 0, 64);
+    u32 rsw[16], h[8], qw[16];
+    for (int k = 0; k < 16; ++k) rsw[k] = ((u32)rs[4 * k] << 24) | ((u32)rs[4 * k + 1] << 16) | ((u32)rs[4 * k + 2] << 8) | rs[4 * k + 3];
+    for (int k = 0; k < 8; ++k) h[k] = ((u32)digest[4 * k] << 24) | ((u32)digest[4 * k + 1] << 16) | ((u32)digest[4 * k + 2] << 8) | digest[4 * k + 3];
+    kfe x, y;
+    u256 u1, u2;
+    if (!k256_recover_front(rsw, recid, h, 0, x, y, u1, u2)) return false;
+    alignas(16) u32 strip[SBV_K256_QTAB_WORDS];
+    kjpt Q;
+    k256_mul_u2Q(Q, x, y, u2, strip);              // u2 R'
+    comb8_add(Q, u1);                              // + u1 G
+    if (!k256_recover_finish(Q, qw)) return false;
+    for (int k = 0; k < 16; ++k) { q[4 * k] = (uint8_t)(qw[k] >> 24); q[4 * k + 1] = (uint8_t)(qw[k] >> 16); q[4 * k + 2] = (uint8_t)(qw[k] >> 8); q[4 * k + 3] = (uint8_t)qw[k]; }
+    return true;
 }
 
 }  // namespace sbvhost

@@ -7,5 +7,9 @@ namespace sbvhost {
 bool k256_pubkey_from_private(const uint8_t d_be[32], uint8_t q[64]);      // false: d = 0 or d >= n
 bool k256_sign_with_nonce(const uint8_t d_be[32], const uint8_t k_be[32], const uint8_t digest[32], uint8_t rs[64]);
 bool k256_sign_rfc6979(const uint8_t d_be[32], const uint8_t digest[32], uint8_t rs[64]);
+// the signer's public key from r | s, the recovery id 0..3 and the digest, by the rules of sbv_secp256k1_recover (include/sbv.h) with
+// flags = 0: the CPU form of the device entry, on the same lane functions (csrc/k256_recover.h) with u1 G from the signer's 8-bit comb.
+// false, and q zeroed, for a refused input.
+bool k256_recover(const uint8_t rs[64], uint8_t recid, const uint8_t digest[32], uint8_t q[64]);
 
 }  // namespace sbvhost

@@ -196,6 +196,10 @@ class SbvBackend : public Backend {
         if (n > ((size_t)1 << 21)) return -2;          // beyond the entry's limit: the caller takes the record path
         return sbv_secp256k1_verify_msgs_keyed(msgs, moff, sigs, soff, slots, n, bitmap);
     }
+    int recover_k256(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) override {
+        if (rc_ != SBV_OK) return rc_;
+        return sbv_secp256k1_recover(sigs, recid, digests, n, 0, pubs, ok);
+    }
     void* host_alloc(size_t bytes) override { return rc_ == SBV_OK ? sbv_host_alloc(bytes) : nullptr; }
     void host_free(void* p) override { sbv_host_free(p); }
     int verify_msgs_keyed(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff,
@@ -360,6 +364,13 @@ class CallbackBackend : public Backend {
         return verify_k256_keyed(rsh.data(), slots, n, bitmap);
     }
     std::vector<uint32_t> last_k256_slots() override { std::lock_guard<std::mutex> lk(mu_); return last_k256_slots_; }
+    // the CPU form: a loop over the host recovery (k256_host.cc), which needs no callback
+    int recover_k256(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) override {
+        parallel_chunks(n, [&](size_t lo, size_t hi) {
+            for (size_t i = lo; i < hi; ++i) ok[i] = k256_recover(sigs + 64 * i, recid[i], digests + 32 * i, pubs + 64 * i) ? 1 : 0;
+        });
+        return 0;
+    }
  private:
     std::vector<std::string> k256_keys_;
     std::vector<long> k256_widened_;
@@ -1366,6 +1377,22 @@ bytes Signer::Sign(const bytes& msg) {
 // derives from the seed on the first batch; byte-identical to Sign (the scheme is deterministic).  Under Scheme::SECP256K1 likewise one
 // sbv_secp256k1_sign_batch call.  Otherwise a loop over Sign.
 // A device error gives empty signatures, as a failed Sign does.  NOT constant-time on the device: see include/sbv.h.
+Status Verifier::RecoverSigners(const uint8_t* sigs65, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) {
+    if (!k256()) return Status::Invalid("RecoverSigners needs Scheme::SECP256K1");
+    if (n == 0) return Status::Ok();
+    // r | s | v -> r | s and the recovery id; a v outside 0..3 and 27..30 becomes 255, which every backend refuses
+    std::vector<uint8_t> sigs(64 * n), recid(n);
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(&sigs[64 * i], sigs65 + 65 * i, 64);
+        const uint8_t v = sigs65[65 * i + 64];
+        recid[i] = v <= 3 ? v : (v >= 27 && v <= 30 ? (uint8_t)(v - 27) : 255);
+    }
+    const int rc = co_.backend().recover_k256(sigs.data(), recid.data(), digests, n, pubs, ok);
+    if (rc == -2) return Status::Unavailable("the backend has no secp256k1 recovery");
+    if (rc != 0) return Status::Unavailable("secp256k1 recovery failed on the backend");
+    return Status::Ok();
+}
+
 std::vector<bytes> Signer::SignBatch(const std::vector<bytes>& msgs) {
     std::vector<bytes> out(msgs.size());
     if (msgs.empty()) return out;

@@ -86,6 +86,11 @@ class Backend {
                                        const uint32_t* slots, size_t n, uint8_t* bitmap) {
         (void)msgs; (void)moff; (void)sigs; (void)soff; (void)slots; (void)n; (void)bitmap; return -2;
     }
+    // secp256k1 public-key recovery (include/sbv.h: sbv_secp256k1_recover): n signatures r|s + recovery ids 0..3 + digests -> n keys
+    // Qx|Qy and ok[i] = 1 per recovered key (a refused input: 64 zero bytes); -2 when unsupported
+    virtual int recover_k256(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) {
+        (void)sigs; (void)recid; (void)digests; (void)n; (void)pubs; (void)ok; return -2;
+    }
     virtual int verify_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* bitmap) {
         (void)rsh; (void)slots; (void)n; (void)bitmap; return -2;
     }
@@ -225,6 +230,11 @@ class Verifier {
     // decisions in one backend call; out[i] = 1 accept / 0 reject.
     Status VerifyConsenterSigBatch(const std::vector<Signature>& sigs, const std::vector<const Proposal*>& props,
                                    std::vector<uint8_t>* out);
+    // Scheme::SECP256K1 only: the signers of n signatures that carry no key, as traffic shaped like Ethereum's does: sigs65 = n x 65
+    // bytes r | s | v with v = the recovery id as 0..3 or 27..30, digests = n x 32 bytes -> pubs n x 64 bytes Qx|Qy, ok[i] = 1 per
+    // recovered key (otherwise 64 zero bytes; any other v is refused).  One backend call (sbv_secp256k1_recover on the device); what an
+    // integrator calls before RegisterClient / register_key_k256.  INVALID under another scheme, UNAVAILABLE on a backend error.
+    Status RecoverSigners(const uint8_t* sigs65, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok);
     CoalescerStats stats() { return co_.stats(); }
     Scheme scheme() const { return opt_.scheme; }
 

@@ -98,6 +98,16 @@ type K256BatchSigner interface {
 	SignBatchSecp256k1(keys [][32]byte, keyIndex []uint32, digests [][32]byte, lowS bool) (sigs [][64]byte, recid []byte, ok []bool, err error)
 }
 
+// K256BatchRecoverer is the secp256k1 public-key recovery of a backend (sbv_secp256k1_recover): key i = the signer's Qx|Qy of
+// signature sigs[i] (r|s, 64 bytes big-endian) with recovery id recid[i] (0..3, as K256BatchSigner emits it) over digests[i], by the
+// rules of libsecp256k1's ecdsa_recover (include/sbv.h); lowS also refuses s > (n-1)/2.  ok[i] = false, and a zero key, for a refused
+// input.  Traffic shaped like Ethereum's carries r|s|v and no key: recover, then register the keys (Backend.RegisterKeys of the
+// secp256k1 registry) and verify keyed.  An optional interface beside Backend like K256BatchSigner, so that existing backends need no
+// change: callers type-assert for it.
+type K256BatchRecoverer interface {
+	RecoverBatchSecp256k1(sigs [][64]byte, recid []byte, digests [][32]byte, lowS bool) (pubs [][64]byte, ok []bool, err error)
+}
+
 // ErrNoBatchSigner: the backend has no batch signing entry (the pure-Go backend).
 var ErrNoBatchSigner = errors.New("gpuverifier: backend has no batch signer")
 

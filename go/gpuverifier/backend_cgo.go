@@ -637,4 +637,40 @@ func (b *gpuBackend) SignBatchSecp256k1(keys [][32]byte, keyIndex []uint32, dige
 	return sigs, recid, ok, nil
 }
 
+// RecoverBatchSecp256k1: sbv_secp256k1_recover (one device call; nothing secret is involved).
+func (b *gpuBackend) RecoverBatchSecp256k1(sigs [][64]byte, recid []byte, digests [][32]byte, lowS bool) (pubs [][64]byte, ok []bool, err error) {
+	n := len(sigs)
+	if n == 0 || len(recid) != n || len(digests) != n {
+		return nil, nil, errors.New("gpuverifier: RecoverBatchSecp256k1 needs one recovery id and one digest per signature")
+	}
+	sb := make([]byte, 64*n)
+	db := make([]byte, 32*n)
+	for i := 0; i < n; i++ {
+		copy(sb[64*i:], sigs[i][:])
+		copy(db[32*i:], digests[i][:])
+	}
+	var mode uint32
+	if lowS {
+		mode = 1 // SBV_K256_RECOVER_LOW_S
+	}
+	out := make([]byte, 64*n)
+	flags := make([]byte, n)
+	b.on(func() {
+		rc := C.sbv_secp256k1_recover(u8(sb), u8(recid), u8(db), C.size_t(n), C.uint32_t(mode), u8(out), u8(flags))
+		if rc != 0 {
+			err = lastError()
+		}
+	})
+	if err != nil {
+		return nil, nil, err
+	}
+	pubs = make([][64]byte, n)
+	ok = make([]bool, n)
+	for i := 0; i < n; i++ {
+		copy(pubs[i][:], out[64*i:64*i+64])
+		ok[i] = flags[i] != 0
+	}
+	return pubs, ok, nil
+}
+
 func (b *gpuBackend) Close() { close(b.jobs) }

@@ -226,6 +226,51 @@ sbv_secp256k1_pubkeys_stream(const void* d_keys, size_t m, void* d_pubs, void* d
  * Any other op is SBV_EINVAL. */
 int sbv_debug_secp256k1_sign_op(int op, const uint8_t* in, uint8_t* out, size_t n);
 
+/* secp256k1 batch public-key recovery: the consumer of the recovery id above.  Traffic shaped like Ethereum's carries no public key
+ * but 65 bytes r | s | v; this returns the signer's key Q of every (r, s, recid, digest), ready for the verify entries or for
+ * sbv_secp256k1_register_keys.  sigs: n x 64 bytes r | s (big-endian), recid: n bytes, digests: n x 32 bytes — exactly the arrays
+ * sbv_secp256k1_sign_batch emits — pubs: n x 64 bytes Qx | Qy, ok: n bytes.  The rules are those of libsecp256k1's ecdsa_recover;
+ * item i fails, with ok[i] = 0 and 64 zero bytes in pubs[i], unless all of these hold:
+ *   - r and s are in [1, n-1];
+ *   - recid is in 0..3;
+ *   - x = r + (recid & 2 ? n : 0) is below p (only r < p - n can take the + n branch);
+ *   - y^2 = x^3 + 7 has a root; y is the root whose canonical parity is recid & 1, R' = (x, y);
+ *   - with e = the digest reduced mod n as the verifier reduces it, u1 = (n - e) r^-1 mod n (0 for e = 0) and u2 = s r^-1 mod n,
+ *     Q = u2 R' + u1 G is not the point at infinity.
+ * Then ok[i] = 1 and pubs[i] = the affine, canonical Qx | Qy, and the verify entries accept (r, s, digest, Q).
+ *   flags   SBV_K256_RECOVER_LOW_S: also refuses s > (n-1)/2, as Bitcoin- and Ethereum-shaped verifiers do.  Any other bit is SBV_EINVAL.
+ * A lane needs a table strip in device memory, so the kernel runs at most SBV_K256_RECOVER_LANES lanes, each over items L, L + LANES,
+ * ...: sbv_secp256k1_recover_workspace(n) = min(n, SBV_K256_RECOVER_LANES) strips of 1536 bytes is all the workspace any n needs.
+ * sbv_secp256k1_recover takes host pointers, uses device buffers and a workspace of the call's own size, waits for the result and
+ * frees them.  sbv_secp256k1_recover_stream takes device pointers and the caller's workspace (d_work, work_bytes >=
+ * sbv_secp256k1_recover_workspace(n)), launches on `hip_stream` and returns without synchronising, under the stream contract of the
+ * `_dev` entries for every buffer it names, the workspace included: two calls that may overlap need two
+ * workspaces.  It owns no mutable device state and shares only the read-only 16-bit comb of G, uploaded (synchronously) by the first
+ * secp256k1 call of the process, which may be this one.  It is named `_stream` for the reason the signer's entries are; its
+ * schedules are in tests/test_gpu_k256_recover.py.
+ * SBV_EINVAL: a null required pointer, an unknown flag bit, and for the `_stream` form a device pointer (sigs, digests, pubs) that
+ * is not 4-byte aligned, a d_work that is not 16-byte aligned or work_bytes too small; SBV_ENOTINIT before sbv_init.  n == 0 is
+ * SBV_OK and writes nothing.  Nothing here is secret, so variable time is no concern. */
+#define SBV_K256_RECOVER_LOW_S 1u
+#ifndef SBV_K256_RECOVER_LANES
+#define SBV_K256_RECOVER_LANES 131072 /* one full residency of an MI355X: 256 CUs x 4 SIMDs x 2 waves x 64 lanes */
+#endif
+int
+sbv_secp256k1_recover(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint32_t flags, uint8_t* pubs,
+                      uint8_t* ok);
+size_t
+sbv_secp256k1_recover_workspace(size_t n);
+int
+sbv_secp256k1_recover_stream(const void* d_sigs, const void* d_recid, const void* d_digests, size_t n, uint32_t flags, void* d_pubs,
+                             void* d_ok, void* d_work, size_t work_bytes, void* hip_stream);
+/* Test only: one case of a unit operation of the recovery per lane on the device, host pointers, in the records of
+ * sbv_debug_secp256k1_sign_op (192 bytes in, 128 bytes out, output field 3 = ok, a case that is not ok is all zero).
+ *   op 0   in: a                  out: a^((p+1)/4)   the square root; ok = a is a square mod p (a is any 256-bit value)
+ *   op 1   in: r | recid          out: x | y         the lifted point R'; ok = 0 when recid > 3, x >= p or x^3 + 7 is no square
+ *   op 2   in: x | y | u1 | u2    out: Qx | Qy       u2 (x, y) + u1 G for a point of the curve and u1, u2 < n; ok = 0: infinity
+ * Any other op is SBV_EINVAL. */
+int sbv_debug_secp256k1_recover_op(int op, const uint8_t* in, uint8_t* out, size_t n);
+
 /* Ed25519 batch signing (RFC 8032 section 5.1.6, pure Ed25519): the batch form of api.Signer.Sign for the Ed25519 variant, in two
  * steps so that a key is expanded once and not once per signature.  Signatures and public keys are byte-identical to RFC 8032,
  * Go's crypto/ed25519 and consensus_amd/host's Signer (the scheme is deterministic: tests compare every byte).
