@@ -580,6 +580,98 @@ def debug_secp256k1_recover_op(op: int, records):
     return [out.raw[128 * i:128 * i + 128] for i in range(n)]
 
 
+def secp256k1_schnorr_verify(pks: bytes, msgs: bytes, sigs: bytes) -> bytes:
+    """sbv_secp256k1_schnorr_verify: BIP-340 verification of n signatures (R.x | s, 64 bytes each) of 32-byte messages under x-only
+    32-byte keys.  Returns ok: one byte per item, 1 = valid (include/sbv.h has the rules)."""
+    lib = load()
+    n = len(sigs) // 64
+    if len(sigs) != 64 * n or len(pks) != 32 * n or len(msgs) != 32 * n:
+        raise ValueError("secp256k1_schnorr_verify: pks, msgs and sigs disagree about n")
+    lib.sbv_secp256k1_schnorr_verify.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
+    ok = ctypes.create_string_buffer(max(1, n))
+    _check(lib.sbv_secp256k1_schnorr_verify(bytes(pks), bytes(msgs), bytes(sigs), n, ok))
+    return ok.raw[:n]
+
+
+def secp256k1_schnorr_verify_workspace(n: int) -> int:
+    """sbv_secp256k1_schnorr_verify_workspace: the bytes of device workspace secp256k1_schnorr_verify_stream needs for n signatures"""
+    lib = load()
+    lib.sbv_secp256k1_schnorr_verify_workspace.argtypes = [ctypes.c_size_t]
+    lib.sbv_secp256k1_schnorr_verify_workspace.restype = ctypes.c_size_t
+    return int(lib.sbv_secp256k1_schnorr_verify_workspace(n))
+
+
+def secp256k1_schnorr_verify_stream(d_pks_ptr: int, d_msgs_ptr: int, d_sigs_ptr: int, n: int, d_ok_ptr: int, d_work_ptr: int,
+                                    work_bytes: int, stream: int = 0) -> None:
+    """device pointers and the caller's workspace (16-byte aligned, secp256k1_schnorr_verify_workspace(n) bytes); asynchronous on
+    `stream` under the stream contract of the _dev entries (include/sbv.h)"""
+    lib = load()
+    lib.sbv_secp256k1_schnorr_verify_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_schnorr_verify_stream(d_pks_ptr or None, d_msgs_ptr or None, d_sigs_ptr or None, n, d_ok_ptr or None,
+                                                   d_work_ptr or None, work_bytes, stream or None))
+
+
+def secp256k1_schnorr_expand_keys(keys: bytes, want_pks: bool = True):
+    """sbv_secp256k1_schnorr_expand_keys: 32-byte private scalars -> (expanded, pks, ok): the 64-byte records d | P.x (AS SECRET AS THE
+    KEYS) in one bytes object, the x-only public keys in one bytes object (None without want_pks) and ok[i] = 1 per key in [1, n-1]
+    (otherwise an all-zero record and key).  NOT constant-time: see include/sbv.h."""
+    lib = load()
+    m = len(keys) // 32
+    lib.sbv_secp256k1_schnorr_expand_keys.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
+    exp, ok = ctypes.create_string_buffer(max(1, 64 * m)), ctypes.create_string_buffer(max(1, m))
+    pks = ctypes.create_string_buffer(max(1, 32 * m)) if want_pks else None
+    _check(lib.sbv_secp256k1_schnorr_expand_keys(bytes(keys), m, exp, pks, ok))
+    return exp.raw[:64 * m], (pks.raw[:32 * m] if want_pks else None), ok.raw[:m]
+
+
+def secp256k1_schnorr_expand_keys_stream(d_keys_ptr: int, m: int, d_expanded_ptr: int, d_pks_ptr: int, d_ok_ptr: int, stream: int = 0) -> None:
+    """device pointers (d_pks_ptr may be 0); asynchronous on `stream` under the stream contract of the _dev entries (include/sbv.h)"""
+    lib = load()
+    lib.sbv_secp256k1_schnorr_expand_keys_stream.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                             ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_schnorr_expand_keys_stream(d_keys_ptr or None, m, d_expanded_ptr or None, d_pks_ptr or None, d_ok_ptr or None,
+                                                        stream or None))
+
+
+def secp256k1_schnorr_sign(expanded: bytes, msgs: bytes, aux=None, key_index=None):
+    """sbv_secp256k1_schnorr_sign: BIP-340 signatures (R.x | s, 64 bytes each) of n 32-byte messages under the records of
+    secp256k1_schnorr_expand_keys (key_index[i], default i % n_keys); aux: n x 32 bytes of auxiliary randomness, None = zero bytes.
+    Returns (sigs, ok); a refused record or an index out of range gives ok[i] = 0 and 64 zero bytes.  Records must come from
+    secp256k1_schnorr_expand_keys: a record whose P.x does not belong to its d yields signatures that can leak d.  NOT constant-time:
+    see include/sbv.h."""
+    lib = load()
+    n, nk = len(msgs) // 32, len(expanded) // 64
+    if aux is not None and len(aux) != 32 * n:
+        raise ValueError("secp256k1_schnorr_sign: aux and msgs disagree about n")
+    lib.sbv_secp256k1_schnorr_sign.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p,
+                                               ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p]
+    sigs, ok = ctypes.create_string_buffer(max(1, 64 * n)), ctypes.create_string_buffer(max(1, n))
+    idx = None if key_index is None else (ctypes.c_uint32 * n)(*key_index)
+    _check(lib.sbv_secp256k1_schnorr_sign(bytes(expanded), nk, idx, bytes(msgs), None if aux is None else bytes(aux), n, sigs, ok))
+    return sigs.raw[:64 * n], ok.raw[:n]
+
+
+def secp256k1_schnorr_sign_stream(d_expanded_ptr: int, n_keys: int, d_index_ptr: int, d_msgs_ptr: int, d_aux_ptr: int, n: int,
+                                  d_sigs_ptr: int, d_ok_ptr: int, stream: int = 0) -> None:
+    """device pointers (d_index_ptr and d_aux_ptr may be 0); asynchronous on `stream` under the stream contract of the _dev entries"""
+    lib = load()
+    lib.sbv_secp256k1_schnorr_sign_stream.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_schnorr_sign_stream(d_expanded_ptr or None, n_keys, d_index_ptr or None, d_msgs_ptr or None, d_aux_ptr or None, n,
+                                                 d_sigs_ptr or None, d_ok_ptr or None, stream or None))
+
+
+def debug_secp256k1_schnorr_op(op: int, records):
+    """sbv_debug_secp256k1_schnorr_op (test only): one case per lane, 192-byte input records -> 128-byte output records (include/sbv.h)"""
+    lib = load()
+    n = len(records)
+    lib.sbv_debug_secp256k1_schnorr_op.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+    out = ctypes.create_string_buffer(max(1, 128 * n))
+    _check(lib.sbv_debug_secp256k1_schnorr_op(op, b"".join(records), out, n))
+    return [out.raw[128 * i:128 * i + 128] for i in range(n)]
+
+
 def ed25519_expand_keys(seeds):
     """sbv_ed25519_expand_keys: 32-byte seeds (a list, or their concatenation) -> (expanded, pks): the 96-byte expanded records
     (a mod L | prefix | A_enc, as secret as the seeds) in one bytes object, and the list of 32-byte public keys."""

@@ -37,6 +37,7 @@
 #include "k256_keyed_kernels.h"
 #include "k256_sign_kernels.h"
 #include "k256_recover_kernels.h"
+#include "k256_schnorr_kernels.h"
 
 namespace {
 
@@ -2906,6 +2907,212 @@ extern "C" int sbv_debug_secp256k1_recover_op(int op, const uint8_t* in, uint8_t
     } while (false);
     if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);
     if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (d_work) (void)hipFree(d_work);
+    return rc;
+}
+
+// ---- BIP-340 Schnorr over secp256k1 (k256_schnorr.h, k256_schnorr_kernels.hip) -------------------------------------------------
+// Stateless apart from the read-only 16-bit comb of G (ensure_k256_table): the _stream forms read and write only buffers of the
+// caller's, the verifier's workspace of table strips included, on the caller's stream: nothing to order, nothing to join back.
+extern "C" size_t sbv_secp256k1_schnorr_verify_workspace(size_t n) { return sbv_secp256k1_recover_workspace(n); }
+
+extern "C" int sbv_secp256k1_schnorr_verify_stream(const void* d_pks, const void* d_msgs, const void* d_sigs, size_t n, void* d_ok, void* d_work,
+                                                   size_t work_bytes, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!d_pks || !d_msgs || !d_sigs || !d_ok || !d_work) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (((reinterpret_cast<uintptr_t>(d_pks) | reinterpret_cast<uintptr_t>(d_msgs) | reinterpret_cast<uintptr_t>(d_sigs)) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_work) & 15)) {
+        g_err = "misaligned device pointer";
+        return SBV_EINVAL;
+    }
+    if (work_bytes < sbv_secp256k1_schnorr_verify_workspace(n)) { g_err = "workspace too small"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_schnorr_verify(static_cast<const uint8_t*>(d_pks), static_cast<const uint8_t*>(d_msgs),
+                                                         static_cast<const uint8_t*>(d_sigs), n, c.d_k256_gtab, static_cast<u32*>(d_work),
+                                                         static_cast<uint8_t*>(d_ok), static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_schnorr_verify(const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!pks || !msgs || !sigs || !ok) { g_err = "null pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    // not a hot path: buffers and a workspace of the call's own size, released before returning
+    uint8_t *d_pk = nullptr, *d_msg = nullptr, *d_sig = nullptr, *d_ok = nullptr;
+    u32* d_work = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_pk, n * 32))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_msg, n * 32))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_work, sbv_secp256k1_schnorr_verify_workspace(n)))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_pk, pks, n * 32, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_msg, msgs, n * 32, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_sig, sigs, n * 64, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_verify(d_pk, d_msg, d_sig, n, c.d_k256_gtab, d_work, d_ok, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);       // nothing of this call is in flight when its buffers go
+    if (d_pk) (void)hipFree(d_pk);
+    if (d_msg) (void)hipFree(d_msg);
+    if (d_sig) (void)hipFree(d_sig);
+    if (d_ok) (void)hipFree(d_ok);
+    if (d_work) (void)hipFree(d_work);
+    return rc;
+}
+
+extern "C" int sbv_secp256k1_schnorr_expand_keys_stream(const void* d_keys, size_t m, void* d_expanded, void* d_pks, void* d_ok, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!d_keys || !d_expanded || !d_ok) { g_err = "null pointer"; return SBV_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(d_keys) | reinterpret_cast<uintptr_t>(d_expanded) | reinterpret_cast<uintptr_t>(d_pks)) & 3) {
+        g_err = "misaligned device pointer";
+        return SBV_EINVAL;
+    }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_schnorr_expand(static_cast<const uint8_t*>(d_keys), m, c.d_k256_gtab, static_cast<uint8_t*>(d_expanded),
+                                                         static_cast<uint8_t*>(d_pks), static_cast<uint8_t*>(d_ok),
+                                                         static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_schnorr_expand_keys(const uint8_t* keys, size_t m, uint8_t* expanded, uint8_t* pks, uint8_t* ok) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!keys || !expanded || !ok) { g_err = "null pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    uint8_t *d_keys = nullptr, *d_exp = nullptr, *d_pk = nullptr, *d_ok = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_keys, m * 32))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_exp, m * 64))) break;
+        if (pks && fail(SBV_ENOMEM, hipMalloc(&d_pk, m * 32))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, m))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_keys, keys, m * 32, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_expand(d_keys, m, c.d_k256_gtab, d_exp, d_pk, d_ok, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(expanded, d_exp, m * 64, hipMemcpyDeviceToHost, c.stream))) break;
+        if (pks && fail(SBV_EDEVICE, hipMemcpyAsync(pks, d_pk, m * 32, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, m, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    // the device copies of the secrets are zeroed before they go
+    if (d_keys) (void)hipMemsetAsync(d_keys, 0, m * 32, c.stream);
+    if (d_exp) (void)hipMemsetAsync(d_exp, 0, m * 64, c.stream);
+    (void)hipStreamSynchronize(c.stream);
+    if (d_keys) (void)hipFree(d_keys);
+    if (d_exp) (void)hipFree(d_exp);
+    if (d_pk) (void)hipFree(d_pk);
+    if (d_ok) (void)hipFree(d_ok);
+    return rc;
+}
+
+extern "C" int sbv_secp256k1_schnorr_sign_stream(const void* d_expanded, uint32_t n_keys, const void* d_key_index, const void* d_msgs,
+                                                 const void* d_aux, size_t n, void* d_sigs, void* d_ok, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!d_expanded || !d_msgs || !d_sigs || !d_ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(d_expanded) | reinterpret_cast<uintptr_t>(d_msgs) | reinterpret_cast<uintptr_t>(d_sigs) |
+         reinterpret_cast<uintptr_t>(d_key_index) | reinterpret_cast<uintptr_t>(d_aux)) & 3) {
+        g_err = "misaligned device pointer";
+        return SBV_EINVAL;
+    }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_schnorr_sign(static_cast<const uint8_t*>(d_expanded), n_keys, static_cast<const u32*>(d_key_index),
+                                                       static_cast<const uint8_t*>(d_msgs), static_cast<const uint8_t*>(d_aux), n, c.d_k256_gtab,
+                                                       static_cast<uint8_t*>(d_sigs), static_cast<uint8_t*>(d_ok),
+                                                       static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_schnorr_sign(const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs,
+                                          const uint8_t* aux, size_t n, uint8_t* sigs, uint8_t* ok) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!expanded || !msgs || !sigs || !ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    // not a hot path: buffers of the call's own size, released before returning (records do not linger in a pool)
+    uint8_t *d_exp = nullptr, *d_msg = nullptr, *d_aux = nullptr, *d_sig = nullptr, *d_ok = nullptr;
+    u32* d_idx = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_exp, (size_t)n_keys * 64))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_msg, n * 32))) break;
+        if (aux && fail(SBV_ENOMEM, hipMalloc(&d_aux, n * 32))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
+        if (key_index && fail(SBV_ENOMEM, hipMalloc(&d_idx, n * sizeof(u32)))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_exp, expanded, (size_t)n_keys * 64, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_msg, msgs, n * 32, hipMemcpyHostToDevice, c.stream))) break;
+        if (aux && fail(SBV_EDEVICE, hipMemcpyAsync(d_aux, aux, n * 32, hipMemcpyHostToDevice, c.stream))) break;
+        if (key_index && fail(SBV_EDEVICE, hipMemcpyAsync(d_idx, key_index, n * sizeof(u32), hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_sign(d_exp, n_keys, d_idx, d_msg, d_aux, n, c.d_k256_gtab, d_sig, d_ok, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(sigs, d_sig, n * 64, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (d_exp) {
+        (void)hipMemsetAsync(d_exp, 0, (size_t)n_keys * 64, c.stream);
+        (void)hipStreamSynchronize(c.stream);
+    }
+    if (d_exp) (void)hipFree(d_exp);
+    if (d_msg) (void)hipFree(d_msg);
+    if (d_aux) (void)hipFree(d_aux);
+    if (d_sig) (void)hipFree(d_sig);
+    if (d_ok) (void)hipFree(d_ok);
+    if (d_idx) (void)hipFree(d_idx);
+    return rc;
+}
+
+// Test only (include/sbv.h): one case of a unit operation of the Schnorr lanes per lane: 192 bytes in, 128 bytes out, one strip per case.
+extern "C" int sbv_debug_secp256k1_schnorr_op(int op, const uint8_t* in, uint8_t* out, size_t n) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (op < 0 || op > 3) { g_err = "unknown operation"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!in || !out || n > 65536) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    u32* d_work = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_in, n * 192))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_out, n * 128))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_work, n * sbv::k256_recover_strip_bytes()))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_in, in, n * 192, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_op(op, d_in, d_out, n, c.d_k256_gtab, d_work, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(out, d_out, n * 128, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (d_in) {
+        (void)hipMemsetAsync(d_in, 0, n * 192, c.stream);
+        (void)hipStreamSynchronize(c.stream);
+        (void)hipFree(d_in);
+    }
     if (d_out) (void)hipFree(d_out);
     if (d_work) (void)hipFree(d_work);
     return rc;

@@ -88,6 +88,15 @@ size_t sbvh_backend_last_k256_slots(void* h, uint32_t* out, size_t cap) {
 int sbvh_recover_signers(void* h, const uint8_t* sigs65, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) {
     return ((VHandle*)h)->v->RecoverSigners(sigs65, digests, n, pubs, ok).code;
 }
+// Verifier::VerifySchnorr: n x 32 bytes x-only keys + n x 32 bytes + n x 64 bytes R.x | s -> n bytes; returns the status code
+int sbvh_verify_schnorr(void* h, const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok) {
+    return ((VHandle*)h)->v->VerifySchnorr(pks, msgs, sigs, n, ok).code;
+}
+// Backend::schnorr_sign_k256 of the handle's backend: records from sbvh_k256_schnorr_expand (or the device entry); 0 or the error code
+int sbvh_sign_schnorr(void* h, const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs, const uint8_t* aux,
+                      size_t n, uint8_t* sigs, uint8_t* ok) {
+    return ((VHandle*)h)->be->schnorr_sign_k256(expanded, n_keys, key_index, msgs, aux, n, sigs, ok);
+}
 void sbvh_register_consenter(void* h, uint64_t id, const uint8_t q[64]) { ((VHandle*)h)->v->RegisterConsenter(id, q); }
 void sbvh_register_client(void* h, const char* client, const uint8_t q[64]) { ((VHandle*)h)->v->RegisterClient(client, q); }
 // 0: clients registered from now on get no comb slot on the device (their request signatures go as generic tuples)
@@ -276,6 +285,12 @@ int sbvh_k256_sign_rfc6979(const uint8_t d[32], const uint8_t digest[32], uint8_
 int sbvh_k256_pubkey(const uint8_t d[32], uint8_t q[64]) { return k256_pubkey_from_private(d, q) ? 0 : -1; }
 // the secp256k1 host recovery on its own (k256_host.cc): 0 and the key, or -1 and 64 zero bytes
 int sbvh_k256_recover(const uint8_t rs[64], uint8_t recid, const uint8_t digest[32], uint8_t q[64]) { return k256_recover(rs, recid, digest, q) ? 0 : -1; }
+// the BIP-340 host forms on their own (k256_host.cc): 0, or -1 (and zeroed output) for a refused key or record / an invalid signature
+int sbvh_k256_schnorr_expand(const uint8_t d[32], uint8_t rec[64]) { return k256_schnorr_expand(d, rec) ? 0 : -1; }
+int sbvh_k256_schnorr_sign(const uint8_t rec[64], const uint8_t msg[32], const uint8_t* aux, uint8_t sig[64]) {
+    return k256_schnorr_sign(rec, msg, aux, sig) ? 0 : -1;
+}
+int sbvh_k256_schnorr_verify(const uint8_t pk[32], const uint8_t msg[32], const uint8_t sig[64]) { return k256_schnorr_verify(pk, msg, sig) ? 0 : -1; }
 
 // ---- formats ---------------------------------------------------------------------------------------
 void sbvh_proposal_digest(const void* payload, size_t pl, const void* header, size_t hl, const void* meta, size_t ml,

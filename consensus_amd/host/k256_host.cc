@@ -10,6 +10,7 @@
 
 #include "../csrc/k256_core.h"
 #include "../csrc/k256_recover.h"
+#include "../csrc/k256_schnorr.h"
 #include "p256_host.h"
 
 namespace sbvhost {
@@ -159,6 +160,57 @@ bool k256_recover(const uint8_t rs[64], uint8_t recid, const uint8_t digest[32],
     if (!k256_recover_finish(Q, qw)) return false;
     for (int k = 0; k < 16; ++k) { q[4 * k] = (uint8_t)(qw[k] >> 24); q[4 * k + 1] = (uint8_t)(qw[k] >> 16); q[4 * k + 2] = (uint8_t)(qw[k] >> 8); q[4 * k + 3] = (uint8_t)qw[k]; }
     return true;
+}
+
+// ---- BIP-340 Schnorr (csrc/k256_schnorr.h): the lanes' own front and back ends, with G from the 8-bit comb above -----------------
+namespace {
+void words_from_be(u32* w, const uint8_t* b, int nwords) {
+    for (int k = 0; k < nwords; ++k) w[k] = ((u32)b[4 * k] << 24) | ((u32)b[4 * k + 1] << 16) | ((u32)b[4 * k + 2] << 8) | b[4 * k + 3];
+}
+void words_to_be(uint8_t* b, const u32* w, int nwords) {
+    for (int k = 0; k < nwords; ++k) { b[4 * k] = (uint8_t)(w[k] >> 24); b[4 * k + 1] = (uint8_t)(w[k] >> 16); b[4 * k + 2] = (uint8_t)(w[k] >> 8); b[4 * k + 3] = (uint8_t)w[k]; }
+}
+}  // namespace
+
+bool k256_schnorr_expand(const uint8_t d_be[32], uint8_t rec[64]) {
+    memset(rec, 0, 64);
+    u256 d, x, y;
+    from_be32(d, d_be);
+    if (!valid_scalar(d)) return false;
+    base_mul_affine(d, x, y);
+    u32 rw[16];
+    k256_schnorr_expand_finish(d, x, y, rw);
+    words_to_be(rec, rw, 16);
+    return true;
+}
+
+bool k256_schnorr_sign(const uint8_t rec[64], const uint8_t msg[32], const uint8_t* aux, uint8_t sig[64]) {
+    memset(sig, 0, 64);
+    u32 rw[16], mw[8], aw[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sw[16];
+    words_from_be(rw, rec, 16);
+    words_from_be(mw, msg, 8);
+    if (aux) words_from_be(aw, aux, 8);
+    u256 d, k0, x, y;
+    if (!k256_schnorr_nonce(rw, mw, aw, d, k0)) return false;
+    base_mul_affine(k0, x, y);
+    k256_schnorr_sign_finish(d, rw + 8, k0, x, y, mw, sw);
+    words_to_be(sig, sw, 16);
+    return true;
+}
+
+bool k256_schnorr_verify(const uint8_t pk[32], const uint8_t msg[32], const uint8_t sig[64]) {
+    u32 pw[8], mw[8], sw[16], qw[16];
+    words_from_be(pw, pk, 8);
+    words_from_be(mw, msg, 8);
+    words_from_be(sw, sig, 16);
+    kfe x, y;
+    u256 u1, u2;
+    if (!k256_schnorr_verify_front(pw, mw, sw, x, y, u1, u2)) return false;
+    alignas(16) u32 strip[SBV_K256_QTAB_WORDS];
+    kjpt R;
+    k256_mul_u2Q(R, x, y, u2, strip);              // (n - e) P
+    comb8_add(R, u1);                              // + s G
+    return k256_schnorr_final(R, sw, qw);
 }
 
 }  // namespace sbvhost

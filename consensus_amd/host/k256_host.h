@@ -11,5 +11,11 @@ bool k256_sign_rfc6979(const uint8_t d_be[32], const uint8_t digest[32], uint8_t
 // flags = 0: the CPU form of the device entry, on the same lane functions (csrc/k256_recover.h) with u1 G from the signer's 8-bit comb.
 // false, and q zeroed, for a refused input.
 bool k256_recover(const uint8_t rs[64], uint8_t recid, const uint8_t digest[32], uint8_t q[64]);
+// BIP-340 Schnorr by the rules of the sbv_secp256k1_schnorr_ entries (include/sbv.h): the CPU forms of the device entries, on the same
+// lane functions (csrc/k256_schnorr.h) with G from the signer's 8-bit comb.  rec = d | P.x, as secret as the key; aux may be null
+// (32 zero bytes).  expand and sign return false, with the output zeroed, for a refused key or record.  NOT constant-time.
+bool k256_schnorr_expand(const uint8_t d_be[32], uint8_t rec[64]);
+bool k256_schnorr_sign(const uint8_t rec[64], const uint8_t msg[32], const uint8_t* aux, uint8_t sig[64]);
+bool k256_schnorr_verify(const uint8_t pk[32], const uint8_t msg[32], const uint8_t sig[64]);
 
 }  // namespace sbvhost

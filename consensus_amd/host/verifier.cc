@@ -115,6 +115,28 @@ void parallel_chunks(size_t n, F fn) {
 }  // namespace
 
 // ---- backends ------------------------------------------------------------------------------------
+// the defaults of the Schnorr entries: a loop over the host forms (k256_host.cc)
+int Backend::schnorr_verify_k256(const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok) {
+    parallel_chunks(n, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) ok[i] = k256_schnorr_verify(pks + 32 * i, msgs + 32 * i, sigs + 64 * i) ? 1 : 0;
+    });
+    return 0;
+}
+int Backend::schnorr_sign_k256(const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs, const uint8_t* aux,
+                               size_t n, uint8_t* sigs, uint8_t* ok) {
+    if (n == 0) return 0;
+    if (n_keys == 0) return SBV_EINVAL;
+    parallel_chunks(n, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) {
+            const uint32_t k = key_index ? key_index[i] : (uint32_t)(i % n_keys);
+            const bool good = k < n_keys && k256_schnorr_sign(expanded + 64 * (size_t)k, msgs + 32 * i, aux ? aux + 32 * i : nullptr, sigs + 64 * i);
+            if (!good) memset(sigs + 64 * i, 0, 64);
+            ok[i] = good ? 1 : 0;
+        }
+    });
+    return 0;
+}
+
 namespace {
 class SbvBackend : public Backend {
  public:
@@ -199,6 +221,15 @@ class SbvBackend : public Backend {
     int recover_k256(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) override {
         if (rc_ != SBV_OK) return rc_;
         return sbv_secp256k1_recover(sigs, recid, digests, n, 0, pubs, ok);
+    }
+    int schnorr_verify_k256(const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok) override {
+        if (rc_ != SBV_OK) return rc_;
+        return sbv_secp256k1_schnorr_verify(pks, msgs, sigs, n, ok);
+    }
+    int schnorr_sign_k256(const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs, const uint8_t* aux, size_t n,
+                          uint8_t* sigs, uint8_t* ok) override {
+        if (rc_ != SBV_OK) return rc_;
+        return sbv_secp256k1_schnorr_sign(expanded, n_keys, key_index, msgs, aux, n, sigs, ok);
     }
     void* host_alloc(size_t bytes) override { return rc_ == SBV_OK ? sbv_host_alloc(bytes) : nullptr; }
     void host_free(void* p) override { sbv_host_free(p); }
@@ -1390,6 +1421,15 @@ Status Verifier::RecoverSigners(const uint8_t* sigs65, const uint8_t* digests, s
     const int rc = co_.backend().recover_k256(sigs.data(), recid.data(), digests, n, pubs, ok);
     if (rc == -2) return Status::Unavailable("the backend has no secp256k1 recovery");
     if (rc != 0) return Status::Unavailable("secp256k1 recovery failed on the backend");
+    return Status::Ok();
+}
+
+Status Verifier::VerifySchnorr(const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok) {
+    if (!k256()) return Status::Invalid("VerifySchnorr needs Scheme::SECP256K1");
+    if (n == 0) return Status::Ok();
+    if (!pks || !msgs || !sigs || !ok) return Status::Invalid("VerifySchnorr: null pointer");
+    const int rc = co_.backend().schnorr_verify_k256(pks, msgs, sigs, n, ok);
+    if (rc != 0) return Status::Unavailable("BIP-340 verification failed on the backend");
     return Status::Ok();
 }
 

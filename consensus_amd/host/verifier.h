@@ -91,6 +91,13 @@ class Backend {
     virtual int recover_k256(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) {
         (void)sigs; (void)recid; (void)digests; (void)n; (void)pubs; (void)ok; return -2;
     }
+    // BIP-340 Schnorr over secp256k1 (include/sbv.h: sbv_secp256k1_schnorr_verify, _sign): x-only keys n x 32, messages n x 32,
+    // signatures n x 64 -> ok[i] = 1 per valid signature; records n_keys x 64 from the expansion, key_index (or null: i % n_keys),
+    // aux n x 32 (or null: zero bytes) -> signatures and ok.  The default is a CPU loop over the host forms (k256_host.cc); the GPU
+    // backend makes one device call.  0, or the backend's error code.
+    virtual int schnorr_verify_k256(const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok);
+    virtual int schnorr_sign_k256(const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs, const uint8_t* aux,
+                                  size_t n, uint8_t* sigs, uint8_t* ok);
     virtual int verify_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* bitmap) {
         (void)rsh; (void)slots; (void)n; (void)bitmap; return -2;
     }
@@ -235,6 +242,10 @@ class Verifier {
     // recovered key (otherwise 64 zero bytes; any other v is refused).  One backend call (sbv_secp256k1_recover on the device); what an
     // integrator calls before RegisterClient / register_key_k256.  INVALID under another scheme, UNAVAILABLE on a backend error.
     Status RecoverSigners(const uint8_t* sigs65, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok);
+    // Scheme::SECP256K1 only: BIP-340 Schnorr verification of n signatures as traffic shaped like Bitcoin's carries them since Taproot:
+    // pks = n x 32 bytes x-only keys, msgs = n x 32 bytes, sigs = n x 64 bytes R.x | s -> ok[i] = 1 per valid signature.  One backend
+    // call (sbv_secp256k1_schnorr_verify on the device, a CPU loop otherwise).  INVALID under another scheme, UNAVAILABLE on a backend error.
+    Status VerifySchnorr(const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok);
     CoalescerStats stats() { return co_.stats(); }
     Scheme scheme() const { return opt_.scheme; }
 

@@ -108,6 +108,17 @@ type K256BatchRecoverer interface {
 	RecoverBatchSecp256k1(sigs [][64]byte, recid []byte, digests [][32]byte, lowS bool) (pubs [][64]byte, ok []bool, err error)
 }
 
+// K256Schnorr is the BIP-340 Schnorr pair of a backend over secp256k1 (sbv_secp256k1_schnorr_verify, _expand_keys and _sign): what
+// traffic shaped like Bitcoin's carries since Taproot.  VerifyBatchSchnorr: ok[i] = the verdict of BIP-340 "Verify" on the x-only key
+// pks[i], the 32-byte message msgs[i] and sigs[i] = R.x|s.  SignBatchSchnorr: signature i = BIP-340 "Default Signing" of msgs[i] under
+// keys[keyIndex[i]] with the auxiliary randomness aux[i] (aux == nil: 32 zero bytes for every message); pks[k] is the x-only public
+// key of keys[k]; ok[i] = false, and a zero signature, when the key is not in [1, n-1] or the index is out of range.  Signing on the
+// device is not constant-time (include/sbv.h).  An optional interface beside Backend like K256BatchRecoverer: callers type-assert.
+type K256Schnorr interface {
+	VerifyBatchSchnorr(pks [][32]byte, msgs [][32]byte, sigs [][64]byte) (ok []bool, err error)
+	SignBatchSchnorr(keys [][32]byte, keyIndex []uint32, msgs [][32]byte, aux [][32]byte) (sigs [][64]byte, pks [][32]byte, ok []bool, err error)
+}
+
 // ErrNoBatchSigner: the backend has no batch signing entry (the pure-Go backend).
 var ErrNoBatchSigner = errors.New("gpuverifier: backend has no batch signer")
 

@@ -673,4 +673,99 @@ func (b *gpuBackend) RecoverBatchSecp256k1(sigs [][64]byte, recid []byte, digest
 	return pubs, ok, nil
 }
 
+// VerifyBatchSchnorr: sbv_secp256k1_schnorr_verify (one device call; nothing secret is involved).
+func (b *gpuBackend) VerifyBatchSchnorr(pks [][32]byte, msgs [][32]byte, sigs [][64]byte) (ok []bool, err error) {
+	n := len(sigs)
+	if n == 0 || len(pks) != n || len(msgs) != n {
+		return nil, errors.New("gpuverifier: VerifyBatchSchnorr needs one key and one message per signature")
+	}
+	pb := make([]byte, 32*n)
+	mb := make([]byte, 32*n)
+	sb := make([]byte, 64*n)
+	for i := 0; i < n; i++ {
+		copy(pb[32*i:], pks[i][:])
+		copy(mb[32*i:], msgs[i][:])
+		copy(sb[64*i:], sigs[i][:])
+	}
+	flags := make([]byte, n)
+	b.on(func() {
+		rc := C.sbv_secp256k1_schnorr_verify(u8(pb), u8(mb), u8(sb), C.size_t(n), u8(flags))
+		if rc != 0 {
+			err = lastError()
+		}
+	})
+	if err != nil {
+		return nil, err
+	}
+	ok = make([]bool, n)
+	for i := 0; i < n; i++ {
+		ok[i] = flags[i] != 0
+	}
+	return ok, nil
+}
+
+// SignBatchSchnorr: sbv_secp256k1_schnorr_expand_keys, then sbv_secp256k1_schnorr_sign under the records (not constant-time — see
+// include/sbv.h).  The records are as secret as the keys and are zeroed with them.
+func (b *gpuBackend) SignBatchSchnorr(keys [][32]byte, keyIndex []uint32, msgs [][32]byte, aux [][32]byte) (sigs [][64]byte, pks [][32]byte, ok []bool, err error) {
+	n := len(msgs)
+	if n == 0 || len(keys) == 0 || len(keyIndex) != n || (aux != nil && len(aux) != n) {
+		return nil, nil, nil, errors.New("gpuverifier: SignBatchSchnorr needs keys, one key index per message and no or one aux per message")
+	}
+	kb := make([]byte, 32*len(keys))
+	for i := range keys {
+		copy(kb[32*i:], keys[i][:])
+	}
+	mb := make([]byte, 32*n)
+	for i := range msgs {
+		copy(mb[32*i:], msgs[i][:])
+	}
+	var ab []byte
+	if aux != nil {
+		ab = make([]byte, 32*n)
+		for i := range aux {
+			copy(ab[32*i:], aux[i][:])
+		}
+	}
+	rec := make([]byte, 64*len(keys))
+	pkb := make([]byte, 32*len(keys))
+	kok := make([]byte, len(keys))
+	out := make([]byte, 64*n)
+	flags := make([]byte, n)
+	b.on(func() {
+		rc := C.sbv_secp256k1_schnorr_expand_keys(u8(kb), C.size_t(len(keys)), u8(rec), u8(pkb), u8(kok))
+		if rc == 0 {
+			if ab == nil {
+				rc = C.sbv_secp256k1_schnorr_sign(u8(rec), C.uint32_t(len(keys)), (*C.uint32_t)(unsafe.Pointer(&keyIndex[0])), u8(mb), nil, C.size_t(n),
+					u8(out), u8(flags))
+			} else {
+				rc = C.sbv_secp256k1_schnorr_sign(u8(rec), C.uint32_t(len(keys)), (*C.uint32_t)(unsafe.Pointer(&keyIndex[0])), u8(mb), u8(ab), C.size_t(n),
+					u8(out), u8(flags))
+			}
+		}
+		if rc != 0 {
+			err = lastError()
+		}
+	})
+	for i := range kb {
+		kb[i] = 0
+	}
+	for i := range rec {
+		rec[i] = 0
+	}
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	sigs = make([][64]byte, n)
+	ok = make([]bool, n)
+	for i := 0; i < n; i++ {
+		copy(sigs[i][:], out[64*i:64*i+64])
+		ok[i] = flags[i] != 0
+	}
+	pks = make([][32]byte, len(keys))
+	for i := range pks {
+		copy(pks[i][:], pkb[32*i:32*i+32])
+	}
+	return sigs, pks, ok, nil
+}
+
 func (b *gpuBackend) Close() { close(b.jobs) }

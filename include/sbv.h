@@ -271,6 +271,78 @@ sbv_secp256k1_recover_stream(const void* d_sigs, const void* d_recid, const void
  * Any other op is SBV_EINVAL. */
 int sbv_debug_secp256k1_recover_op(int op, const uint8_t* in, uint8_t* out, size_t n);
 
+/* BIP-340 Schnorr signatures over secp256k1 (Bitcoin's since Taproot): batch verification, key expansion and batch signing.  Keys are
+ * x-only (32 bytes: the x of the point with even y), messages are 32 bytes, signatures are 64 bytes R.x | s, all big-endian; `ok`
+ * is one byte per item (0 or 1), as in the sign, pubkeys and recover family, not a bitmap.
+ *
+ * Verification follows BIP-340 "Verify" exactly.  pks: n x 32, msgs: n x 32, sigs: n x 64, ok: n bytes.  ok[i] = 1 iff all hold:
+ *   - pk < p and pk^3 + 7 is a square mod p; P = lift_x(pk) is the point with that x and even y;
+ *   - r < p and s < n (s = 0 is in range);
+ *   - with e = int(SHA256 tagged "BIP0340/challenge" of r | pk | msg) mod n, R = s G - e P is not the point at infinity, has even y
+ *     and x = r.
+ * A lane needs a table strip in device memory, exactly as recovery does: at most SBV_K256_RECOVER_LANES lanes run, each over items L,
+ * L + LANES, ..., and sbv_secp256k1_schnorr_verify_workspace(n) = min(n, SBV_K256_RECOVER_LANES) strips of 1536 bytes serves any n.
+ * sbv_secp256k1_schnorr_verify takes host pointers, uses device buffers and a workspace of the call's own size, waits and frees
+ * them.  sbv_secp256k1_schnorr_verify_stream takes device pointers and the caller's workspace (d_work, work_bytes >= the size above),
+ * launches on `hip_stream` and returns without synchronising, under the stream contract of the `_dev` entries (DESIGN.md section
+ * 4.2.4) for every buffer it names, the workspace included: two calls that may overlap need two workspaces.
+ *
+ * Signing is BIP-340 "Default Signing" without its optional final self-verification, in two steps so that the base multiplication
+ * for the key is paid once and not once per signature (as for sbv_ed25519_expand_keys; libsecp256k1 calls the record a keypair).
+ *   sbv_secp256k1_schnorr_expand_keys   keys: m x 32 bytes (d', big-endian).  expanded: m x 64 bytes, one RECORD per key:
+ *                                           bytes  0..31  d     d' when P = d' G has even y, else n - d'
+ *                                           bytes 32..63  P.x   the x-only public key
+ *                                       pks: m x 32 bytes P.x, or NULL when not wanted.  ok[i] = 0 with an all-zero record (and
+ *                                       key) for d' outside [1, n-1].
+ *   sbv_secp256k1_schnorr_sign          expanded: n_keys records; key_index: n x u32, or NULL meaning key i % n_keys; msgs: n x 32;
+ *                                       aux: n x 32 bytes of auxiliary randomness, or NULL meaning 32 zero bytes for every item
+ *                                       (what libsecp256k1 does without auxiliary data); sigs: n x 64; ok: n bytes.  ok[i] = 0 with
+ *                                       64 zero bytes when the index is >= n_keys, the record's d is outside [1, n-1] (the record
+ *                                       of a refused key) or the nonce is 0 (probability ~2^-256).
+ * A RECORD IS AS SECRET AS ITS KEY.  Records must come from sbv_secp256k1_schnorr_expand_keys: the signer does not check that P.x
+ * belongs to d, and a record whose P.x does not yields signatures that can leak d.
+ * The host-pointer forms use device buffers of the call's own size, wait for the result and zero the device copies of keys and
+ * records before they free them.  The `_stream` forms take device pointers, launch on `hip_stream` and return without synchronising,
+ * under the same stream contract.  None of the `_stream` forms owns mutable device state: they share only the read-only 16-bit comb
+ * of G, uploaded (synchronously) by the first secp256k1 call of the process, which may be any of them.  They are named `_stream` for
+ * the reason the ECDSA signer's entries are; their schedules are in tests/test_gpu_k256_schnorr.py.
+ * SBV_EINVAL: a null required pointer, n_keys == 0, and for the `_stream` forms a device pointer to data that is not 4-byte aligned,
+ * a d_work that is not 16-byte aligned or work_bytes too small; SBV_ENOTINIT before sbv_init.  n == 0 (m == 0) is SBV_OK and writes
+ * nothing.
+ * Expansion and signing are NOT constant-time (secret-indexed table lookups in HBM, a variable-time inversion): for test traffic and
+ * trusted single-tenant hosts, see consensus_amd/csrc/k256_schnorr.h.  Verification handles nothing secret. */
+int
+sbv_secp256k1_schnorr_verify(const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok);
+size_t
+sbv_secp256k1_schnorr_verify_workspace(size_t n);
+int
+sbv_secp256k1_schnorr_verify_stream(const void* d_pks, const void* d_msgs, const void* d_sigs, size_t n, void* d_ok, void* d_work,
+                                    size_t work_bytes, void* hip_stream);
+int
+sbv_secp256k1_schnorr_expand_keys(const uint8_t* keys, size_t m, uint8_t* expanded, uint8_t* pks, uint8_t* ok);
+int
+sbv_secp256k1_schnorr_expand_keys_stream(const void* d_keys, size_t m, void* d_expanded, void* d_pks, void* d_ok, void* hip_stream);
+int
+sbv_secp256k1_schnorr_sign(const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs, const uint8_t* aux,
+                           size_t n, uint8_t* sigs, uint8_t* ok);
+int
+sbv_secp256k1_schnorr_sign_stream(const void* d_expanded, uint32_t n_keys, const void* d_key_index, const void* d_msgs, const void* d_aux,
+                                  size_t n, void* d_sigs, void* d_ok, void* hip_stream);
+/* Test only: one case of a unit operation of the Schnorr lanes per lane on the device, host pointers, in the records of
+ * sbv_debug_secp256k1_sign_op (192 bytes in, 128 bytes out, output field 3 = ok).
+ *   op 0   in: a | b | c, selector   out: the tagged hash     selector = the last 4 bytes of field 5: 0 "BIP0340/aux" of a alone,
+ *                                                             1 "BIP0340/nonce", 2 "BIP0340/challenge" of a | b | c; ok = 1
+ *   op 1   in: x                     out: y                   lift_x: the even root of x^3 + 7; ok = 0 (all zero) for x >= p or no root
+ *   op 2   in: X | Y | Z | r         out: x | y               the affine form of a Jacobian point (coordinates below p; Z = 0 is
+ *                                                             infinity: all zero); ok = the verdict of the final check of "Verify":
+ *                                                             not infinity, x = r, y even
+ *   op 3   in: d | Px | k' | m       out: R.x | s             the signing equation on plain integers (d < n): R = k' G, k = k' or
+ *                                                             n - k' by the parity of R.y, s = k + e d; ok = 0 (all zero) for k'
+ *                                                             outside [1, n-1]
+ * Any other op is SBV_EINVAL.  The double-scalar walk is op 2 of sbv_debug_secp256k1_recover_op. */
+int
+sbv_debug_secp256k1_schnorr_op(int op, const uint8_t* in, uint8_t* out, size_t n);
+
 /* Ed25519 batch signing (RFC 8032 section 5.1.6, pure Ed25519): the batch form of api.Signer.Sign for the Ed25519 variant, in two
  * steps so that a key is expanded once and not once per signature.  Signatures and public keys are byte-identical to RFC 8032,
  * Go's crypto/ed25519 and consensus_amd/host's Signer (the scheme is deterministic: tests compare every byte).
