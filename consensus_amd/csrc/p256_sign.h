@@ -18,19 +18,10 @@
 
 namespace sbv {
 
-// (r, s) for a candidate nonce k (plain integers); false when k, r or s falls outside [1, N-1]
-SBV_HD bool sign29_with_nonce(const u256& d, const u256& k, const u256& e, const gcomb& gc, u256& r, u256& s) {
-    const sc n_ = sc_n();
-    if (is_zero256(k) || !lt256(k, n_)) return false;
-    xyzz R;
-    gphase29_point(R, k, gc);
-    if (R.inf) return false;                       // cannot happen for 0 < k < N
-    fe29 zi, xM, x1, one_plain = {{1, 0, 0, 0, 0, 0, 0, 0, 0}};
-    f29_inv_ct(zi, R.ZZ);
-    f29_mul(xM, R.X, zi);                          // affine x, Montgomery domain
-    f29_mul(x1, xM, one_plain);                    // plain
-    u256 x;
-    f29_store_canon(x.v, x1);
+// The signing equation behind the nonce point: r = x mod N, s = k^-1 (e + r d) mod N.  Plain integers: x < p the affine x of k G,
+// d and k in [1, N-1], e < N.  false when r = 0 or s = 0.  On its own so that the branches no nonce reaches (x >= N, r = 0, s = 0)
+// can be run on chosen integers (tools/devunit.hip).
+SBV_HD bool sign29_finish(const u256& x, const u256& d, const u256& k, const u256& e, u256& r, u256& s) {
     sc_cond_sub_n(r, x, 0);                        // x < p < 2N
     if (is_zero256(r)) return false;
     fe29 kL, kM, kinv, rL, dL, dM, eL, t, sM;
@@ -46,6 +37,22 @@ SBV_HD bool sign29_with_nonce(const u256& d, const u256& k, const u256& e, const
     s29_mul(sM, kinv, t);                          // plain(k^-1 (e + r d))
     s29_store_canon(s, sM);
     return !is_zero256(s);
+}
+
+// (r, s) for a candidate nonce k (plain integers); false when k, r or s falls outside [1, N-1]
+SBV_HD bool sign29_with_nonce(const u256& d, const u256& k, const u256& e, const gcomb& gc, u256& r, u256& s) {
+    const sc n_ = sc_n();
+    if (is_zero256(k) || !lt256(k, n_)) return false;
+    xyzz R;
+    gphase29_point(R, k, gc);
+    if (R.inf) return false;                       // cannot happen for 0 < k < N
+    fe29 zi, xM, x1, one_plain = {{1, 0, 0, 0, 0, 0, 0, 0, 0}};
+    f29_inv_ct(zi, R.ZZ);
+    f29_mul(xM, R.X, zi);                          // affine x, Montgomery domain
+    f29_mul(x1, xM, one_plain);                    // plain
+    u256 x;
+    f29_store_canon(x.v, x1);
+    return sign29_finish(x, d, k, e, r, s);
 }
 
 // d_be, digest: 8 big-endian words each.  rs: r | s as 16 big-endian words.  false: d outside [1, N-1] (rs zeroed).

@@ -172,7 +172,16 @@ int sbv_p256_verify_batch_keyed_dev(const void* d_rsh, const void* d_slots, size
  * i % n_keys.  keys: n_keys x 32 bytes (private scalar, big-endian); digests: n x 32 bytes (SHA-256 of the message);
  * sigs: n x 64 bytes r | s (big-endian; DER-encode for types.Signature.Value); ok[i] = 0 when key i is not in [1, N-1] or the
  * index is out of range (sigs[i] is then all zero).  NOT constant-time (secret-indexed table lookups in HBM): for test
- * traffic and trusted single-tenant hosts, see consensus_amd/csrc/p256_sign.h. */
+ * traffic and trusted single-tenant hosts, see consensus_amd/csrc/p256_sign.h.
+ * SBV_ENOTINIT before sbv_init, for both entries and whatever the arguments.  n == 0 is SBV_OK and writes nothing.  Otherwise
+ * SBV_EINVAL, with nothing written: a null keys, digests, sigs or ok, n_keys == 0, and for the `_dev` entry a d_keys, d_key_index,
+ * d_digests or d_sigs that is not 4-byte aligned (the kernel reads and writes them as 32-bit words); d_ok is a byte array and may
+ * sit at any address.  A refused call leaves the library as it was: the next good call signs.
+ * sbv_p256_sign_batch takes host pointers, uses device buffers of the call's own size, waits for the result and zeroes the device
+ * copy of the keys before it frees it.  sbv_p256_sign_batch_dev takes device pointers, launches on `hip_stream` and returns without
+ * synchronising, under the stream contract of the `_dev` entries above; it may be the first call of a
+ * process after sbv_init.  Both are held byte for byte to an independent RFC 6979 signer, the retry of section 3.2 h (a first
+ * candidate >= N: 2^-32 per signature) included, in tests/test_emul_sign.py and tests/test_gpu_sign.py. */
 int sbv_p256_sign_batch(const uint8_t* keys, uint32_t n_keys, const uint32_t* key_index, const uint8_t* digests, size_t n,
                         uint8_t* sigs, uint8_t* ok);
 int sbv_p256_sign_batch_dev(const void* d_keys, uint32_t n_keys, const void* d_key_index, const void* d_digests, size_t n,

@@ -13,6 +13,7 @@ the source under test.  Used by both backends of the library: 0 = host loop (CPU
 """
 import ctypes
 import hashlib
+import hmac
 import os
 import random
 import subprocess
@@ -25,6 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import ed25519_py as ed  # noqa: E402
 import k256_py as kc  # noqa: E402
 import p256_py as ec  # noqa: E402
+import p256_sign_cases as sign_cases  # noqa: E402
 
 SEED = 0xD3C0DE
 M29 = (1 << 29) - 1
@@ -1214,6 +1216,101 @@ def chk_sha512_ram(rec, out):
     assert got == hashlib.sha512(data).digest()
 
 
+# ---- the P-256 signer's helpers (sha256_dev.h, hmac_sha256_dev.h, p256_sign.h) -----------------------------------------------------
+SHA256_LENS = [0, 1, 54, 55, 56, 57, 63, 64, 65, 118, 119, 120, 127, 128, 1023, 1024]
+
+
+def gen_sha256_msg(rng, n):
+    recs = []
+    for mlen in SHA256_LENS + [rng.randrange(1025) for _ in range(n)]:
+        data = rng.randbytes(mlen) + b"\xa5" * (1024 - mlen)          # what lies behind the message must not be hashed
+        recs.append([mlen] + list(np.frombuffer(data, dtype="<u4").astype(np.int64)))
+    return recs
+
+
+def chk_sha256_msg(rec, out):
+    data = np.array(rec[1:], dtype=np.int64).astype("<u4").tobytes()[:rec[0]]
+    assert be_bytes(out) == hashlib.sha256(data).digest()
+
+
+def be_words(b):
+    """bytes -> big-endian word values, as the signer's lanes hold K, V, x and h"""
+    return [int.from_bytes(b[i:i + 4], "big") for i in range(0, len(b), 4)]
+
+
+def be_bytes(ws):
+    return b"".join(u(w).to_bytes(4, "big") for w in ws)
+
+
+def _mac256(key, data):
+    return hmac.new(key, data, hashlib.sha256).digest()
+
+
+HMAC_EDGE = [bytes(32), b"\xff" * 32]
+
+
+def hmac_kv(rng, n):
+    """(K, V): every pairing of the all-zero and all-0xFF strings, then n random ones"""
+    return [(k, v) for k in HMAC_EDGE for v in HMAC_EDGE] + [(rng.randbytes(32), rng.randbytes(32)) for _ in range(n)]
+
+
+def gen_hmac_v(rng, n):
+    return [be_words(k) + be_words(v) for k, v in hmac_kv(rng, n)]
+
+
+def chk_hmac_v(rec, out):
+    assert be_bytes(out) == _mac256(be_bytes(rec[:8]), be_bytes(rec[8:16]))
+
+
+def gen_hmac_v_tag(rng, n):
+    """every edge (K, V) under tags 0, 1, 0xFF and both shapes; the random ones draw a tag and a shape.  With tail_only set, x and h
+    hold garbage that must not be read."""
+    recs = []
+    kvs = hmac_kv(rng, n)
+    for i, (k, v) in enumerate(kvs):
+        for tag, tail in ([(t, s) for t in (0, 1, 0xFF) for s in (0, 1)] if i < 4 else [(rng.choice([0, 1, 0xFF]), rng.randrange(2))]):
+            x, h = (rng.choice(HMAC_EDGE + [rng.randbytes(32)]) for _ in range(2))
+            recs.append(be_words(k) + be_words(v) + [tag] + be_words(x) + be_words(h) + [tail])
+    return recs
+
+
+def chk_hmac_v_tag(rec, out):
+    msg = be_bytes(rec[8:16]) + bytes([rec[16]])
+    if not rec[33]:
+        msg += be_bytes(rec[17:33])
+    assert be_bytes(out) == _mac256(be_bytes(rec[:8]), msg)
+
+
+SIGN_EDGE_KEYS = [1, 2, N - 2, N - 1]
+
+
+def gen_sign29_finish(rng, n):
+    """x | d | k | e, plain integers: x < p, d and k in [1, N-1], e < N.  x around N (x = N gives r = 0), a triple with
+    e + r d = 0 mod N (s = 0) and its neighbour e + 1, e = N - 1 with r d = N - 1 (the lazily added e + r d at its largest), the edge
+    keys as d and k under e of {0, 1, N-1}, 200 seeded cases, then n random ones"""
+    quads = [(x, rng.randrange(1, N), rng.randrange(1, N), rng.randrange(N)) for x in (1, N - 1, N, N + 1, P - 1)]
+    for x in (rng.randrange(1, N), rng.randrange(N + 1, P)):                # r = x and r = x - N
+        r, d, k = x % N, rng.randrange(1, N), rng.randrange(1, N)
+        e0 = (N - r * d % N) % N
+        quads += [(x, d, k, e0), (x, d, k, (e0 + 1) % N)]
+        quads.append((x, (N - 1) * pow(r, -1, N) % N, k, N - 1))                # r d = N - 1 and e = N - 1
+    quads += [(rng.randrange(1, P), d, k, e) for d in SIGN_EDGE_KEYS for k in SIGN_EDGE_KEYS for e in (0, 1, N - 1)]
+    seeded = random.Random(0x29F1)
+    quads += [(seeded.randrange(1, P), seeded.randrange(1, N), seeded.randrange(1, N), seeded.randrange(N)) for _ in range(200)]
+    quads += [(rng.randrange(1, P), rng.randrange(1, N), rng.randrange(1, N), rng.randrange(N)) for _ in range(n)]
+    return [words(x) + words(d) + words(k) + words(e) for x, d, k, e in quads]
+
+
+def chk_sign29_finish(rec, out):
+    x, d, k, e = (wval(rec[8 * i:8 * i + 8]) for i in range(4))
+    want = sign_cases.finish(x, d, k, e)
+    if want is None:
+        assert x == N or (e + x % N * d) % N == 0, "the reference refuses a case that has r != 0 and s != 0"
+        assert [u(v) for v in out] == [0] * 17, "a refused case must answer all zero"
+    else:
+        assert (wval(out[:8]), wval(out[8:16]), u(out[16])) == (want[0], want[1], 1)
+
+
 # ---- secp256k1 (k256_fe.h, k256_sc.h, k256_core.h) ---------------------------------------------------------------------------------
 K_TOP_LO, K_TOP_HI = -(1 << 20), (1 << 24) + (1 << 20)          # limb 8 of a reduced value
 
@@ -1669,7 +1766,7 @@ CROSS_LANE = ["x_keychain29", "x_edchain", "x_k256chain", "x_shfl_sum"]
 SLOW = {"f29_inv", "f29_inv_ct", "s29_inv", "s29_inv_ct", "sc_inv", "sc_inv_gcd", "fe_inv_gcd", "modinv30", "modinv30_ct",
         "pt29_dbl", "pt29_madd", "pt29_add", "pt29_mdbl", "pt29_mdbl_a", "pt29_dbl_jac", "pt29_dbl_jacx", "pt29_madd_jacx",
         "apt29_add_with_inverse", "pt29_rx_matches", "fe25_inv", "fe25_inv_gcd", "fe25_pow22523", "ed_dbl", "ed_add_pniels",
-        "ed_add_aniels", "ed_decompress", "ed_encoding_matches", "sha512_ram", "kfe_inv", "ksc_inv", "kpt_dbl", "kpt_madd", "k256_on_curve"}
+        "ed_add_aniels", "ed_decompress", "ed_encoding_matches", "sha512_ram", "sha256_msg", "sign29_finish", "kfe_inv", "ksc_inv", "kpt_dbl", "kpt_madd", "k256_on_curve"}
 
 GEN = {k[4:]: v for k, v in list(globals().items()) if k.startswith("gen_") and callable(v)}
 CHK = {k[4:]: v for k, v in list(globals().items()) if k.startswith("chk_") and callable(v)}

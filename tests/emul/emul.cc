@@ -1539,4 +1539,70 @@ void sbve_p256_sign_batch(const uint8_t* keys, uint32_t n_keys, const uint32_t* 
     }
 }
 
+// sign29_with_nonce on big-endian d, k, e (d in [1, N-1], e < N): 1 and r | s, or 0 and nothing written
+int sbve_p256_sign_with_nonce(const uint8_t d_be[32], const uint8_t k_be[32], const uint8_t e_be[32], uint8_t rs[64]) {
+    u256 d, k, e, r, s;
+    from_be32(d, d_be); from_be32(k, k_be); from_be32(e, e_be);
+    if (!sign29_with_nonce(d, k, e, g16rtab(), r, s)) return 0;
+    for (int i = 0; i < 32; ++i) {
+        rs[i] = (uint8_t)(r.v[7 - i / 4] >> (8 * (3 - i % 4)));
+        rs[32 + i] = (uint8_t)(s.v[7 - i / 4] >> (8 * (3 - i % 4)));
+    }
+    return 1;
+}
+
 }  // extern "C"
+
+#ifdef SBV_EMUL_MAIN
+// With -DSBV_EMUL_MAIN the file is a program of its own (so that a sanitizer build needs nothing loaded into an interpreter):
+//     emul CASES
+// CASES holds one P-256 signing case per line, three hex fields separated by blanks: private key, digest, r | s ("-" when the key is
+// rejected: the lane must then answer 64 zero bytes and ok = 0).  Every case is signed twice through sbve_p256_sign_batch, case i
+// under key i: once with a null key index and once with an explicit one.  Exit status 0 = every byte matched.
+#include <stdio.h>
+static bool unhex(const char* s, uint8_t* out, size_t want) {
+    if (!strcmp(s, "-")) { memset(out, 0, want); return true; }
+    if (strlen(s) != 2 * want) return false;
+    for (size_t i = 0; i < want; ++i) {
+        unsigned v;
+        if (sscanf(s + 2 * i, "%2x", &v) != 1) return false;
+        out[i] = (uint8_t)v;
+    }
+    return true;
+}
+
+int main(int argc, char** argv) {
+    if (argc != 2) { fprintf(stderr, "usage: %s CASES\n", argv[0]); return 2; }
+    FILE* f = fopen(argv[1], "r");
+    if (!f) { perror(argv[1]); return 2; }
+    std::vector<uint8_t> keys, digs, want, want_ok;
+    static char a[70], b[70], c[140];
+    size_t n = 0;
+    while (fscanf(f, "%69s %69s %139s", a, b, c) == 3) {
+        uint8_t key[32], dig[32], sig[64];
+        if (!unhex(a, key, 32) || !unhex(b, dig, 32) || !unhex(c, sig, 64)) { fprintf(stderr, "case %zu is malformed\n", n); return 2; }
+        keys.insert(keys.end(), key, key + 32);
+        digs.insert(digs.end(), dig, dig + 32);
+        want.insert(want.end(), sig, sig + 64);
+        want_ok.push_back(strcmp(c, "-") != 0);
+        ++n;
+    }
+    fclose(f);
+    if (n == 0) { fprintf(stderr, "no cases\n"); return 2; }
+    size_t bad = 0;
+    std::vector<uint32_t> index(n);
+    for (size_t i = 0; i < n; ++i) index[i] = (uint32_t)i;
+    for (int pass = 0; pass < 2; ++pass) {
+        std::vector<uint8_t> sigs(64 * n, 0xA5), ok(n, 0xA5);
+        sbve_p256_sign_batch(keys.data(), (uint32_t)n, pass ? index.data() : nullptr, digs.data(), n, sigs.data(), ok.data());
+        for (size_t i = 0; i < n; ++i)
+            if (ok[i] != want_ok[i] || memcmp(&sigs[64 * i], &want[64 * i], 64)) {
+                if (bad++ < 8) fprintf(stderr, "case %zu, pass %d: the signature differs\n", i, pass);
+            }
+    }
+    printf("%zu cases, %zu differ\n", n, bad);
+    free(g_gc_tab);
+    g_gc_tab = nullptr;
+    return bad ? 1 : 0;
+}
+#endif

@@ -23,6 +23,7 @@
 #include "../consensus_amd/csrc/p256_pt29.h"
 #include "../consensus_amd/csrc/p256_sc29.h"
 #include "../consensus_amd/csrc/p256_keytab29.h"
+#include "../consensus_amd/csrc/p256_sign.h"
 #include "../consensus_amd/csrc/ed25519_core.h"
 #include "../consensus_amd/csrc/ed25519_group.h"
 #include "../consensus_amd/csrc/sha512_dev.h"
@@ -32,7 +33,8 @@
 using namespace sbv;
 
 // name, words in, words out.  Layouts: f = fe29 / kfe (9 limbs), w = 8 words, e = fe25 (10 limbs), xyzz = X Y ZZ ZZZ inf (37),
-// jac = X Y Z (27), jacf / kjpt = X Y Z inf (28), ept / pniels = 40 limbs, flags and counts one word each.
+// jac = X Y Z (27), jacf / kjpt = X Y Z inf (28), ept / pniels = 40 limbs, flags and counts one word each.  The P-256 signer's
+// helpers (sha256_msg, hmac_v, hmac_v_tag, sign29_finish: p256_sign.h and below) state their records next to their code.
 #define SBVD_OPS(X) \
     X(f29_mul, 18, 9) X(f29_sqr, 9, 9) X(f29_mulx, 18, 9) X(f29_sqrx, 9, 9) X(f29_mul_sub_mul, 36, 9) X(f29_sqr_sub_val, 18, 9) \
     X(f29_canon, 9, 9) X(f29_norm, 9, 9) X(f29_norm_red, 9, 9) X(f29_is_zero, 9, 1) X(f29_maybe_zero, 9, 1) X(f29_pack, 9, 8) \
@@ -40,6 +42,7 @@ using namespace sbv;
     X(f29_mulchain, 19, 9) \
     X(s29_mul, 18, 9) X(s29_canon, 9, 9) X(s29_inv, 9, 9) X(s29_inv_ct, 9, 9) X(sc_mul, 16, 8) X(sc_inv, 8, 8) X(sc_inv_gcd, 8, 8) \
     X(fe_inv_gcd, 8, 8) X(modinv30, 9, 8) X(modinv30_ct, 9, 8) \
+    X(sha256_msg, 257, 8) X(hmac_v, 16, 8) X(hmac_v_tag, 34, 8) X(sign29_finish, 32, 17) \
     X(pt29_dbl, 37, 37) X(pt29_madd, 56, 37) X(pt29_add, 74, 37) X(pt29_mdbl, 18, 37) X(pt29_mdbl_a, 27, 37) X(pt29_dbl_jac, 27, 27) \
     X(pt29_dbl_jacx, 28, 28) X(pt29_madd_jacx, 47, 28) X(apt29_add_with_inverse, 45, 18) X(pt29_rx_matches, 45, 1) \
     X(fe25_mul, 20, 10) X(fe25_sqr, 10, 10) X(fe25_carry, 10, 10) X(fe25_add, 20, 10) X(fe25_sub, 20, 10) X(fe25_neg, 10, 10) \
@@ -132,6 +135,26 @@ SBV_HD void run_op(const u32* in, u32* out) {
     else if constexpr (OP == OP_fe_inv_gcd) { fe z; fe_inv_gcd(z, ldw(in)); stw(out, z); }
     else if constexpr (OP == OP_modinv30) { u256 z; modinv30(z, ldw(in + 1), modinfo_of(in[0])); stw(out, z); }
     else if constexpr (OP == OP_modinv30_ct) { u256 z; modinv30_ct(z, ldw(in + 1), modinfo_of(in[0])); stw(out, z); }
+    else if constexpr (OP == OP_sha256_msg) {                   // in: length | message (SBVD_SHA_MAX_MSG bytes, little-endian words); out: the digest's big-endian words
+        const size_t mlen = in[0] <= SBVD_SHA_MAX_MSG ? in[0] : SBVD_SHA_MAX_MSG;
+        sha256_msg(reinterpret_cast<const uint8_t*>(in + 1), mlen, out);
+    }
+    else if constexpr (OP == OP_hmac_v) {                       // in: K | V (big-endian words); out: HMAC(K, V)
+        hmac_key hk;
+        hmac_set_key(hk, in);
+        hmac_v(hk, in + 8, out);
+    }
+    else if constexpr (OP == OP_hmac_v_tag) {                   // in: K | V | tag | x | h | tail_only; out: HMAC(K, V || tag [|| x || h])
+        hmac_key hk;
+        hmac_set_key(hk, in);
+        hmac_v_tag(hk, in + 8, in[16], in + 17, in + 25, in[33] != 0, out);
+    }
+    else if constexpr (OP == OP_sign29_finish) {                // in: x | d | k | e (plain integers); out: r | s | ok, all zero when not ok
+        u256 r, s;
+        const bool ok = sign29_finish(ldw(in), ldw(in + 8), ldw(in + 16), ldw(in + 24), r, s);
+        for (int i = 0; i < 8; ++i) { out[i] = ok ? r.v[i] : 0u; out[8 + i] = ok ? s.v[i] : 0u; }
+        out[16] = ok ? 1u : 0u;
+    }
     else if constexpr (OP == OP_pt29_dbl) { xyzz R = ldxyzz(in); pt29_dbl(R); stxyzz(out, R); }
     else if constexpr (OP == OP_pt29_madd) { xyzz R = ldxyzz(in); apt29 q; q.x = ld29(in + 37); q.y = ld29(in + 46); pt29_madd(R, q, in[55] != 0); stxyzz(out, R); }
     else if constexpr (OP == OP_pt29_add) { xyzz R = ldxyzz(in); const xyzz Q = ldxyzz(in + 37); pt29_add(R, Q); stxyzz(out, R); }
