@@ -672,6 +672,71 @@ def debug_secp256k1_schnorr_op(op: int, records):
     return [out.raw[128 * i:128 * i + 128] for i in range(n)]
 
 
+def secp256k1_schnorr_lift_keys(pks: bytes):
+    """sbv_secp256k1_schnorr_lift_keys: x-only 32-byte keys -> (keys64, ok): x | y of lift_x per key in one bytes object, the bytes
+    secp256k1_register_keys takes, and ok[i] = 1 per key on the curve (otherwise x | 32 zero bytes, which registers as an invalid slot)."""
+    lib = load()
+    m = len(pks) // 32
+    if len(pks) != 32 * m:
+        raise ValueError("secp256k1_schnorr_lift_keys: pks is not a multiple of 32 bytes")
+    lib.sbv_secp256k1_schnorr_lift_keys.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p]
+    keys, ok = ctypes.create_string_buffer(max(1, 64 * m)), ctypes.create_string_buffer(max(1, m))
+    _check(lib.sbv_secp256k1_schnorr_lift_keys(bytes(pks), m, keys, ok))
+    return keys.raw[:64 * m], ok.raw[:m]
+
+
+def secp256k1_schnorr_lift_keys_stream(d_pks_ptr: int, m: int, d_keys64_ptr: int, d_ok_ptr: int, stream: int = 0) -> None:
+    """device pointers (d_ok_ptr may be 0); asynchronous on `stream` under the stream contract of the _dev entries (include/sbv.h)"""
+    lib = load()
+    lib.sbv_secp256k1_schnorr_lift_keys_stream.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_schnorr_lift_keys_stream(d_pks_ptr or None, m, d_keys64_ptr or None, d_ok_ptr or None, stream or None))
+
+
+def secp256k1_schnorr_register_keys(pks: bytes):
+    """lift + register: x-only 32-byte keys -> (slots, ok).  The slots are those of secp256k1_register_keys (one registry for ECDSA and
+    Schnorr); a key off the curve gets a slot too, an invalid one (ok[i] = 0), against which every signature is rejected."""
+    keys, ok = secp256k1_schnorr_lift_keys(pks)
+    return secp256k1_register_keys([keys[64 * i:64 * i + 64] for i in range(len(ok))]), ok
+
+
+def secp256k1_schnorr_verify_keyed(msgs: bytes, sigs: bytes, slots) -> bytes:
+    """sbv_secp256k1_schnorr_verify_keyed: BIP-340 verification of n signatures (R.x | s) of 32-byte messages under registered keys
+    (slots of secp256k1_register_keys / secp256k1_schnorr_register_keys).  Returns ok: one byte per item, 1 = valid; byte for byte
+    secp256k1_schnorr_verify with pk = the slot's Qx."""
+    lib = load()
+    n = len(sigs) // 64
+    if len(sigs) != 64 * n or len(msgs) != 32 * n or len(slots) != n:
+        raise ValueError("secp256k1_schnorr_verify_keyed: msgs, sigs and slots disagree about n")
+    lib.sbv_secp256k1_schnorr_verify_keyed.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p]
+    arr = (ctypes.c_uint32 * max(1, n))(*slots)
+    ok = ctypes.create_string_buffer(max(1, n))
+    _check(lib.sbv_secp256k1_schnorr_verify_keyed(bytes(msgs), bytes(sigs), arr, n, ok))
+    return ok.raw[:n]
+
+
+def secp256k1_schnorr_verify_keyed_stream(d_msgs_ptr: int, d_sigs_ptr: int, d_slots_ptr: int, n: int, d_ok_ptr: int, stream: int = 0) -> None:
+    """device pointers; asynchronous on `stream` under the stream contract of the _dev entries (include/sbv.h); no workspace"""
+    lib = load()
+    lib.sbv_secp256k1_schnorr_verify_keyed_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                              ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_schnorr_verify_keyed_stream(d_msgs_ptr or None, d_sigs_ptr or None, d_slots_ptr or None, n, d_ok_ptr or None,
+                                                         stream or None))
+
+
+def debug_secp256k1_schnorr_keyed_op(op: int, records, slots):
+    """sbv_debug_secp256k1_schnorr_keyed_op (test only): one case per lane, 192-byte input records u1 | u2 and a slot each -> 128-byte
+    output records x | y | . | ok of u1 G + u2 Q_slot (include/sbv.h)"""
+    lib = load()
+    n = len(records)
+    if len(slots) != n:
+        raise ValueError("debug_secp256k1_schnorr_keyed_op: records and slots disagree about n")
+    lib.sbv_debug_secp256k1_schnorr_keyed_op.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+    arr = (ctypes.c_uint32 * max(1, n))(*slots)
+    out = ctypes.create_string_buffer(max(1, 128 * n))
+    _check(lib.sbv_debug_secp256k1_schnorr_keyed_op(op, b"".join(records), arr, out, n))
+    return [out.raw[128 * i:128 * i + 128] for i in range(n)]
+
+
 def ed25519_expand_keys(seeds):
     """sbv_ed25519_expand_keys: 32-byte seeds (a list, or their concatenation) -> (expanded, pks): the 96-byte expanded records
     (a mod L | prefix | A_enc, as secret as the seeds) in one bytes object, and the list of 32-byte public keys."""

@@ -7,6 +7,11 @@
 
 namespace sbv {
 
+// The wave rule of the kernels that walk registered slots (k_k256_keyed_verify; k256_schnorr_keyed_kernels.hip): the wavefront takes the
+// 16-bit combs when a lane of it is live and every live lane's slot owns one (lane_wide = k256_keyed_slot_wide); dead lanes never
+// decide.  ONE function for every such kernel.
+__device__ inline bool k256_keyed_wave_wide(bool live, bool lane_wide) { return __ballot(live) != 0 && __ballot(live && !lane_wide) == 0; }
+
 // stage A + stage B of n keyed records (96 bytes, 16-byte aligned) on `stream`; s: the limb-major scratch planes, d_gcomb: the
 // `gcomb_bits`-wide comb of G of the grouped step.  after_prep (optional) is recorded between the stages.
 hipError_t launch_k256_verify_keyed(const uint8_t* d_recs, const u32* d_slots, size_t n, const Scratch& s, const K256KeyedRegistry& reg,

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(SBV_VERIFY_BLOCK, 2) void k_k256_keyed_verify(Scrat
     const bool live = in && k256_keyed_live(s, ii, slot, reg);
     // the ballot: dead lanes never decide their wavefront
     const bool lane_wide = k256_keyed_slot_wide(slot, reg);
-    const bool wide = __ballot(live) != 0 && __ballot(live && !lane_wide) == 0;
+    const bool wide = k256_keyed_wave_wide(live, lane_wide);
     const bool accept = k256_keyed_verify_lane(s, ii, slot, live, reg, gc, wide);
     const unsigned long long m = __ballot(accept);
     const int lane = threadIdx.x & 63;

@@ -38,6 +38,7 @@
 #include "k256_sign_kernels.h"
 #include "k256_recover_kernels.h"
 #include "k256_schnorr_kernels.h"
+#include "k256_schnorr_keyed_kernels.h"
 
 namespace {
 
@@ -3115,6 +3116,153 @@ extern "C" int sbv_debug_secp256k1_schnorr_op(int op, const uint8_t* in, uint8_t
     }
     if (d_out) (void)hipFree(d_out);
     if (d_work) (void)hipFree(d_work);
+    return rc;
+}
+
+// ---- BIP-340 Schnorr against registered secp256k1 keys (k256_schnorr_keyed.h, k256_schnorr_keyed_kernels.hip) -----------------
+// The slots are those of sbv_secp256k1_register_keys: the entries take the context and the registry as sbv_secp256k1_verify_batch_keyed
+// and _dev do (K256Reg::ensure, the comb of G at its configured bits, the registry's view at enqueue time) and add the registry's key
+// array, which the challenge reads.  One kernel per call, no Scratch planes, no chunk loop: nothing of the context is written, so the
+// _stream form has nothing to order against other calls (c.busy is neither waited for nor recorded) and reads and writes the caller's
+// buffers on the caller's stream alone.  The registry's arrays only change under the context's lock, and a registration or widening
+// that replaces them synchronises the device first (local_reg_reserve, local_wide_reserve), so a queued call keeps valid tables.
+// n <= SBV_K256_SCHNORR_KEYED_MAX_N = 2^32 items per call (one lane per item: the grid's bound), no 2^21 chunking.
+// Lifting is stateless: no table at all.
+namespace {
+int schnorr_keyed_check_n(size_t n) {
+    if (n <= SBV_K256_SCHNORR_KEYED_MAX_N) return SBV_OK;
+    g_err = "batch larger than 2^32: split it";
+    return SBV_EINVAL;
+}
+}  // namespace
+
+extern "C" int sbv_secp256k1_schnorr_lift_keys_stream(const void* d_pks, size_t m, void* d_keys64, void* d_ok, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!d_pks || !d_keys64) { g_err = "null pointer"; return SBV_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(d_pks) | reinterpret_cast<uintptr_t>(d_keys64)) & 3) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
+    if (schnorr_keyed_check_n(m) != SBV_OK) return SBV_EINVAL;
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_schnorr_lift(static_cast<const uint8_t*>(d_pks), m, static_cast<uint8_t*>(d_keys64), static_cast<uint8_t*>(d_ok),
+                                                       static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_schnorr_lift_keys(const uint8_t* pks, size_t m, uint8_t* keys64, uint8_t* ok) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!pks || !keys64) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (schnorr_keyed_check_n(m) != SBV_OK) return SBV_EINVAL;
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = SBV_OK;
+    uint8_t *d_pk = nullptr, *d_keys = nullptr, *d_ok = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_pk, m * 32))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_keys, m * 64))) break;
+        if (ok && fail(SBV_ENOMEM, hipMalloc(&d_ok, m))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_pk, pks, m * 32, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_lift(d_pk, m, d_keys, d_ok, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(keys64, d_keys, m * 64, hipMemcpyDeviceToHost, c.stream))) break;
+        if (ok && fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, m, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);       // nothing of this call is in flight when its buffers go
+    if (d_pk) (void)hipFree(d_pk);
+    if (d_keys) (void)hipFree(d_keys);
+    if (d_ok) (void)hipFree(d_ok);
+    return rc;
+}
+
+extern "C" int sbv_secp256k1_schnorr_verify_keyed_stream(const void* d_msgs, const void* d_sigs, const void* d_slots, size_t n, void* d_ok, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!d_msgs || !d_sigs || !d_slots || !d_ok) { g_err = "null pointer"; return SBV_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(d_msgs) | reinterpret_cast<uintptr_t>(d_sigs) | reinterpret_cast<uintptr_t>(d_slots)) & 3) {
+        g_err = "misaligned device pointer";
+        return SBV_EINVAL;
+    }
+    if (schnorr_keyed_check_n(n) != SBV_OK) return SBV_EINVAL;
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (c.k256reg.nkeys == 0) {      // every slot is out of range: every item is a reject
+        HIP_TRY(SBV_EDEVICE, hipMemsetAsync(d_ok, 0, n, stream));
+        return SBV_OK;
+    }
+    const int rc = K256Reg::ensure(c);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_schnorr_verify_keyed(static_cast<const uint8_t*>(d_msgs), static_cast<const uint8_t*>(d_sigs),
+                                                               static_cast<const u32*>(d_slots), n, k256_reg_view(c), c.k256reg.kkeys, c.d_k256_gcomb,
+                                                               c.k256_gbits, static_cast<uint8_t*>(d_ok), stream));
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_schnorr_verify_keyed(const uint8_t* msgs, const uint8_t* sigs, const uint32_t* slots, size_t n, uint8_t* ok) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!msgs || !sigs || !slots || !ok) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (schnorr_keyed_check_n(n) != SBV_OK) return SBV_EINVAL;
+    if (c.k256reg.nkeys == 0) { memset(ok, 0, n); return SBV_OK; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = K256Reg::ensure(c);
+    if (rc != SBV_OK) return rc;
+    // buffers of the call's own size, released before returning, as sbv_secp256k1_schnorr_verify's
+    uint8_t *d_msg = nullptr, *d_sig = nullptr, *d_ok = nullptr;
+    u32* d_sl = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_msg, n * 32))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_sl, n * sizeof(u32)))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_msg, msgs, n * 32, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_sig, sigs, n * 64, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_sl, slots, n * sizeof(u32), hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_verify_keyed(d_msg, d_sig, d_sl, n, k256_reg_view(c), c.k256reg.kkeys, c.d_k256_gcomb, c.k256_gbits,
+                                                                    d_ok, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);       // nothing of this call is in flight when its buffers go
+    if (d_msg) (void)hipFree(d_msg);
+    if (d_sig) (void)hipFree(d_sig);
+    if (d_sl) (void)hipFree(d_sl);
+    if (d_ok) (void)hipFree(d_ok);
+    return rc;
+}
+
+// Test only (include/sbv.h): one case of the keyed walk per lane: 192 bytes in (u1 | u2), a slot, 128 bytes out.
+extern "C" int sbv_debug_secp256k1_schnorr_keyed_op(int op, const uint8_t* in, const uint32_t* slots, uint8_t* out, size_t n) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (op != 0) { g_err = "unknown operation"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!in || !slots || !out || n > 65536) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
+    if (c.k256reg.nkeys == 0) { memset(out, 0, n * 128); return SBV_OK; }      // every slot is out of range
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    int rc = K256Reg::ensure(c);
+    if (rc != SBV_OK) return rc;
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    u32* d_sl = nullptr;
+    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
+    do {
+        if (fail(SBV_ENOMEM, hipMalloc(&d_in, n * 192))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_out, n * 128))) break;
+        if (fail(SBV_ENOMEM, hipMalloc(&d_sl, n * sizeof(u32)))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_in, in, n * 192, hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_sl, slots, n * sizeof(u32), hipMemcpyHostToDevice, c.stream))) break;
+        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_keyed_op(d_in, d_sl, d_out, n, k256_reg_view(c), c.d_k256_gcomb, c.k256_gbits, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipMemcpyAsync(out, d_out, n * 128, hipMemcpyDeviceToHost, c.stream))) break;
+        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
+    } while (false);
+    if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (d_sl) (void)hipFree(d_sl);
     return rc;
 }
 

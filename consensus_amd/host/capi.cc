@@ -92,6 +92,12 @@ int sbvh_recover_signers(void* h, const uint8_t* sigs65, const uint8_t* digests,
 int sbvh_verify_schnorr(void* h, const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok) {
     return ((VHandle*)h)->v->VerifySchnorr(pks, msgs, sigs, n, ok).code;
 }
+// Verifier::RegisterSchnorrKey: an x-only key -> its slot (-1: no registry or another scheme); Verifier::VerifySchnorrKeyed: n x 32 bytes
+// + n x 64 bytes R.x | s + n slots -> n bytes; returns the status code
+long sbvh_register_schnorr_key(void* h, const uint8_t* pk32) { return ((VHandle*)h)->v->RegisterSchnorrKey(pk32); }
+int sbvh_verify_schnorr_keyed(void* h, const uint8_t* msgs, const uint8_t* sigs, const uint32_t* slots, size_t n, uint8_t* ok) {
+    return ((VHandle*)h)->v->VerifySchnorrKeyed(msgs, sigs, slots, n, ok).code;
+}
 // Backend::schnorr_sign_k256 of the handle's backend: records from sbvh_k256_schnorr_expand (or the device entry); 0 or the error code
 int sbvh_sign_schnorr(void* h, const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs, const uint8_t* aux,
                       size_t n, uint8_t* sigs, uint8_t* ok) {
@@ -291,6 +297,7 @@ int sbvh_k256_schnorr_sign(const uint8_t rec[64], const uint8_t msg[32], const u
     return k256_schnorr_sign(rec, msg, aux, sig) ? 0 : -1;
 }
 int sbvh_k256_schnorr_verify(const uint8_t pk[32], const uint8_t msg[32], const uint8_t sig[64]) { return k256_schnorr_verify(pk, msg, sig) ? 0 : -1; }
+int sbvh_k256_schnorr_lift(const uint8_t pk[32], uint8_t key[64]) { return k256_schnorr_lift(pk, key) ? 0 : -1; }
 
 // ---- formats ---------------------------------------------------------------------------------------
 void sbvh_proposal_digest(const void* payload, size_t pl, const void* header, size_t hl, const void* meta, size_t ml,

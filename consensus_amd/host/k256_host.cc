@@ -11,6 +11,7 @@
 #include "../csrc/k256_core.h"
 #include "../csrc/k256_recover.h"
 #include "../csrc/k256_schnorr.h"
+#include "../csrc/k256_schnorr_keyed.h"
 #include "p256_host.h"
 
 namespace sbvhost {
@@ -211,6 +212,22 @@ bool k256_schnorr_verify(const uint8_t pk[32], const uint8_t msg[32], const uint
     k256_mul_u2Q(R, x, y, u2, strip);              // (n - e) P
     comb8_add(R, u1);                              // + s G
     return k256_schnorr_final(R, sw, qw);
+}
+
+bool k256_schnorr_lift(const uint8_t pk[32], uint8_t key[64]) {
+    u32 pw[8], kw[16];
+    words_from_be(pw, pk, 8);
+    const bool ok = k256_schnorr_lift_lane(pw, kw);
+    words_to_be(key, kw, 16);
+    return ok;
+}
+
+bool k256_schnorr_verify_keyed(const uint8_t key[64], const uint8_t msg[32], const uint8_t sig[64]) {
+    u32 kw[16];
+    memcpy(kw, key, 64);                           // k256_key_load_words swaps the bytes itself
+    kfe x, y;
+    if (!k256_key_load_words(kw, x, y)) return false;
+    return k256_schnorr_verify(key, msg, sig);
 }
 
 }  // namespace sbvhost

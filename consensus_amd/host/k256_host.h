@@ -17,5 +17,10 @@ bool k256_recover(const uint8_t rs[64], uint8_t recid, const uint8_t digest[32],
 bool k256_schnorr_expand(const uint8_t d_be[32], uint8_t rec[64]);
 bool k256_schnorr_sign(const uint8_t rec[64], const uint8_t msg[32], const uint8_t* aux, uint8_t sig[64]);
 bool k256_schnorr_verify(const uint8_t pk[32], const uint8_t msg[32], const uint8_t sig[64]);
+// BIP-340 against registered keys (include/sbv.h: sbv_secp256k1_schnorr_lift_keys, _verify_keyed).  lift: key = x | y of lift_x(pk), or
+// x | 32 zero bytes and false for a key off the curve.  verify_keyed: the verdict of the device entry for a slot that holds `key`
+// (Qx | Qy of either parity): false when the key is no curve point (an invalid slot), else k256_schnorr_verify under Qx.
+bool k256_schnorr_lift(const uint8_t pk[32], uint8_t key[64]);
+bool k256_schnorr_verify_keyed(const uint8_t key[64], const uint8_t msg[32], const uint8_t sig[64]);
 
 }  // namespace sbvhost

@@ -231,6 +231,10 @@ class SbvBackend : public Backend {
         if (rc_ != SBV_OK) return rc_;
         return sbv_secp256k1_schnorr_sign(expanded, n_keys, key_index, msgs, aux, n, sigs, ok);
     }
+    int schnorr_verify_keyed_k256(const uint8_t* msgs, const uint8_t* sigs, const uint32_t* slots, size_t n, uint8_t* ok) override {
+        if (rc_ != SBV_OK) return rc_;
+        return sbv_secp256k1_schnorr_verify_keyed(msgs, sigs, slots, n, ok);
+    }
     void* host_alloc(size_t bytes) override { return rc_ == SBV_OK ? sbv_host_alloc(bytes) : nullptr; }
     void host_free(void* p) override { sbv_host_free(p); }
     int verify_msgs_keyed(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff,
@@ -395,6 +399,21 @@ class CallbackBackend : public Backend {
         return verify_k256_keyed(rsh.data(), slots, n, bitmap);
     }
     std::vector<uint32_t> last_k256_slots() override { std::lock_guard<std::mutex> lk(mu_); return last_k256_slots_; }
+    // the CPU form of sbv_secp256k1_schnorr_verify_keyed: a loop over the host verifier under the slot's Qx; a slot out of range or a
+    // key that is no curve point is a reject
+    int schnorr_verify_keyed_k256(const uint8_t* msgs, const uint8_t* sigs, const uint32_t* slots, size_t n, uint8_t* ok) override {
+        if (!registry_) return -2;
+        std::vector<std::string> keys;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            keys = k256_keys_;
+        }
+        parallel_chunks(n, [&](size_t lo, size_t hi) {
+            for (size_t i = lo; i < hi; ++i)
+                ok[i] = slots[i] < keys.size() && k256_schnorr_verify_keyed((const uint8_t*)keys[slots[i]].data(), msgs + 32 * i, sigs + 64 * i) ? 1 : 0;
+        });
+        return 0;
+    }
     // the CPU form: a loop over the host recovery (k256_host.cc), which needs no callback
     int recover_k256(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) override {
         parallel_chunks(n, [&](size_t lo, size_t hi) {
@@ -1430,6 +1449,23 @@ Status Verifier::VerifySchnorr(const uint8_t* pks, const uint8_t* msgs, const ui
     if (!pks || !msgs || !sigs || !ok) return Status::Invalid("VerifySchnorr: null pointer");
     const int rc = co_.backend().schnorr_verify_k256(pks, msgs, sigs, n, ok);
     if (rc != 0) return Status::Unavailable("BIP-340 verification failed on the backend");
+    return Status::Ok();
+}
+
+long Verifier::RegisterSchnorrKey(const uint8_t pk[32]) {
+    if (!k256() || !pk) return -1;
+    uint8_t key[64];
+    (void)k256_schnorr_lift(pk, key);              // a key off the curve: x | 0^32, which registers as an invalid slot
+    return co_.backend().register_key_k256(key);
+}
+
+Status Verifier::VerifySchnorrKeyed(const uint8_t* msgs, const uint8_t* sigs, const uint32_t* slots, size_t n, uint8_t* ok) {
+    if (!k256()) return Status::Invalid("VerifySchnorrKeyed needs Scheme::SECP256K1");
+    if (n == 0) return Status::Ok();
+    if (!msgs || !sigs || !slots || !ok) return Status::Invalid("VerifySchnorrKeyed: null pointer");
+    const int rc = co_.backend().schnorr_verify_keyed_k256(msgs, sigs, slots, n, ok);
+    if (rc == -2) return Status::Unavailable("the backend has no secp256k1 key registry");
+    if (rc != 0) return Status::Unavailable("BIP-340 keyed verification failed on the backend");
     return Status::Ok();
 }
 

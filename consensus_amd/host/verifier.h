@@ -98,6 +98,12 @@ class Backend {
     virtual int schnorr_verify_k256(const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok);
     virtual int schnorr_sign_k256(const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs, const uint8_t* aux,
                                   size_t n, uint8_t* sigs, uint8_t* ok);
+    // BIP-340 against registered secp256k1 keys (include/sbv.h: sbv_secp256k1_schnorr_verify_keyed): messages n x 32, signatures n x 64
+    // and slots of register_key_k256 -> ok[i] = 1 per valid signature under the slot's Qx; an unknown or invalid slot is a reject.  -2
+    // when the backend has no registry; the callback backend loops over the host form, the GPU backend makes one device call.
+    virtual int schnorr_verify_keyed_k256(const uint8_t* msgs, const uint8_t* sigs, const uint32_t* slots, size_t n, uint8_t* ok) {
+        (void)msgs; (void)sigs; (void)slots; (void)n; (void)ok; return -2;
+    }
     virtual int verify_keyed(const uint8_t* rsh, const uint32_t* slots, size_t n, uint8_t* bitmap) {
         (void)rsh; (void)slots; (void)n; (void)bitmap; return -2;
     }
@@ -246,6 +252,13 @@ class Verifier {
     // pks = n x 32 bytes x-only keys, msgs = n x 32 bytes, sigs = n x 64 bytes R.x | s -> ok[i] = 1 per valid signature.  One backend
     // call (sbv_secp256k1_schnorr_verify on the device, a CPU loop otherwise).  INVALID under another scheme, UNAVAILABLE on a backend error.
     Status VerifySchnorr(const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok);
+    // Scheme::SECP256K1 only: BIP-340 against the backend's registered secp256k1 keys, for a fixed key set that signs again and again.
+    // RegisterSchnorrKey: an x-only key -> its slot in the registry RegisterConsenter / RegisterClient use on this curve (lift_x, then
+    // register_key_k256), -1 when the backend has no registry or the scheme is another; a key off the curve gets a slot too, against
+    // which every signature is rejected.  VerifySchnorrKeyed: msgs n x 32, sigs n x 64, slots n x u32 -> ok[i], one backend call
+    // (sbv_secp256k1_schnorr_verify_keyed on the device).  INVALID under another scheme, UNAVAILABLE without a registry or on an error.
+    long RegisterSchnorrKey(const uint8_t pk[32]);
+    Status VerifySchnorrKeyed(const uint8_t* msgs, const uint8_t* sigs, const uint32_t* slots, size_t n, uint8_t* ok);
     CoalescerStats stats() { return co_.stats(); }
     Scheme scheme() const { return opt_.scheme; }
 

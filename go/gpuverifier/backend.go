@@ -119,6 +119,18 @@ type K256Schnorr interface {
 	SignBatchSchnorr(keys [][32]byte, keyIndex []uint32, msgs [][32]byte, aux [][32]byte) (sigs [][64]byte, pks [][32]byte, ok []bool, err error)
 }
 
+// K256SchnorrKeyed is BIP-340 verification against registered secp256k1 keys (sbv_secp256k1_schnorr_lift_keys +
+// sbv_secp256k1_register_keys, sbv_secp256k1_schnorr_verify_keyed): for a fixed key set that signs again and again.
+// RegisterSchnorrKeys: slots[i] = the slot of the x-only key pks[i] in the registry of K256KeyRegistry (one registry for ECDSA and
+// Schnorr; WidenKeySecp256k1 works on these slots); onCurve[i] = false for a key that is no x of a curve point: it gets a slot too,
+// against which every signature is rejected.  VerifyBatchSchnorrKeyed: ok[i] = the verdict of BIP-340 "Verify" on msgs[i] and
+// sigs[i] = R.x|s under the key of slots[i]; an unknown slot is a reject.  An optional interface beside K256Schnorr, so that
+// existing backends need no change: callers type-assert.
+type K256SchnorrKeyed interface {
+	RegisterSchnorrKeys(pks [][32]byte) (slots []uint32, onCurve []bool, err error)
+	VerifyBatchSchnorrKeyed(msgs [][32]byte, sigs [][64]byte, slots []uint32) (ok []bool, err error)
+}
+
 // ErrNoBatchSigner: the backend has no batch signing entry (the pure-Go backend).
 var ErrNoBatchSigner = errors.New("gpuverifier: backend has no batch signer")
 

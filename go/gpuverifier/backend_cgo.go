@@ -704,6 +704,68 @@ func (b *gpuBackend) VerifyBatchSchnorr(pks [][32]byte, msgs [][32]byte, sigs []
 	return ok, nil
 }
 
+// RegisterSchnorrKeys: sbv_secp256k1_schnorr_lift_keys, then sbv_secp256k1_register_keys on the lifted keys, in one visit to the
+// device thread.
+func (b *gpuBackend) RegisterSchnorrKeys(pks [][32]byte) (slots []uint32, onCurve []bool, err error) {
+	m := len(pks)
+	if m == 0 {
+		return nil, nil, errors.New("gpuverifier: RegisterSchnorrKeys needs a key")
+	}
+	pb := make([]byte, 32*m)
+	for i := range pks {
+		copy(pb[32*i:], pks[i][:])
+	}
+	keys := make([]byte, 64*m)
+	flags := make([]byte, m)
+	slots = make([]uint32, m)
+	b.on(func() {
+		rc := C.sbv_secp256k1_schnorr_lift_keys(u8(pb), C.size_t(m), u8(keys), u8(flags))
+		if rc == 0 {
+			rc = C.sbv_secp256k1_register_keys(u8(keys), C.size_t(m), (*C.uint32_t)(unsafe.Pointer(&slots[0])))
+		}
+		if rc != 0 {
+			err = lastError()
+		}
+	})
+	if err != nil {
+		return nil, nil, err
+	}
+	onCurve = make([]bool, m)
+	for i := 0; i < m; i++ {
+		onCurve[i] = flags[i] != 0
+	}
+	return slots, onCurve, nil
+}
+
+// VerifyBatchSchnorrKeyed: sbv_secp256k1_schnorr_verify_keyed (one device call; nothing secret is involved).
+func (b *gpuBackend) VerifyBatchSchnorrKeyed(msgs [][32]byte, sigs [][64]byte, slots []uint32) (ok []bool, err error) {
+	n := len(sigs)
+	if n == 0 || len(msgs) != n || len(slots) != n {
+		return nil, errors.New("gpuverifier: VerifyBatchSchnorrKeyed needs one message and one slot per signature")
+	}
+	mb := make([]byte, 32*n)
+	sb := make([]byte, 64*n)
+	for i := 0; i < n; i++ {
+		copy(mb[32*i:], msgs[i][:])
+		copy(sb[64*i:], sigs[i][:])
+	}
+	flags := make([]byte, n)
+	b.on(func() {
+		rc := C.sbv_secp256k1_schnorr_verify_keyed(u8(mb), u8(sb), (*C.uint32_t)(unsafe.Pointer(&slots[0])), C.size_t(n), u8(flags))
+		if rc != 0 {
+			err = lastError()
+		}
+	})
+	if err != nil {
+		return nil, err
+	}
+	ok = make([]bool, n)
+	for i := 0; i < n; i++ {
+		ok[i] = flags[i] != 0
+	}
+	return ok, nil
+}
+
 // SignBatchSchnorr: sbv_secp256k1_schnorr_expand_keys, then sbv_secp256k1_schnorr_sign under the records (not constant-time — see
 // include/sbv.h).  The records are as secret as the keys and are zeroed with them.
 func (b *gpuBackend) SignBatchSchnorr(keys [][32]byte, keyIndex []uint32, msgs [][32]byte, aux [][32]byte) (sigs [][64]byte, pks [][32]byte, ok []bool, err error) {

@@ -352,6 +352,52 @@ sbv_secp256k1_schnorr_sign_stream(const void* d_expanded, uint32_t n_keys, const
 int
 sbv_debug_secp256k1_schnorr_op(int op, const uint8_t* in, uint8_t* out, size_t n);
 
+/* BIP-340 Schnorr verification against REGISTERED secp256k1 keys: the fixed key set of a consenter group, verified from the combs the
+ * registry of sbv_secp256k1_register_keys holds in device memory.  There is no second registry: a slot is a slot of that registry, one
+ * slot serves the ECDSA keyed entries and this one, and sbv_secp256k1_wide_keys / sbv_secp256k1_widen_keys / sbv_secp256k1_clear_keys
+ * work unchanged.
+ *   sbv_secp256k1_schnorr_lift_keys      pks: m x 32 bytes (x-only).  keys64: m x 64 bytes x | y of lift_x(pk), the point with that x
+ *                                        and even y — the bytes sbv_secp256k1_register_keys takes.  ok: m bytes, or NULL when not
+ *                                        wanted.  For pk >= p or pk^3 + 7 no square: ok[i] = 0 and keys64 = pk | 32 zero bytes.  No
+ *                                        curve point has y = 0, so registering such an output gives an INVALID slot, and every
+ *                                        signature against it is rejected: the verdict of sbv_secp256k1_schnorr_verify for that key.
+ *                                        Registration of an x-only key is lift_keys followed by register_keys.
+ *   sbv_secp256k1_schnorr_verify_keyed   msgs: n x 32, sigs: n x 64 (R.x | s), slots: n x u32, ok: n bytes (0 or 1, not a bitmap).
+ *                                        ok[i] is byte for byte what sbv_secp256k1_schnorr_verify answers for the same message and
+ *                                        signature with pk = the first 32 bytes (Qx) of the slot's key as registered.  The registered
+ *                                        Qy may have either parity (a key registered for ECDSA serves as it is): BIP-340's key is the
+ *                                        point with even y, P = Q or -Q, and R = s G - e P is walked as s G + u2 Q with u2 = n - e for
+ *                                        an even Qy and u2 = e for an odd one.  An out-of-range slot, an invalid slot, r >= p, s >= n
+ *                                        and R at infinity are rejects, not errors.  With no registered key every item is a reject.
+ * Per item: two SHA-256 compressions, the comb of G, the slot's comb (8-bit, or 16-bit when every live lane of the wavefront owns
+ * one, the rule of sbv_secp256k1_verify_batch_keyed) and one field inversion; no square root, no doubling, no workspace, no cap on
+ * the grid.  n (m) <= 2^32 per call; there is no 2^21 chunking because no scratch plane of the context is used.
+ * The host-pointer forms use device buffers of the call's own size, wait for the result and free them.  The `_stream` forms take
+ * device pointers, launch on `hip_stream` and return without synchronising, under the stream contract of the `_dev` entries
+ *  for every buffer they name.  They write no state of the library: the registry's tables and the comb of G
+ * are read-only, and a registration or widening that replaces the registry's arrays synchronises the device before it frees the old
+ * ones, so a queued call stays valid, as for sbv_secp256k1_verify_batch_keyed_dev.  The first secp256k1 call of the process uploads
+ * the comb of G synchronously, and it may be one of these.  Their schedules are in tests/test_gpu_k256_schnorr_keyed.py.
+ * SBV_EINVAL: a null required pointer, n > 2^32, and for the `_stream` forms a device pointer to data that is not 4-byte aligned;
+ * SBV_ENOTINIT before sbv_init.  n == 0 (m == 0) is SBV_OK and writes nothing.  Nothing here is secret. */
+int
+sbv_secp256k1_schnorr_lift_keys(const uint8_t* pks, size_t m, uint8_t* keys64, uint8_t* ok);
+int
+sbv_secp256k1_schnorr_lift_keys_stream(const void* d_pks, size_t m, void* d_keys64, void* d_ok, void* hip_stream);
+int
+sbv_secp256k1_schnorr_verify_keyed(const uint8_t* msgs, const uint8_t* sigs, const uint32_t* slots, size_t n, uint8_t* ok);
+int
+sbv_secp256k1_schnorr_verify_keyed_stream(const void* d_msgs, const void* d_sigs, const void* d_slots, size_t n, void* d_ok,
+                                          void* hip_stream);
+/* Test only: the keyed walk, one case per lane, host pointers, in the records of sbv_debug_secp256k1_sign_op (192 bytes in, 128 bytes
+ * out, output field 3 = ok) plus one slot per case.
+ *   op 0   in: u1 | u2 (below n)     out: x | y               the affine u1 G + u2 Q_slot through exactly the walk and the wavefront
+ *                                                             rule of sbv_secp256k1_schnorr_verify_keyed; ok = 0 (all zero) for
+ *                                                             infinity and for an out-of-range or invalid slot
+ * Any other op is SBV_EINVAL; at most 65536 cases.  The final check is op 2 of sbv_debug_secp256k1_schnorr_op. */
+int
+sbv_debug_secp256k1_schnorr_keyed_op(int op, const uint8_t* in, const uint32_t* slots, uint8_t* out, size_t n);
+
 /* Ed25519 batch signing (RFC 8032 section 5.1.6, pure Ed25519): the batch form of api.Signer.Sign for the Ed25519 variant, in two
  * steps so that a key is expanded once and not once per signature.  Signatures and public keys are byte-identical to RFC 8032,
  * Go's crypto/ed25519 and consensus_amd/host's Signer (the scheme is deterministic: tests compare every byte).
