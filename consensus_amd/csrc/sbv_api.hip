@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/sbv.h"
+#include "call_buffers.h"
 #include "ed25519_keyed.h"
 #include "ed25519_kernels.h"
 #include "p256_kernels.h"
@@ -1003,6 +1004,10 @@ int check_offsets(const uint64_t* offsets, size_t n, const void* payload, size_t
     if (bytes && !payload) { g_err = "null pointer"; return SBV_EINVAL; }
     return SBV_OK;
 }
+
+// any of the device pointers with a bit of `mask` set?  A null (absent) pointer passes.
+template <class... P>
+bool misaligned(uintptr_t mask, const P*... ptrs) { return ((reinterpret_cast<uintptr_t>(ptrs) | ...) & mask) != 0; }
 
 }  // namespace
 
@@ -2626,11 +2631,7 @@ extern "C" int sbv_p256_sign_batch_dev(const void* d_keys, uint32_t n_keys, cons
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (n == 0) return SBV_OK;
     if (!d_keys || !d_digests || !d_sigs || !d_ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(d_keys) | reinterpret_cast<uintptr_t>(d_digests) | reinterpret_cast<uintptr_t>(d_sigs) |
-         reinterpret_cast<uintptr_t>(d_key_index)) & 3) {
-        g_err = "misaligned device pointer";
-        return SBV_EINVAL;
-    }
+    if (misaligned(3, d_keys, d_digests, d_sigs, d_key_index)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     HIP_TRY(SBV_EDEVICE, sbv::launch_p256_sign(static_cast<const uint8_t*>(d_keys), n_keys, static_cast<const u32*>(d_key_index),
                                                static_cast<const uint8_t*>(d_digests), n, sbv::gcomb_make(c.d_g16r, c.g_bits),
@@ -2646,33 +2647,18 @@ extern "C" int sbv_p256_sign_batch(const uint8_t* keys, uint32_t n_keys, const u
     if (n == 0) return SBV_OK;
     if (!keys || !digests || !sigs || !ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    // not a hot path: buffers of the call's own size, released before returning (private keys do not linger in a pool)
-    uint8_t *d_keys = nullptr, *d_dig = nullptr, *d_sig = nullptr, *d_ok = nullptr;
-    u32* d_idx = nullptr;
-    int rc = SBV_OK;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_keys, (size_t)n_keys * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_dig, n * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
-        if (key_index && fail(SBV_ENOMEM, hipMalloc(&d_idx, n * sizeof(u32)))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_keys, keys, (size_t)n_keys * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_dig, digests, n * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (key_index && fail(SBV_EDEVICE, hipMemcpyAsync(d_idx, key_index, n * sizeof(u32), hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_p256_sign(d_keys, n_keys, d_idx, d_dig, n, sbv::gcomb_make(c.d_g16r, c.g_bits), d_sig, d_ok, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(sigs, d_sig, n * 64, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-        (void)hipMemsetAsync(d_keys, 0, (size_t)n_keys * 32, c.stream);
-        (void)hipStreamSynchronize(c.stream);
-    } while (false);
-    if (d_keys) (void)hipFree(d_keys);
-    if (d_dig) (void)hipFree(d_dig);
-    if (d_sig) (void)hipFree(d_sig);
-    if (d_ok) (void)hipFree(d_ok);
-    if (d_idx) (void)hipFree(d_idx);
-    return rc;
+    // not a hot path: buffers of the call's own size, zeroed where secret and released before returning (call_buffers.h): private
+    // keys do not linger in a pool.  The same holds for every host-pointer form from here to sbv_host_alloc.
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_keys = cb.upload(keys, (size_t)n_keys * 32, true);
+    const uint8_t* d_dig = cb.upload(digests, n * 32);
+    const u32* d_idx = cb.upload(key_index, n * sizeof(u32));
+    uint8_t* d_sig = cb.alloc(n * 64);
+    uint8_t* d_ok = cb.alloc(n);
+    if (cb.good()) cb.launch(sbv::launch_p256_sign(d_keys, n_keys, d_idx, d_dig, n, sbv::gcomb_make(c.d_g16r, c.g_bits), d_sig, d_ok, c.stream));
+    cb.download(sigs, d_sig, n * 64);
+    cb.download(ok, d_ok, n);
+    return cb.finish();
 }
 
 // ---- secp256k1 batch signing (k256_sign.h, k256_sign_kernels.hip) -----------------------------------------------------------
@@ -2685,11 +2671,7 @@ extern "C" int sbv_secp256k1_sign_batch_stream(const void* d_keys, uint32_t n_ke
     if (flags & ~SBV_K256_SIGN_LOW_S) { g_err = "unknown flag"; return SBV_EINVAL; }
     if (n == 0) return SBV_OK;
     if (!d_keys || !d_digests || !d_sigs || !d_ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(d_keys) | reinterpret_cast<uintptr_t>(d_digests) | reinterpret_cast<uintptr_t>(d_sigs) |
-         reinterpret_cast<uintptr_t>(d_key_index)) & 3) {
-        g_err = "misaligned device pointer";
-        return SBV_EINVAL;
-    }
+    if (misaligned(3, d_keys, d_digests, d_sigs, d_key_index)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
@@ -2704,7 +2686,7 @@ extern "C" int sbv_secp256k1_pubkeys_stream(const void* d_keys, size_t m, void* 
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (m == 0) return SBV_OK;
     if (!d_keys || !d_pubs || !d_ok) { g_err = "null pointer"; return SBV_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(d_keys) | reinterpret_cast<uintptr_t>(d_pubs)) & 3) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
+    if (misaligned(3, d_keys, d_pubs)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
@@ -2721,39 +2703,20 @@ extern "C" int sbv_secp256k1_sign_batch(const uint8_t* keys, uint32_t n_keys, co
     if (n == 0) return SBV_OK;
     if (!keys || !digests || !sigs || !ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_k256_table(c);
+    const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
-    // not a hot path: buffers of the call's own size, released before returning (private keys do not linger in a pool)
-    uint8_t *d_keys = nullptr, *d_dig = nullptr, *d_sig = nullptr, *d_rid = nullptr, *d_ok = nullptr;
-    u32* d_idx = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_keys, (size_t)n_keys * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_dig, n * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
-        if (recid && fail(SBV_ENOMEM, hipMalloc(&d_rid, n))) break;
-        if (key_index && fail(SBV_ENOMEM, hipMalloc(&d_idx, n * sizeof(u32)))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_keys, keys, (size_t)n_keys * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_dig, digests, n * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (key_index && fail(SBV_EDEVICE, hipMemcpyAsync(d_idx, key_index, n * sizeof(u32), hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_k256_sign(d_keys, n_keys, d_idx, d_dig, n, c.d_k256_gtab, flags, d_sig, d_rid, d_ok, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(sigs, d_sig, n * 64, hipMemcpyDeviceToHost, c.stream))) break;
-        if (recid && fail(SBV_EDEVICE, hipMemcpyAsync(recid, d_rid, n, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (d_keys) {
-        (void)hipMemsetAsync(d_keys, 0, (size_t)n_keys * 32, c.stream);
-        (void)hipStreamSynchronize(c.stream);
-    }
-    if (d_keys) (void)hipFree(d_keys);
-    if (d_dig) (void)hipFree(d_dig);
-    if (d_sig) (void)hipFree(d_sig);
-    if (d_rid) (void)hipFree(d_rid);
-    if (d_ok) (void)hipFree(d_ok);
-    if (d_idx) (void)hipFree(d_idx);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_keys = cb.upload(keys, (size_t)n_keys * 32, true);
+    const uint8_t* d_dig = cb.upload(digests, n * 32);
+    const u32* d_idx = cb.upload(key_index, n * sizeof(u32));
+    uint8_t* d_sig = cb.alloc(n * 64);
+    uint8_t* d_rid = recid ? cb.alloc(n) : nullptr;
+    uint8_t* d_ok = cb.alloc(n);
+    if (cb.good()) cb.launch(sbv::launch_k256_sign(d_keys, n_keys, d_idx, d_dig, n, c.d_k256_gtab, flags, d_sig, d_rid, d_ok, c.stream));
+    cb.download(sigs, d_sig, n * 64);
+    cb.download(recid, d_rid, n);
+    cb.download(ok, d_ok, n);
+    return cb.finish();
 }
 
 extern "C" int sbv_secp256k1_pubkeys(const uint8_t* keys, size_t m, uint8_t* pubs, uint8_t* ok) {
@@ -2762,28 +2725,16 @@ extern "C" int sbv_secp256k1_pubkeys(const uint8_t* keys, size_t m, uint8_t* pub
     if (m == 0) return SBV_OK;
     if (!keys || !pubs || !ok) { g_err = "null pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_k256_table(c);
+    const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
-    uint8_t *d_keys = nullptr, *d_pub = nullptr, *d_ok = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_keys, m * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_pub, m * 64))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, m))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_keys, keys, m * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_k256_pubkeys(d_keys, m, c.d_k256_gtab, d_pub, d_ok, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(pubs, d_pub, m * 64, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, m, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (d_keys) {
-        (void)hipMemsetAsync(d_keys, 0, m * 32, c.stream);
-        (void)hipStreamSynchronize(c.stream);
-    }
-    if (d_keys) (void)hipFree(d_keys);
-    if (d_pub) (void)hipFree(d_pub);
-    if (d_ok) (void)hipFree(d_ok);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_keys = cb.upload(keys, m * 32, true);
+    uint8_t* d_pub = cb.alloc(m * 64);
+    uint8_t* d_ok = cb.alloc(m);
+    if (cb.good()) cb.launch(sbv::launch_k256_pubkeys(d_keys, m, c.d_k256_gtab, d_pub, d_ok, c.stream));
+    cb.download(pubs, d_pub, m * 64);
+    cb.download(ok, d_ok, m);
+    return cb.finish();
 }
 
 // Test only (include/sbv.h): one case of a unit operation of the signer per lane: 192 bytes in, 128 bytes out.
@@ -2794,25 +2745,14 @@ extern "C" int sbv_debug_secp256k1_sign_op(int op, const uint8_t* in, uint8_t* o
     if (n == 0) return SBV_OK;
     if (!in || !out || n > kMaxChunk) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_k256_table(c);
+    const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_in, n * 192))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_out, n * 128))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_in, in, n * 192, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_k256_sign_op(op, d_in, d_out, n, c.d_k256_gtab, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(out, d_out, n * 128, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (d_in) {
-        (void)hipMemsetAsync(d_in, 0, n * 192, c.stream);
-        (void)hipStreamSynchronize(c.stream);
-        (void)hipFree(d_in);
-    }
-    if (d_out) (void)hipFree(d_out);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_in = cb.upload(in, n * 192, true);
+    uint8_t* d_out = cb.alloc(n * 128);
+    if (cb.good()) cb.launch(sbv::launch_k256_sign_op(op, d_in, d_out, n, c.d_k256_gtab, c.stream));
+    cb.download(out, d_out, n * 128);
+    return cb.finish();
 }
 
 // ---- secp256k1 public-key recovery (k256_recover.h, k256_recover_kernels.hip) --------------------------------------------------
@@ -2830,11 +2770,7 @@ extern "C" int sbv_secp256k1_recover_stream(const void* d_sigs, const void* d_re
     if (flags & ~SBV_K256_RECOVER_LOW_S) { g_err = "unknown flag"; return SBV_EINVAL; }
     if (n == 0) return SBV_OK;
     if (!d_sigs || !d_recid || !d_digests || !d_pubs || !d_ok || !d_work) { g_err = "null pointer"; return SBV_EINVAL; }
-    if (((reinterpret_cast<uintptr_t>(d_sigs) | reinterpret_cast<uintptr_t>(d_digests) | reinterpret_cast<uintptr_t>(d_pubs)) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_work) & 15)) {
-        g_err = "misaligned device pointer";
-        return SBV_EINVAL;
-    }
+    if (misaligned(3, d_sigs, d_digests, d_pubs) || misaligned(15, d_work)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
     if (work_bytes < sbv_secp256k1_recover_workspace(n)) { g_err = "workspace too small"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     const int rc = ensure_k256_table(c);
@@ -2853,35 +2789,19 @@ extern "C" int sbv_secp256k1_recover(const uint8_t* sigs, const uint8_t* recid, 
     if (n == 0) return SBV_OK;
     if (!sigs || !recid || !digests || !pubs || !ok) { g_err = "null pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_k256_table(c);
+    const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
-    // not a hot path: buffers and a workspace of the call's own size, released before returning
-    uint8_t *d_sig = nullptr, *d_rid = nullptr, *d_dig = nullptr, *d_pub = nullptr, *d_ok = nullptr;
-    u32* d_work = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_rid, n))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_dig, n * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_pub, n * 64))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_work, sbv_secp256k1_recover_workspace(n)))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_sig, sigs, n * 64, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_rid, recid, n, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_dig, digests, n * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_k256_recover(d_sig, d_rid, d_dig, n, flags, c.d_k256_gtab, d_work, d_pub, d_ok, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(pubs, d_pub, n * 64, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);       // nothing of this call is in flight when its buffers go
-    if (d_sig) (void)hipFree(d_sig);
-    if (d_rid) (void)hipFree(d_rid);
-    if (d_dig) (void)hipFree(d_dig);
-    if (d_pub) (void)hipFree(d_pub);
-    if (d_ok) (void)hipFree(d_ok);
-    if (d_work) (void)hipFree(d_work);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_sig = cb.upload(sigs, n * 64);
+    const uint8_t* d_rid = cb.upload(recid, n);
+    const uint8_t* d_dig = cb.upload(digests, n * 32);
+    uint8_t* d_pub = cb.alloc(n * 64);
+    uint8_t* d_ok = cb.alloc(n);
+    u32* d_work = cb.alloc<u32>(sbv_secp256k1_recover_workspace(n));
+    if (cb.good()) cb.launch(sbv::launch_k256_recover(d_sig, d_rid, d_dig, n, flags, c.d_k256_gtab, d_work, d_pub, d_ok, c.stream));
+    cb.download(pubs, d_pub, n * 64);
+    cb.download(ok, d_ok, n);
+    return cb.finish();
 }
 
 // Test only (include/sbv.h): one case of a unit operation of the recovery per lane: 192 bytes in, 128 bytes out, one strip per case.
@@ -2892,25 +2812,15 @@ extern "C" int sbv_debug_secp256k1_recover_op(int op, const uint8_t* in, uint8_t
     if (n == 0) return SBV_OK;
     if (!in || !out || n > 65536) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_k256_table(c);
+    const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    u32* d_work = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_in, n * 192))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_out, n * 128))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_work, n * sbv::k256_recover_strip_bytes()))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_in, in, n * 192, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_k256_recover_op(op, d_in, d_out, n, c.d_k256_gtab, d_work, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(out, d_out, n * 128, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_work) (void)hipFree(d_work);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_in = cb.upload(in, n * 192);
+    uint8_t* d_out = cb.alloc(n * 128);
+    u32* d_work = cb.alloc<u32>(n * sbv::k256_recover_strip_bytes());
+    if (cb.good()) cb.launch(sbv::launch_k256_recover_op(op, d_in, d_out, n, c.d_k256_gtab, d_work, c.stream));
+    cb.download(out, d_out, n * 128);
+    return cb.finish();
 }
 
 // ---- BIP-340 Schnorr over secp256k1 (k256_schnorr.h, k256_schnorr_kernels.hip) -------------------------------------------------
@@ -2924,11 +2834,7 @@ extern "C" int sbv_secp256k1_schnorr_verify_stream(const void* d_pks, const void
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (n == 0) return SBV_OK;
     if (!d_pks || !d_msgs || !d_sigs || !d_ok || !d_work) { g_err = "null pointer"; return SBV_EINVAL; }
-    if (((reinterpret_cast<uintptr_t>(d_pks) | reinterpret_cast<uintptr_t>(d_msgs) | reinterpret_cast<uintptr_t>(d_sigs)) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_work) & 15)) {
-        g_err = "misaligned device pointer";
-        return SBV_EINVAL;
-    }
+    if (misaligned(3, d_pks, d_msgs, d_sigs) || misaligned(15, d_work)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
     if (work_bytes < sbv_secp256k1_schnorr_verify_workspace(n)) { g_err = "workspace too small"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     const int rc = ensure_k256_table(c);
@@ -2945,32 +2851,17 @@ extern "C" int sbv_secp256k1_schnorr_verify(const uint8_t* pks, const uint8_t* m
     if (n == 0) return SBV_OK;
     if (!pks || !msgs || !sigs || !ok) { g_err = "null pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_k256_table(c);
+    const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
-    // not a hot path: buffers and a workspace of the call's own size, released before returning
-    uint8_t *d_pk = nullptr, *d_msg = nullptr, *d_sig = nullptr, *d_ok = nullptr;
-    u32* d_work = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_pk, n * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_msg, n * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_work, sbv_secp256k1_schnorr_verify_workspace(n)))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_pk, pks, n * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_msg, msgs, n * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_sig, sigs, n * 64, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_verify(d_pk, d_msg, d_sig, n, c.d_k256_gtab, d_work, d_ok, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);       // nothing of this call is in flight when its buffers go
-    if (d_pk) (void)hipFree(d_pk);
-    if (d_msg) (void)hipFree(d_msg);
-    if (d_sig) (void)hipFree(d_sig);
-    if (d_ok) (void)hipFree(d_ok);
-    if (d_work) (void)hipFree(d_work);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_pk = cb.upload(pks, n * 32);
+    const uint8_t* d_msg = cb.upload(msgs, n * 32);
+    const uint8_t* d_sig = cb.upload(sigs, n * 64);
+    uint8_t* d_ok = cb.alloc(n);
+    u32* d_work = cb.alloc<u32>(sbv_secp256k1_schnorr_verify_workspace(n));
+    if (cb.good()) cb.launch(sbv::launch_k256_schnorr_verify(d_pk, d_msg, d_sig, n, c.d_k256_gtab, d_work, d_ok, c.stream));
+    cb.download(ok, d_ok, n);
+    return cb.finish();
 }
 
 extern "C" int sbv_secp256k1_schnorr_expand_keys_stream(const void* d_keys, size_t m, void* d_expanded, void* d_pks, void* d_ok, void* hip_stream) {
@@ -2978,10 +2869,7 @@ extern "C" int sbv_secp256k1_schnorr_expand_keys_stream(const void* d_keys, size
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (m == 0) return SBV_OK;
     if (!d_keys || !d_expanded || !d_ok) { g_err = "null pointer"; return SBV_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(d_keys) | reinterpret_cast<uintptr_t>(d_expanded) | reinterpret_cast<uintptr_t>(d_pks)) & 3) {
-        g_err = "misaligned device pointer";
-        return SBV_EINVAL;
-    }
+    if (misaligned(3, d_keys, d_expanded, d_pks)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
@@ -2997,31 +2885,18 @@ extern "C" int sbv_secp256k1_schnorr_expand_keys(const uint8_t* keys, size_t m, 
     if (m == 0) return SBV_OK;
     if (!keys || !expanded || !ok) { g_err = "null pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_k256_table(c);
+    const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
-    uint8_t *d_keys = nullptr, *d_exp = nullptr, *d_pk = nullptr, *d_ok = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_keys, m * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_exp, m * 64))) break;
-        if (pks && fail(SBV_ENOMEM, hipMalloc(&d_pk, m * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, m))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_keys, keys, m * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_expand(d_keys, m, c.d_k256_gtab, d_exp, d_pk, d_ok, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(expanded, d_exp, m * 64, hipMemcpyDeviceToHost, c.stream))) break;
-        if (pks && fail(SBV_EDEVICE, hipMemcpyAsync(pks, d_pk, m * 32, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, m, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    // the device copies of the secrets are zeroed before they go
-    if (d_keys) (void)hipMemsetAsync(d_keys, 0, m * 32, c.stream);
-    if (d_exp) (void)hipMemsetAsync(d_exp, 0, m * 64, c.stream);
-    (void)hipStreamSynchronize(c.stream);
-    if (d_keys) (void)hipFree(d_keys);
-    if (d_exp) (void)hipFree(d_exp);
-    if (d_pk) (void)hipFree(d_pk);
-    if (d_ok) (void)hipFree(d_ok);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_keys = cb.upload(keys, m * 32, true);
+    uint8_t* d_exp = cb.alloc(m * 64, true);
+    uint8_t* d_pk = pks ? cb.alloc(m * 32) : nullptr;
+    uint8_t* d_ok = cb.alloc(m);
+    if (cb.good()) cb.launch(sbv::launch_k256_schnorr_expand(d_keys, m, c.d_k256_gtab, d_exp, d_pk, d_ok, c.stream));
+    cb.download(expanded, d_exp, m * 64);
+    cb.download(pks, d_pk, m * 32);
+    cb.download(ok, d_ok, m);
+    return cb.finish();
 }
 
 extern "C" int sbv_secp256k1_schnorr_sign_stream(const void* d_expanded, uint32_t n_keys, const void* d_key_index, const void* d_msgs,
@@ -3030,11 +2905,7 @@ extern "C" int sbv_secp256k1_schnorr_sign_stream(const void* d_expanded, uint32_
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (n == 0) return SBV_OK;
     if (!d_expanded || !d_msgs || !d_sigs || !d_ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(d_expanded) | reinterpret_cast<uintptr_t>(d_msgs) | reinterpret_cast<uintptr_t>(d_sigs) |
-         reinterpret_cast<uintptr_t>(d_key_index) | reinterpret_cast<uintptr_t>(d_aux)) & 3) {
-        g_err = "misaligned device pointer";
-        return SBV_EINVAL;
-    }
+    if (misaligned(3, d_expanded, d_msgs, d_sigs, d_key_index, d_aux)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
@@ -3052,39 +2923,19 @@ extern "C" int sbv_secp256k1_schnorr_sign(const uint8_t* expanded, uint32_t n_ke
     if (n == 0) return SBV_OK;
     if (!expanded || !msgs || !sigs || !ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_k256_table(c);
+    const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
-    // not a hot path: buffers of the call's own size, released before returning (records do not linger in a pool)
-    uint8_t *d_exp = nullptr, *d_msg = nullptr, *d_aux = nullptr, *d_sig = nullptr, *d_ok = nullptr;
-    u32* d_idx = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_exp, (size_t)n_keys * 64))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_msg, n * 32))) break;
-        if (aux && fail(SBV_ENOMEM, hipMalloc(&d_aux, n * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
-        if (key_index && fail(SBV_ENOMEM, hipMalloc(&d_idx, n * sizeof(u32)))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_exp, expanded, (size_t)n_keys * 64, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_msg, msgs, n * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (aux && fail(SBV_EDEVICE, hipMemcpyAsync(d_aux, aux, n * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (key_index && fail(SBV_EDEVICE, hipMemcpyAsync(d_idx, key_index, n * sizeof(u32), hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_sign(d_exp, n_keys, d_idx, d_msg, d_aux, n, c.d_k256_gtab, d_sig, d_ok, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(sigs, d_sig, n * 64, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (d_exp) {
-        (void)hipMemsetAsync(d_exp, 0, (size_t)n_keys * 64, c.stream);
-        (void)hipStreamSynchronize(c.stream);
-    }
-    if (d_exp) (void)hipFree(d_exp);
-    if (d_msg) (void)hipFree(d_msg);
-    if (d_aux) (void)hipFree(d_aux);
-    if (d_sig) (void)hipFree(d_sig);
-    if (d_ok) (void)hipFree(d_ok);
-    if (d_idx) (void)hipFree(d_idx);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_exp = cb.upload(expanded, (size_t)n_keys * 64, true);
+    const uint8_t* d_msg = cb.upload(msgs, n * 32);
+    const uint8_t* d_aux = cb.upload(aux, n * 32);
+    const u32* d_idx = cb.upload(key_index, n * sizeof(u32));
+    uint8_t* d_sig = cb.alloc(n * 64);
+    uint8_t* d_ok = cb.alloc(n);
+    if (cb.good()) cb.launch(sbv::launch_k256_schnorr_sign(d_exp, n_keys, d_idx, d_msg, d_aux, n, c.d_k256_gtab, d_sig, d_ok, c.stream));
+    cb.download(sigs, d_sig, n * 64);
+    cb.download(ok, d_ok, n);
+    return cb.finish();
 }
 
 // Test only (include/sbv.h): one case of a unit operation of the Schnorr lanes per lane: 192 bytes in, 128 bytes out, one strip per case.
@@ -3095,28 +2946,15 @@ extern "C" int sbv_debug_secp256k1_schnorr_op(int op, const uint8_t* in, uint8_t
     if (n == 0) return SBV_OK;
     if (!in || !out || n > 65536) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_k256_table(c);
+    const int rc = ensure_k256_table(c);
     if (rc != SBV_OK) return rc;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    u32* d_work = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_in, n * 192))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_out, n * 128))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_work, n * sbv::k256_recover_strip_bytes()))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_in, in, n * 192, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_op(op, d_in, d_out, n, c.d_k256_gtab, d_work, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(out, d_out, n * 128, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (d_in) {
-        (void)hipMemsetAsync(d_in, 0, n * 192, c.stream);
-        (void)hipStreamSynchronize(c.stream);
-        (void)hipFree(d_in);
-    }
-    if (d_out) (void)hipFree(d_out);
-    if (d_work) (void)hipFree(d_work);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_in = cb.upload(in, n * 192, true);
+    uint8_t* d_out = cb.alloc(n * 128);
+    u32* d_work = cb.alloc<u32>(n * sbv::k256_recover_strip_bytes());
+    if (cb.good()) cb.launch(sbv::launch_k256_schnorr_op(op, d_in, d_out, n, c.d_k256_gtab, d_work, c.stream));
+    cb.download(out, d_out, n * 128);
+    return cb.finish();
 }
 
 // ---- BIP-340 Schnorr against registered secp256k1 keys (k256_schnorr_keyed.h, k256_schnorr_keyed_kernels.hip) -----------------
@@ -3141,7 +2979,7 @@ extern "C" int sbv_secp256k1_schnorr_lift_keys_stream(const void* d_pks, size_t 
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (m == 0) return SBV_OK;
     if (!d_pks || !d_keys64) { g_err = "null pointer"; return SBV_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(d_pks) | reinterpret_cast<uintptr_t>(d_keys64)) & 3) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
+    if (misaligned(3, d_pks, d_keys64)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
     if (schnorr_keyed_check_n(m) != SBV_OK) return SBV_EINVAL;
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     HIP_TRY(SBV_EDEVICE, sbv::launch_k256_schnorr_lift(static_cast<const uint8_t*>(d_pks), m, static_cast<uint8_t*>(d_keys64), static_cast<uint8_t*>(d_ok),
@@ -3156,24 +2994,14 @@ extern "C" int sbv_secp256k1_schnorr_lift_keys(const uint8_t* pks, size_t m, uin
     if (!pks || !keys64) { g_err = "null pointer"; return SBV_EINVAL; }
     if (schnorr_keyed_check_n(m) != SBV_OK) return SBV_EINVAL;
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = SBV_OK;
-    uint8_t *d_pk = nullptr, *d_keys = nullptr, *d_ok = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_pk, m * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_keys, m * 64))) break;
-        if (ok && fail(SBV_ENOMEM, hipMalloc(&d_ok, m))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_pk, pks, m * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_lift(d_pk, m, d_keys, d_ok, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(keys64, d_keys, m * 64, hipMemcpyDeviceToHost, c.stream))) break;
-        if (ok && fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, m, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);       // nothing of this call is in flight when its buffers go
-    if (d_pk) (void)hipFree(d_pk);
-    if (d_keys) (void)hipFree(d_keys);
-    if (d_ok) (void)hipFree(d_ok);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_pk = cb.upload(pks, m * 32);
+    uint8_t* d_keys = cb.alloc(m * 64);
+    uint8_t* d_ok = ok ? cb.alloc(m) : nullptr;
+    if (cb.good()) cb.launch(sbv::launch_k256_schnorr_lift(d_pk, m, d_keys, d_ok, c.stream));
+    cb.download(keys64, d_keys, m * 64);
+    cb.download(ok, d_ok, m);
+    return cb.finish();
 }
 
 extern "C" int sbv_secp256k1_schnorr_verify_keyed_stream(const void* d_msgs, const void* d_sigs, const void* d_slots, size_t n, void* d_ok, void* hip_stream) {
@@ -3181,10 +3009,7 @@ extern "C" int sbv_secp256k1_schnorr_verify_keyed_stream(const void* d_msgs, con
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (n == 0) return SBV_OK;
     if (!d_msgs || !d_sigs || !d_slots || !d_ok) { g_err = "null pointer"; return SBV_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(d_msgs) | reinterpret_cast<uintptr_t>(d_sigs) | reinterpret_cast<uintptr_t>(d_slots)) & 3) {
-        g_err = "misaligned device pointer";
-        return SBV_EINVAL;
-    }
+    if (misaligned(3, d_msgs, d_sigs, d_slots)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
     if (schnorr_keyed_check_n(n) != SBV_OK) return SBV_EINVAL;
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -3208,31 +3033,17 @@ extern "C" int sbv_secp256k1_schnorr_verify_keyed(const uint8_t* msgs, const uin
     if (schnorr_keyed_check_n(n) != SBV_OK) return SBV_EINVAL;
     if (c.k256reg.nkeys == 0) { memset(ok, 0, n); return SBV_OK; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = K256Reg::ensure(c);
+    const int rc = K256Reg::ensure(c);
     if (rc != SBV_OK) return rc;
-    // buffers of the call's own size, released before returning, as sbv_secp256k1_schnorr_verify's
-    uint8_t *d_msg = nullptr, *d_sig = nullptr, *d_ok = nullptr;
-    u32* d_sl = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_msg, n * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_sl, n * sizeof(u32)))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_msg, msgs, n * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_sig, sigs, n * 64, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_sl, slots, n * sizeof(u32), hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_verify_keyed(d_msg, d_sig, d_sl, n, k256_reg_view(c), c.k256reg.kkeys, c.d_k256_gcomb, c.k256_gbits,
-                                                                    d_ok, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);       // nothing of this call is in flight when its buffers go
-    if (d_msg) (void)hipFree(d_msg);
-    if (d_sig) (void)hipFree(d_sig);
-    if (d_sl) (void)hipFree(d_sl);
-    if (d_ok) (void)hipFree(d_ok);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_msg = cb.upload(msgs, n * 32);
+    const uint8_t* d_sig = cb.upload(sigs, n * 64);
+    const u32* d_sl = cb.upload(slots, n * sizeof(u32));
+    uint8_t* d_ok = cb.alloc(n);
+    if (cb.good()) cb.launch(sbv::launch_k256_schnorr_verify_keyed(d_msg, d_sig, d_sl, n, k256_reg_view(c), c.k256reg.kkeys, c.d_k256_gcomb,
+                                                                   c.k256_gbits, d_ok, c.stream));
+    cb.download(ok, d_ok, n);
+    return cb.finish();
 }
 
 // Test only (include/sbv.h): one case of the keyed walk per lane: 192 bytes in (u1 | u2), a slot, 128 bytes out.
@@ -3244,26 +3055,15 @@ extern "C" int sbv_debug_secp256k1_schnorr_keyed_op(int op, const uint8_t* in, c
     if (!in || !slots || !out || n > 65536) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
     if (c.k256reg.nkeys == 0) { memset(out, 0, n * 128); return SBV_OK; }      // every slot is out of range
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = K256Reg::ensure(c);
+    const int rc = K256Reg::ensure(c);
     if (rc != SBV_OK) return rc;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    u32* d_sl = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_in, n * 192))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_out, n * 128))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_sl, n * sizeof(u32)))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_in, in, n * 192, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_sl, slots, n * sizeof(u32), hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_k256_schnorr_keyed_op(d_in, d_sl, d_out, n, k256_reg_view(c), c.d_k256_gcomb, c.k256_gbits, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(out, d_out, n * 128, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (rc != SBV_OK) (void)hipStreamSynchronize(c.stream);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_sl) (void)hipFree(d_sl);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_in = cb.upload(in, n * 192);
+    const u32* d_sl = cb.upload(slots, n * sizeof(u32));
+    uint8_t* d_out = cb.alloc(n * 128);
+    if (cb.good()) cb.launch(sbv::launch_k256_schnorr_keyed_op(d_in, d_sl, d_out, n, k256_reg_view(c), c.d_k256_gcomb, c.k256_gbits, c.stream));
+    cb.download(out, d_out, n * 128);
+    return cb.finish();
 }
 
 // ---- Ed25519 batch signing (ed25519_sign.h, ed25519_sign_kernels.hip) -------------------------------------------------------
@@ -3275,10 +3075,7 @@ extern "C" int sbv_ed25519_expand_keys_stream(const void* d_seeds, size_t m, voi
     if (m == 0) return SBV_OK;
     if (!d_seeds || !d_expanded) { g_err = "null pointer"; return SBV_EINVAL; }
     if (m > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(d_seeds) | reinterpret_cast<uintptr_t>(d_expanded) | reinterpret_cast<uintptr_t>(d_pks)) & 3) {
-        g_err = "misaligned device pointer";
-        return SBV_EINVAL;
-    }
+    if (misaligned(3, d_seeds, d_expanded, d_pks)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     const int rc = ensure_ed_table(c);
     if (rc != SBV_OK) return rc;
@@ -3294,11 +3091,7 @@ extern "C" int sbv_ed25519_sign_msgs_stream(const void* d_expanded, uint32_t n_k
     if (n == 0) return SBV_OK;
     if (!d_expanded || !d_msg_offsets || !d_sigs || !d_ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
     if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
-    if (((reinterpret_cast<uintptr_t>(d_expanded) | reinterpret_cast<uintptr_t>(d_key_index) | reinterpret_cast<uintptr_t>(d_sigs)) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_msg_offsets) & 7)) {
-        g_err = "misaligned device pointer";
-        return SBV_EINVAL;
-    }
+    if (misaligned(3, d_expanded, d_key_index, d_sigs) || misaligned(7, d_msg_offsets)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     const int rc = ensure_ed_table(c);
     if (rc != SBV_OK) return rc;
@@ -3315,28 +3108,16 @@ extern "C" int sbv_ed25519_expand_keys(const uint8_t* seeds, size_t m, uint8_t* 
     if (!seeds || !expanded) { g_err = "null pointer"; return SBV_EINVAL; }
     if (m > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_ed_table(c);
+    const int rc = ensure_ed_table(c);
     if (rc != SBV_OK) return rc;
-    // not a hot path: buffers of the call's own size, zeroed and released before returning (seeds and records do not linger in a pool)
-    uint8_t *d_seeds = nullptr, *d_exp = nullptr, *d_pks = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_seeds, m * 32))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_exp, m * 96))) break;
-        if (pks && fail(SBV_ENOMEM, hipMalloc(&d_pks, m * 32))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_seeds, seeds, m * 32, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_ed_sign_expand(d_seeds, m, c.d_btab, d_exp, d_pks, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(expanded, d_exp, m * 96, hipMemcpyDeviceToHost, c.stream))) break;
-        if (pks && fail(SBV_EDEVICE, hipMemcpyAsync(pks, d_pks, m * 32, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (d_seeds) (void)hipMemsetAsync(d_seeds, 0, m * 32, c.stream);
-    if (d_exp) (void)hipMemsetAsync(d_exp, 0, m * 96, c.stream);
-    (void)hipStreamSynchronize(c.stream);
-    if (d_seeds) (void)hipFree(d_seeds);
-    if (d_exp) (void)hipFree(d_exp);
-    if (d_pks) (void)hipFree(d_pks);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_seeds = cb.upload(seeds, m * 32, true);
+    uint8_t* d_exp = cb.alloc(m * 96, true);
+    uint8_t* d_pks = pks ? cb.alloc(m * 32) : nullptr;
+    if (cb.good()) cb.launch(sbv::launch_ed_sign_expand(d_seeds, m, c.d_btab, d_exp, d_pks, c.stream));
+    cb.download(expanded, d_exp, m * 96);
+    cb.download(pks, d_pks, m * 32);
+    return cb.finish();
 }
 
 extern "C" int sbv_ed25519_sign_msgs(const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs,
@@ -3351,37 +3132,18 @@ extern "C" int sbv_ed25519_sign_msgs(const uint8_t* expanded, uint32_t n_keys, c
     if (rc != SBV_OK) return rc;
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     if ((rc = ensure_ed_table(c)) != SBV_OK) return rc;
-    uint8_t *d_exp = nullptr, *d_msgs = nullptr, *d_sig = nullptr, *d_ok = nullptr;
-    uint64_t* d_moff = nullptr;
-    u32* d_idx = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_exp, (size_t)n_keys * 96))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_msgs, mbytes + 16))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_moff, (n + 1) * sizeof(uint64_t)))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_sig, n * 64))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_ok, n))) break;
-        if (key_index && fail(SBV_ENOMEM, hipMalloc(&d_idx, n * sizeof(u32)))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_exp, expanded, (size_t)n_keys * 96, hipMemcpyHostToDevice, c.stream))) break;
-        if (mbytes && fail(SBV_EDEVICE, hipMemcpyAsync(d_msgs, msgs, mbytes, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_moff, msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream))) break;
-        if (key_index && fail(SBV_EDEVICE, hipMemcpyAsync(d_idx, key_index, n * sizeof(u32), hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_ed_sign(d_exp, n_keys, d_idx, d_msgs, d_moff, n, c.d_btab, d_sig, d_ok, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(sigs, d_sig, n * 64, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (d_exp) {
-        (void)hipMemsetAsync(d_exp, 0, (size_t)n_keys * 96, c.stream);
-        (void)hipStreamSynchronize(c.stream);
-    }
-    if (d_exp) (void)hipFree(d_exp);
-    if (d_msgs) (void)hipFree(d_msgs);
-    if (d_moff) (void)hipFree(d_moff);
-    if (d_sig) (void)hipFree(d_sig);
-    if (d_ok) (void)hipFree(d_ok);
-    if (d_idx) (void)hipFree(d_idx);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_exp = cb.upload(expanded, (size_t)n_keys * 96, true);
+    uint8_t* d_msgs = cb.alloc(mbytes + 16);        // a buffer even when every message is empty (msgs may then be null)
+    cb.copy_in(d_msgs, msgs, mbytes);
+    const uint64_t* d_moff = cb.upload(msg_offsets, (n + 1) * sizeof(uint64_t));
+    const u32* d_idx = cb.upload(key_index, n * sizeof(u32));
+    uint8_t* d_sig = cb.alloc(n * 64);
+    uint8_t* d_ok = cb.alloc(n);
+    if (cb.good()) cb.launch(sbv::launch_ed_sign(d_exp, n_keys, d_idx, d_msgs, d_moff, n, c.d_btab, d_sig, d_ok, c.stream));
+    cb.download(sigs, d_sig, n * 64);
+    cb.download(ok, d_ok, n);
+    return cb.finish();
 }
 
 // Test only (include/sbv.h): one case of a unit operation of the signer per lane.
@@ -3392,22 +3154,14 @@ extern "C" int sbv_debug_ed25519_sign_op(int op, const uint8_t* in, uint8_t* out
     if (n == 0) return SBV_OK;
     if (!in || !out || n > kMaxChunk) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    int rc = ensure_ed_table(c);
+    const int rc = ensure_ed_table(c);
     if (rc != SBV_OK) return rc;
-    const size_t in_bytes = n * (op == 0 ? 96 : 32);
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    auto fail = [&](int code, hipError_t e) { if (e != hipSuccess && rc == SBV_OK) { g_err = hipGetErrorString(e); rc = code; } return e != hipSuccess; };
-    do {
-        if (fail(SBV_ENOMEM, hipMalloc(&d_in, in_bytes))) break;
-        if (fail(SBV_ENOMEM, hipMalloc(&d_out, n * 32))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c.stream))) break;
-        if (fail(SBV_EDEVICE, sbv::launch_ed_sign_op(op, d_in, d_out, n, c.d_btab, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, c.stream))) break;
-        if (fail(SBV_EDEVICE, hipStreamSynchronize(c.stream))) break;
-    } while (false);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_in = cb.upload(in, n * (op == 0 ? 96 : 32), true);     // op 0 takes expanded secret records
+    uint8_t* d_out = cb.alloc(n * 32);
+    if (cb.good()) cb.launch(sbv::launch_ed_sign_op(op, d_in, d_out, n, c.d_btab, c.stream));
+    cb.download(out, d_out, n * 32);
+    return cb.finish();
 }
 
 extern "C" void* sbv_host_alloc(size_t bytes) {

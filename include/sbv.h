@@ -178,10 +178,14 @@ int sbv_p256_verify_batch_keyed_dev(const void* d_rsh, const void* d_slots, size
  * d_digests or d_sigs that is not 4-byte aligned (the kernel reads and writes them as 32-bit words); d_ok is a byte array and may
  * sit at any address.  A refused call leaves the library as it was: the next good call signs.
  * sbv_p256_sign_batch takes host pointers, uses device buffers of the call's own size, waits for the result and zeroes the device
- * copy of the keys before it frees it.  sbv_p256_sign_batch_dev takes device pointers, launches on `hip_stream` and returns without
- * synchronising, under the stream contract of the `_dev` entries above; it may be the first call of a
- * process after sbv_init.  Both are held byte for byte to an independent RFC 6979 signer, the retry of section 3.2 h (a first
- * candidate >= N: 2^-32 per signature) included, in tests/test_emul_sign.py and tests/test_gpu_sign.py. */
+ * copy of the keys before it frees it.  That holds for every host-pointer form below that takes or makes secrets (the signers,
+ * sbv_secp256k1_pubkeys, both expand_keys entries and the sign / Schnorr debug entries): the device copies of private keys, seeds and
+ * expanded records are zeroed before they are released, on success and on failure alike.  The zeroing is itself device work whose
+ * result no call reports: if the fill or the wait for it fails, as on a faulted device, the buffers are still released, unzeroed.
+ * sbv_p256_sign_batch_dev takes device pointers, launches on `hip_stream` and returns without synchronising, under the stream
+ * contract of the `_dev` entries above; it may be the first call of a process after sbv_init.  Both are
+ * held byte for byte to an independent RFC 6979 signer, the retry of section 3.2 h (a first candidate >= N: 2^-32 per signature)
+ * included, in tests/test_emul_sign.py and tests/test_gpu_sign.py. */
 int sbv_p256_sign_batch(const uint8_t* keys, uint32_t n_keys, const uint32_t* key_index, const uint8_t* digests, size_t n,
                         uint8_t* sigs, uint8_t* ok);
 int sbv_p256_sign_batch_dev(const void* d_keys, uint32_t n_keys, const void* d_key_index, const void* d_digests, size_t n,
