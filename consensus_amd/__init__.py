@@ -580,6 +580,89 @@ def debug_secp256k1_recover_op(op: int, records):
     return [out.raw[128 * i:128 * i + 128] for i in range(n)]
 
 
+def keccak256_msgs(msgs, offsets=None):
+    """sbv_keccak256_msgs: Keccak-256 (Ethereum's keccak256, not SHA3-256) of a list of byte strings -> the list of 32-byte digests.
+    With `offsets` (n + 1 integers), `msgs` is instead the messages back to back in one bytes object (None when all are empty) and the
+    result is the n x 32 digest bytes in one object: the raw entry, bad offset tables included."""
+    lib = load()
+    lib.sbv_keccak256_msgs.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p]
+    if offsets is None:
+        msgs = [bytes(m) for m in msgs]
+        offs, blob = [0], b"".join(msgs)
+        for m in msgs:
+            offs.append(offs[-1] + len(m))
+    else:
+        offs, blob = list(offsets), msgs
+    n = len(offs) - 1
+    out = ctypes.create_string_buffer(max(1, 32 * n))
+    _check(lib.sbv_keccak256_msgs(blob, (ctypes.c_uint64 * (n + 1))(*offs), n, out))
+    return [out.raw[32 * i:32 * i + 32] for i in range(n)] if offsets is None else out.raw[:32 * n]
+
+
+def keccak256_msgs_stream(d_msgs_ptr: int, d_offsets_ptr: int, n: int, d_digests_ptr: int, stream: int = 0) -> None:
+    """device pointers (offsets: n + 1 u64, 8-byte aligned; messages at any alignment); asynchronous on `stream` under the stream
+    contract of the _dev entries (include/sbv.h)"""
+    lib = load()
+    lib.sbv_keccak256_msgs_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib.sbv_keccak256_msgs_stream(d_msgs_ptr or None, d_offsets_ptr or None, n, d_digests_ptr or None, stream or None))
+
+
+def secp256k1_addresses(pubs: bytes) -> bytes:
+    """sbv_secp256k1_addresses: m x 64 bytes Qx | Qy -> m x 20 bytes, the Ethereum-style addresses Keccak-256(Qx | Qy)[12:]; a pure
+    hash, the keys are not checked against the curve"""
+    lib = load()
+    m = len(pubs) // 64
+    if len(pubs) != 64 * m:
+        raise ValueError("secp256k1_addresses: pubs is not a whole number of 64-byte keys")
+    lib.sbv_secp256k1_addresses.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
+    addrs = ctypes.create_string_buffer(max(1, 20 * m))
+    _check(lib.sbv_secp256k1_addresses(bytes(pubs), m, addrs))
+    return addrs.raw[:20 * m]
+
+
+def secp256k1_addresses_stream(d_pubs_ptr: int, m: int, d_addrs_ptr: int, stream: int = 0) -> None:
+    lib = load()
+    lib.sbv_secp256k1_addresses_stream.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib.sbv_secp256k1_addresses_stream(d_pubs_ptr or None, m, d_addrs_ptr or None, stream or None))
+
+
+def secp256k1_recover_addresses(sigs: bytes, recid: bytes, digests: bytes, low_s: bool = False):
+    """sbv_secp256k1_recover_addresses: secp256k1_recover with the signer's 20-byte address in place of the key (what Ethereum's
+    ecrecover returns).  Returns (addrs, ok): n x 20 bytes in one object and ok[i] = 1 per recovered signer; a refused input gives
+    ok[i] = 0 and 20 zero bytes."""
+    lib = load()
+    n = len(recid)
+    if len(sigs) != 64 * n or len(digests) != 32 * n:
+        raise ValueError("secp256k1_recover_addresses: sigs, recid and digests disagree about n")
+    lib.sbv_secp256k1_recover_addresses.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32,
+                                                    ctypes.c_char_p, ctypes.c_char_p]
+    addrs, ok = ctypes.create_string_buffer(max(1, 20 * n)), ctypes.create_string_buffer(max(1, n))
+    _check(lib.sbv_secp256k1_recover_addresses(bytes(sigs), bytes(recid), bytes(digests), n, K256_RECOVER_LOW_S if low_s else 0, addrs, ok))
+    return addrs.raw[:20 * n], ok.raw[:n]
+
+
+def secp256k1_recover_addresses_stream(d_sigs_ptr: int, d_recid_ptr: int, d_digests_ptr: int, n: int, d_addrs_ptr: int, d_ok_ptr: int,
+                                       d_work_ptr: int, work_bytes: int, low_s: bool = False, stream: int = 0, flags=None) -> None:
+    """device pointers and the caller's workspace, exactly as secp256k1_recover_stream; addrs is n x 20 bytes"""
+    lib = load()
+    lib.sbv_secp256k1_recover_addresses_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                           ctypes.c_size_t, ctypes.c_void_p]
+    f = (K256_RECOVER_LOW_S if low_s else 0) if flags is None else flags
+    _check(lib.sbv_secp256k1_recover_addresses_stream(d_sigs_ptr or None, d_recid_ptr or None, d_digests_ptr or None, n, f,
+                                                      d_addrs_ptr or None, d_ok_ptr or None, d_work_ptr or None, work_bytes, stream or None))
+
+
+def debug_keccak_op(op: int, states):
+    """sbv_debug_keccak_op (test only): one case per lane, 200-byte states -> 200-byte states (include/sbv.h)"""
+    lib = load()
+    n = len(states)
+    lib.sbv_debug_keccak_op.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+    out = ctypes.create_string_buffer(max(1, 200 * n))
+    _check(lib.sbv_debug_keccak_op(op, b"".join(states), out, n))
+    return [out.raw[200 * i:200 * i + 200] for i in range(n)]
+
+
 def secp256k1_schnorr_verify(pks: bytes, msgs: bytes, sigs: bytes) -> bytes:
     """sbv_secp256k1_schnorr_verify: BIP-340 verification of n signatures (R.x | s, 64 bytes each) of 32-byte messages under x-only
     32-byte keys.  Returns ok: one byte per item, 1 = valid (include/sbv.h has the rules)."""

@@ -38,6 +38,7 @@
 #include "k256_keyed_kernels.h"
 #include "k256_sign_kernels.h"
 #include "k256_recover_kernels.h"
+#include "keccak_kernels.h"
 #include "k256_schnorr_kernels.h"
 #include "k256_schnorr_keyed_kernels.h"
 
@@ -2820,6 +2821,125 @@ extern "C" int sbv_debug_secp256k1_recover_op(int op, const uint8_t* in, uint8_t
     u32* d_work = cb.alloc<u32>(n * sbv::k256_recover_strip_bytes());
     if (cb.good()) cb.launch(sbv::launch_k256_recover_op(op, d_in, d_out, n, c.d_k256_gtab, d_work, c.stream));
     cb.download(out, d_out, n * 128);
+    return cb.finish();
+}
+
+// ---- Keccak-256 and Ethereum-style addresses (keccak256_dev.h, keccak_kernels.hip) --------------------------------------------------
+// The two hash entries own no state and upload nothing; the recovery form shares only the read-only 16-bit comb of G
+// (ensure_k256_table).  The _stream forms read and write only buffers of the caller's on the caller's stream: nothing to order, nothing
+// to join back.
+extern "C" int sbv_keccak256_msgs_stream(const void* d_msgs, const void* d_msg_offsets, size_t n, void* d_digests, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!d_msg_offsets || !d_digests) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (misaligned(3, d_digests) || misaligned(7, d_msg_offsets)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, sbv::launch_keccak256_msgs(static_cast<const uint8_t*>(d_msgs), static_cast<const uint64_t*>(d_msg_offsets), n,
+                                                    static_cast<uint8_t*>(d_digests), static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_keccak256_msgs(const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, uint8_t* digests) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!msg_offsets || !digests) { g_err = "null pointer"; return SBV_EINVAL; }
+    size_t mbytes = 0;
+    const int rc = check_offsets(msg_offsets, n, msgs, mbytes);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    sbv::CallBuffers cb(c.stream, &g_err);
+    uint8_t* d_msgs = cb.alloc(mbytes + 16);        // a buffer even when every message is empty (msgs may then be null)
+    cb.copy_in(d_msgs, msgs, mbytes);
+    const uint64_t* d_moff = cb.upload(msg_offsets, (n + 1) * sizeof(uint64_t));
+    uint8_t* d_dig = cb.alloc(n * 32);
+    if (cb.good()) cb.launch(sbv::launch_keccak256_msgs(d_msgs, d_moff, n, d_dig, c.stream));
+    cb.download(digests, d_dig, n * 32);
+    return cb.finish();
+}
+
+extern "C" int sbv_secp256k1_addresses_stream(const void* d_pubs, size_t m, void* d_addrs, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!d_pubs || !d_addrs) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (misaligned(3, d_pubs, d_addrs)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_addresses(static_cast<const uint8_t*>(d_pubs), m, static_cast<uint8_t*>(d_addrs),
+                                                    static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_addresses(const uint8_t* pubs, size_t m, uint8_t* addrs) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!pubs || !addrs) { g_err = "null pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_pub = cb.upload(pubs, m * 64);
+    uint8_t* d_addr = cb.alloc(m * 20);
+    if (cb.good()) cb.launch(sbv::launch_k256_addresses(d_pub, m, d_addr, c.stream));
+    cb.download(addrs, d_addr, m * 20);
+    return cb.finish();
+}
+
+extern "C" int sbv_secp256k1_recover_addresses_stream(const void* d_sigs, const void* d_recid, const void* d_digests, size_t n, uint32_t flags,
+                                                      void* d_addrs, void* d_ok, void* d_work, size_t work_bytes, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (flags & ~SBV_K256_RECOVER_LOW_S) { g_err = "unknown flag"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!d_sigs || !d_recid || !d_digests || !d_addrs || !d_ok || !d_work) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (misaligned(3, d_sigs, d_digests, d_addrs) || misaligned(15, d_work)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
+    if (work_bytes < sbv_secp256k1_recover_workspace(n)) { g_err = "workspace too small"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, sbv::launch_k256_recover_addr(static_cast<const uint8_t*>(d_sigs), static_cast<const uint8_t*>(d_recid),
+                                                       static_cast<const uint8_t*>(d_digests), n, flags, c.d_k256_gtab, static_cast<u32*>(d_work),
+                                                       static_cast<uint8_t*>(d_addrs), static_cast<uint8_t*>(d_ok),
+                                                       static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_secp256k1_recover_addresses(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint32_t flags,
+                                               uint8_t* addrs, uint8_t* ok) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (flags & ~SBV_K256_RECOVER_LOW_S) { g_err = "unknown flag"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!sigs || !recid || !digests || !addrs || !ok) { g_err = "null pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    const int rc = ensure_k256_table(c);
+    if (rc != SBV_OK) return rc;
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_sig = cb.upload(sigs, n * 64);
+    const uint8_t* d_rid = cb.upload(recid, n);
+    const uint8_t* d_dig = cb.upload(digests, n * 32);
+    uint8_t* d_addr = cb.alloc(n * 20);
+    uint8_t* d_ok = cb.alloc(n);
+    u32* d_work = cb.alloc<u32>(sbv_secp256k1_recover_workspace(n));
+    if (cb.good()) cb.launch(sbv::launch_k256_recover_addr(d_sig, d_rid, d_dig, n, flags, c.d_k256_gtab, d_work, d_addr, d_ok, c.stream));
+    cb.download(addrs, d_addr, n * 20);
+    cb.download(ok, d_ok, n);
+    return cb.finish();
+}
+
+// Test only (include/sbv.h): one case of a unit operation of Keccak per lane: 200 bytes in, 200 bytes out.
+extern "C" int sbv_debug_keccak_op(int op, const uint8_t* in, uint8_t* out, size_t n) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (op != 0) { g_err = "unknown operation"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!in || !out || n > 65536) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_in = cb.upload(in, n * 200);
+    uint8_t* d_out = cb.alloc(n * 200);
+    if (cb.good()) cb.launch(sbv::launch_keccak_op(op, d_in, d_out, n, c.stream));
+    cb.download(out, d_out, n * 200);
     return cb.finish();
 }
 

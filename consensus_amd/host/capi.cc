@@ -88,6 +88,14 @@ size_t sbvh_backend_last_k256_slots(void* h, uint32_t* out, size_t cap) {
 int sbvh_recover_signers(void* h, const uint8_t* sigs65, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) {
     return ((VHandle*)h)->v->RecoverSigners(sigs65, digests, n, pubs, ok).code;
 }
+// Verifier::RecoverAddresses: n x 65 bytes r | s | v + n x 32 bytes -> n x 20 bytes + n bytes; Verifier::Keccak256Batch: messages back
+// to back + n + 1 offsets -> n x 32 bytes; both return the status code
+int sbvh_recover_addresses(void* h, const uint8_t* sigs65, const uint8_t* digests, size_t n, uint8_t* addrs20, uint8_t* ok) {
+    return ((VHandle*)h)->v->RecoverAddresses(sigs65, digests, n, addrs20, ok).code;
+}
+int sbvh_keccak256_batch(void* h, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, uint8_t* digests) {
+    return ((VHandle*)h)->v->Keccak256Batch(msgs, msg_offsets, n, digests).code;
+}
 // Verifier::VerifySchnorr: n x 32 bytes x-only keys + n x 32 bytes + n x 64 bytes R.x | s -> n bytes; returns the status code
 int sbvh_verify_schnorr(void* h, const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok) {
     return ((VHandle*)h)->v->VerifySchnorr(pks, msgs, sigs, n, ok).code;
@@ -291,6 +299,17 @@ int sbvh_k256_sign_rfc6979(const uint8_t d[32], const uint8_t digest[32], uint8_
 int sbvh_k256_pubkey(const uint8_t d[32], uint8_t q[64]) { return k256_pubkey_from_private(d, q) ? 0 : -1; }
 // the secp256k1 host recovery on its own (k256_host.cc): 0 and the key, or -1 and 64 zero bytes
 int sbvh_k256_recover(const uint8_t rs[64], uint8_t recid, const uint8_t digest[32], uint8_t q[64]) { return k256_recover(rs, recid, digest, q) ? 0 : -1; }
+// the Keccak-256 host forms on their own (k256_host.cc): the digest, the address of 64 key bytes, and 0 with the signer's address or -1
+// with 20 zero bytes
+void sbvh_keccak256(const uint8_t* msg, size_t len, uint8_t digest[32]) { keccak256(msg, len, digest); }
+// items lo .. hi - 1 of an offset table, one after the other on the calling thread (tools/bench_keccak.py sets the number of threads)
+void sbvh_keccak256_range(const uint8_t* msgs, const uint64_t* moff, size_t lo, size_t hi, uint8_t* digests) {
+    for (size_t i = lo; i < hi; ++i) keccak256(moff[i + 1] > moff[i] ? msgs + moff[i] : nullptr, (size_t)(moff[i + 1] - moff[i]), digests + 32 * i);
+}
+void sbvh_k256_address(const uint8_t q[64], uint8_t addr[20]) { k256_address(q, addr); }
+int sbvh_k256_recover_address(const uint8_t rs[64], uint8_t recid, const uint8_t digest[32], uint8_t addr[20]) {
+    return k256_recover_address(rs, recid, digest, addr) ? 0 : -1;
+}
 // the BIP-340 host forms on their own (k256_host.cc): 0, or -1 (and zeroed output) for a refused key or record / an invalid signature
 int sbvh_k256_schnorr_expand(const uint8_t d[32], uint8_t rec[64]) { return k256_schnorr_expand(d, rec) ? 0 : -1; }
 int sbvh_k256_schnorr_sign(const uint8_t rec[64], const uint8_t msg[32], const uint8_t* aux, uint8_t sig[64]) {

@@ -12,6 +12,7 @@
 #include "../csrc/k256_recover.h"
 #include "../csrc/k256_schnorr.h"
 #include "../csrc/k256_schnorr_keyed.h"
+#include "../csrc/keccak256_dev.h"
 #include "p256_host.h"
 
 namespace sbvhost {
@@ -172,6 +173,28 @@ void words_to_be(uint8_t* b, const u32* w, int nwords) {
     for (int k = 0; k < nwords; ++k) { b[4 * k] = (uint8_t)(w[k] >> 24); b[4 * k + 1] = (uint8_t)(w[k] >> 16); b[4 * k + 2] = (uint8_t)(w[k] >> 8); b[4 * k + 3] = (uint8_t)w[k]; }
 }
 }  // namespace
+
+// ---- Keccak-256 and addresses (csrc/keccak256_dev.h): the lane code on the host -------------------------------------------------
+void keccak256(const uint8_t* msg, size_t len, uint8_t digest[32]) {
+    u32 h[8];
+    sbv::keccak256(msg, len, h);
+    words_to_be(digest, h, 8);
+}
+
+void k256_address(const uint8_t q[64], uint8_t addr[20]) {
+    u32 qw[16], a[5];
+    words_from_be(qw, q, 16);
+    sbv::k256_address(qw, a);
+    words_to_be(addr, a, 5);
+}
+
+bool k256_recover_address(const uint8_t rs[64], uint8_t recid, const uint8_t digest[32], uint8_t addr[20]) {
+    uint8_t q[64];
+    memset(addr, 0, 20);
+    if (!k256_recover(rs, recid, digest, q)) return false;
+    k256_address(q, addr);
+    return true;
+}
 
 bool k256_schnorr_expand(const uint8_t d_be[32], uint8_t rec[64]) {
     memset(rec, 0, 64);

@@ -1,5 +1,6 @@
 // k256_host.h — host-side secp256k1 key derivation and RFC 6979 signing for Scheme::SECP256K1 (verifier.h).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace sbvhost {
@@ -11,6 +12,13 @@ bool k256_sign_rfc6979(const uint8_t d_be[32], const uint8_t digest[32], uint8_t
 // flags = 0: the CPU form of the device entry, on the same lane functions (csrc/k256_recover.h) with u1 G from the signer's 8-bit comb.
 // false, and q zeroed, for a refused input.
 bool k256_recover(const uint8_t rs[64], uint8_t recid, const uint8_t digest[32], uint8_t q[64]);
+// Keccak-256 (Ethereum's keccak256, not SHA3-256) and the hashes around a recovery, by the rules of sbv_keccak256_msgs,
+// sbv_secp256k1_addresses and sbv_secp256k1_recover_addresses (include/sbv.h): the CPU forms of the device entries, on the same lane
+// code (csrc/keccak256_dev.h).  keccak256 reads msg[0 .. len) only (msg may be null when len is 0).  k256_address hashes any 64 bytes.
+// k256_recover_address is k256_recover followed by k256_address: false, and addr zeroed, for a refused input.
+void keccak256(const uint8_t* msg, size_t len, uint8_t digest[32]);
+void k256_address(const uint8_t q[64], uint8_t addr[20]);
+bool k256_recover_address(const uint8_t rs[64], uint8_t recid, const uint8_t digest[32], uint8_t addr[20]);
 // BIP-340 Schnorr by the rules of the sbv_secp256k1_schnorr_ entries (include/sbv.h): the CPU forms of the device entries, on the same
 // lane functions (csrc/k256_schnorr.h) with G from the signer's 8-bit comb.  rec = d | P.x, as secret as the key; aux may be null
 // (32 zero bytes).  expand and sign return false, with the output zeroed, for a refused key or record.  NOT constant-time.

@@ -122,6 +122,12 @@ int Backend::schnorr_verify_k256(const uint8_t* pks, const uint8_t* msgs, const 
     });
     return 0;
 }
+int Backend::keccak256_msgs(const uint8_t* msgs, const uint64_t* moff, size_t n, uint8_t* digests) {
+    parallel_chunks(n, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) keccak256(moff[i + 1] > moff[i] ? msgs + moff[i] : nullptr, (size_t)(moff[i + 1] - moff[i]), digests + 32 * i);
+    });
+    return 0;
+}
 int Backend::schnorr_sign_k256(const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs, const uint8_t* aux,
                                size_t n, uint8_t* sigs, uint8_t* ok) {
     if (n == 0) return 0;
@@ -221,6 +227,14 @@ class SbvBackend : public Backend {
     int recover_k256(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) override {
         if (rc_ != SBV_OK) return rc_;
         return sbv_secp256k1_recover(sigs, recid, digests, n, 0, pubs, ok);
+    }
+    int recover_addresses_k256(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint8_t* addrs, uint8_t* ok) override {
+        if (rc_ != SBV_OK) return rc_;
+        return sbv_secp256k1_recover_addresses(sigs, recid, digests, n, 0, addrs, ok);
+    }
+    int keccak256_msgs(const uint8_t* msgs, const uint64_t* moff, size_t n, uint8_t* digests) override {
+        if (rc_ != SBV_OK) return rc_;
+        return sbv_keccak256_msgs(msgs, moff, n, digests);
     }
     int schnorr_verify_k256(const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok) override {
         if (rc_ != SBV_OK) return rc_;
@@ -418,6 +432,12 @@ class CallbackBackend : public Backend {
     int recover_k256(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) override {
         parallel_chunks(n, [&](size_t lo, size_t hi) {
             for (size_t i = lo; i < hi; ++i) ok[i] = k256_recover(sigs + 64 * i, recid[i], digests + 32 * i, pubs + 64 * i) ? 1 : 0;
+        });
+        return 0;
+    }
+    int recover_addresses_k256(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint8_t* addrs, uint8_t* ok) override {
+        parallel_chunks(n, [&](size_t lo, size_t hi) {
+            for (size_t i = lo; i < hi; ++i) ok[i] = k256_recover_address(sigs + 64 * i, recid[i], digests + 32 * i, addrs + 20 * i) ? 1 : 0;
         });
         return 0;
     }
@@ -1440,6 +1460,34 @@ Status Verifier::RecoverSigners(const uint8_t* sigs65, const uint8_t* digests, s
     const int rc = co_.backend().recover_k256(sigs.data(), recid.data(), digests, n, pubs, ok);
     if (rc == -2) return Status::Unavailable("the backend has no secp256k1 recovery");
     if (rc != 0) return Status::Unavailable("secp256k1 recovery failed on the backend");
+    return Status::Ok();
+}
+
+Status Verifier::RecoverAddresses(const uint8_t* sigs65, const uint8_t* digests, size_t n, uint8_t* addrs20, uint8_t* ok) {
+    if (!k256()) return Status::Invalid("RecoverAddresses needs Scheme::SECP256K1");
+    if (n == 0) return Status::Ok();
+    // r | s | v -> r | s and the recovery id, by the rule of RecoverSigners
+    std::vector<uint8_t> sigs(64 * n), recid(n);
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(&sigs[64 * i], sigs65 + 65 * i, 64);
+        const uint8_t v = sigs65[65 * i + 64];
+        recid[i] = v <= 3 ? v : (v >= 27 && v <= 30 ? (uint8_t)(v - 27) : 255);
+    }
+    const int rc = co_.backend().recover_addresses_k256(sigs.data(), recid.data(), digests, n, addrs20, ok);
+    if (rc == -2) return Status::Unavailable("the backend has no secp256k1 address recovery");
+    if (rc != 0) return Status::Unavailable("secp256k1 address recovery failed on the backend");
+    return Status::Ok();
+}
+
+Status Verifier::Keccak256Batch(const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, uint8_t* digests) {
+    if (n == 0) return Status::Ok();
+    if (!msg_offsets || !digests) return Status::Invalid("Keccak256Batch: null pointer");
+    if (msg_offsets[0] != 0) return Status::Invalid("Keccak256Batch: the offset table must start at 0");
+    for (size_t i = 0; i < n; ++i)
+        if (msg_offsets[i + 1] < msg_offsets[i]) return Status::Invalid("Keccak256Batch: the offset table decreases");
+    if (msg_offsets[n] != 0 && !msgs) return Status::Invalid("Keccak256Batch: null pointer");
+    const int rc = co_.backend().keccak256_msgs(msgs, msg_offsets, n, digests);
+    if (rc != 0) return Status::Unavailable("Keccak-256 failed on the backend");
     return Status::Ok();
 }
 

@@ -91,6 +91,15 @@ class Backend {
     virtual int recover_k256(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) {
         (void)sigs; (void)recid; (void)digests; (void)n; (void)pubs; (void)ok; return -2;
     }
+    // recover_k256 with the signer's 20-byte address Keccak-256(Qx | Qy)[12:] in place of the key (include/sbv.h:
+    // sbv_secp256k1_recover_addresses): addrs n x 20 bytes, ok as recover_k256 (a refused input: 20 zero bytes); -2 when unsupported
+    virtual int recover_addresses_k256(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint8_t* addrs, uint8_t* ok) {
+        (void)sigs; (void)recid; (void)digests; (void)n; (void)addrs; (void)ok; return -2;
+    }
+    // Keccak-256 of n messages (include/sbv.h: sbv_keccak256_msgs): message i is msgs[moff[i] .. moff[i+1]), moff starts at 0 and never
+    // decreases -> digests n x 32.  The default is a CPU loop over the host form (k256_host.cc); the GPU backend makes one device call.
+    // 0, or the backend's error code.
+    virtual int keccak256_msgs(const uint8_t* msgs, const uint64_t* moff, size_t n, uint8_t* digests);
     // BIP-340 Schnorr over secp256k1 (include/sbv.h: sbv_secp256k1_schnorr_verify, _sign): x-only keys n x 32, messages n x 32,
     // signatures n x 64 -> ok[i] = 1 per valid signature; records n_keys x 64 from the expansion, key_index (or null: i % n_keys),
     // aux n x 32 (or null: zero bytes) -> signatures and ok.  The default is a CPU loop over the host forms (k256_host.cc); the GPU
@@ -248,6 +257,15 @@ class Verifier {
     // recovered key (otherwise 64 zero bytes; any other v is refused).  One backend call (sbv_secp256k1_recover on the device); what an
     // integrator calls before RegisterClient / register_key_k256.  INVALID under another scheme, UNAVAILABLE on a backend error.
     Status RecoverSigners(const uint8_t* sigs65, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok);
+    // Scheme::SECP256K1 only: RecoverSigners with the signers' 20-byte addresses Keccak-256(Qx | Qy)[12:] in place of the keys, which
+    // is what traffic shaped like Ethereum's compares (ecrecover): same sigs65 and `v` rules (0..3 or 27..30, anything else refused),
+    // addrs20 = n x 20 bytes, ok[i] = 1 per recovered signer (otherwise 20 zero bytes).  One backend call
+    // (sbv_secp256k1_recover_addresses on the device).  EIP-155 `v`, EIP-191 prefixes and EIP-55 checksums are the caller's formatting.
+    Status RecoverAddresses(const uint8_t* sigs65, const uint8_t* digests, size_t n, uint8_t* addrs20, uint8_t* ok);
+    // Keccak-256 (Ethereum's keccak256) of n messages under any scheme: the digests RecoverAddresses and RecoverSigners take.  One
+    // backend call (sbv_keccak256_msgs on the device, a CPU loop otherwise).  INVALID for an offset table that does not start at 0 or
+    // decreases, UNAVAILABLE on a backend error.
+    Status Keccak256Batch(const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, uint8_t* digests);
     // Scheme::SECP256K1 only: BIP-340 Schnorr verification of n signatures as traffic shaped like Bitcoin's carries them since Taproot:
     // pks = n x 32 bytes x-only keys, msgs = n x 32 bytes, sigs = n x 64 bytes R.x | s -> ok[i] = 1 per valid signature.  One backend
     // call (sbv_secp256k1_schnorr_verify on the device, a CPU loop otherwise).  INVALID under another scheme, UNAVAILABLE on a backend error.

@@ -108,6 +108,15 @@ type K256BatchRecoverer interface {
 	RecoverBatchSecp256k1(sigs [][64]byte, recid []byte, digests [][32]byte, lowS bool) (pubs [][64]byte, ok []bool, err error)
 }
 
+// K256AddressRecoverer is K256BatchRecoverer with the signer's 20-byte address Keccak-256(Qx|Qy)[12:] in place of the key
+// (sbv_secp256k1_recover_addresses): what Ethereum's ecrecover returns and what traffic shaped like Ethereum's compares.  Rules, recid
+// and lowS are those of RecoverBatchSecp256k1; ok[i] = false, and a zero address, for a refused input.  The digests are Keccak-256 of
+// the transaction or message (sbv_keccak256_msgs).  EIP-155 v values, EIP-191 prefixes and EIP-55 checksums are the caller's
+// formatting.  An optional interface beside K256BatchRecoverer, so that existing backends need no change: callers type-assert.
+type K256AddressRecoverer interface {
+	RecoverAddressesSecp256k1(sigs [][64]byte, recid []byte, digests [][32]byte, lowS bool) (addrs [][20]byte, ok []bool, err error)
+}
+
 // K256Schnorr is the BIP-340 Schnorr pair of a backend over secp256k1 (sbv_secp256k1_schnorr_verify, _expand_keys and _sign): what
 // traffic shaped like Bitcoin's carries since Taproot.  VerifyBatchSchnorr: ok[i] = the verdict of BIP-340 "Verify" on the x-only key
 // pks[i], the 32-byte message msgs[i] and sigs[i] = R.x|s.  SignBatchSchnorr: signature i = BIP-340 "Default Signing" of msgs[i] under

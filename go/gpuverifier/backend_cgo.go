@@ -673,6 +673,42 @@ func (b *gpuBackend) RecoverBatchSecp256k1(sigs [][64]byte, recid []byte, digest
 	return pubs, ok, nil
 }
 
+// RecoverAddressesSecp256k1: sbv_secp256k1_recover_addresses (one device call; nothing secret is involved).
+func (b *gpuBackend) RecoverAddressesSecp256k1(sigs [][64]byte, recid []byte, digests [][32]byte, lowS bool) (addrs [][20]byte, ok []bool, err error) {
+	n := len(sigs)
+	if n == 0 || len(recid) != n || len(digests) != n {
+		return nil, nil, errors.New("gpuverifier: RecoverAddressesSecp256k1 needs one recovery id and one digest per signature")
+	}
+	sb := make([]byte, 64*n)
+	db := make([]byte, 32*n)
+	for i := 0; i < n; i++ {
+		copy(sb[64*i:], sigs[i][:])
+		copy(db[32*i:], digests[i][:])
+	}
+	var mode uint32
+	if lowS {
+		mode = 1 // SBV_K256_RECOVER_LOW_S
+	}
+	out := make([]byte, 20*n)
+	flags := make([]byte, n)
+	b.on(func() {
+		rc := C.sbv_secp256k1_recover_addresses(u8(sb), u8(recid), u8(db), C.size_t(n), C.uint32_t(mode), u8(out), u8(flags))
+		if rc != 0 {
+			err = lastError()
+		}
+	})
+	if err != nil {
+		return nil, nil, err
+	}
+	addrs = make([][20]byte, n)
+	ok = make([]bool, n)
+	for i := 0; i < n; i++ {
+		copy(addrs[i][:], out[20*i:20*i+20])
+		ok[i] = flags[i] != 0
+	}
+	return addrs, ok, nil
+}
+
 // VerifyBatchSchnorr: sbv_secp256k1_schnorr_verify (one device call; nothing secret is involved).
 func (b *gpuBackend) VerifyBatchSchnorr(pks [][32]byte, msgs [][32]byte, sigs [][64]byte) (ok []bool, err error) {
 	n := len(sigs)

@@ -284,6 +284,52 @@ sbv_secp256k1_recover_stream(const void* d_sigs, const void* d_recid, const void
  * Any other op is SBV_EINVAL. */
 int sbv_debug_secp256k1_recover_op(int op, const uint8_t* in, uint8_t* out, size_t n);
 
+/* Keccak-256 and Ethereum-style addresses: the two hashes at either end of a recovery.  Keccak-256 is the original Keccak at rate 136
+ * with the padding byte 0x01 (what Ethereum calls keccak256), NOT FIPS 202's SHA3-256, which differs in that one byte.
+ *   sbv_keccak256_msgs                msgs: all messages back to back, msg_offsets: n + 1 offsets, message i is
+ *                                     msgs[msg_offsets[i] .. msg_offsets[i+1]); digests: n x 32 bytes.  The offset table follows the rule
+ *                                     of sbv_ed25519_sign_msgs: it starts at 0 and never decreases, otherwise SBV_EINVAL; msgs may be
+ *                                     NULL when every message is empty.  The digests are exactly the `digests` array that
+ *                                     sbv_secp256k1_sign_batch and sbv_secp256k1_recover take.
+ *   sbv_secp256k1_addresses           pubs: m x 64 bytes Qx | Qy (big-endian, as sbv_secp256k1_pubkeys and sbv_secp256k1_recover emit);
+ *                                     addrs: m x 20 bytes, Keccak-256(Qx | Qy)[12..31].  A pure hash: the key is not checked against
+ *                                     the curve, and 64 zero bytes have an address like any other input.
+ *   sbv_secp256k1_recover_addresses   sbv_secp256k1_recover with the address in place of the key: what Ethereum's ecrecover returns.
+ *                                     Arrays, rules, flags and workspace (sbv_secp256k1_recover_workspace(n), 16-byte aligned) are
+ *                                     exactly that entry's; addrs: n x 20 bytes, ok: n bytes.  For every item ok[i] is that entry's
+ *                                     ok[i]; addrs[i] is the address of that entry's key when ok[i] = 1 and 20 zero bytes when
+ *                                     ok[i] = 0.  The stride of addrs is 20 bytes and byte 20 n is not written.
+ * EIP-155 `v` values, EIP-191 prefixes and EIP-55 checksums are the caller's formatting.
+ * The host-pointer forms use device buffers of the call's own size, wait for the result and free them.  The `_stream` forms take device
+ * pointers, launch on `hip_stream` and return without synchronising, under the stream contract of the `_dev` entries (DESIGN.md
+ * section 4.2.4) for every buffer they name, the workspace included.  The two hash entries own no state and upload nothing;
+ * sbv_secp256k1_recover_addresses_stream shares only the read-only 16-bit comb of G, uploaded (synchronously) by the first secp256k1
+ * call of the process, which may be this one.  In sbv_keccak256_msgs_stream nothing on the host sees the offsets: an item whose offset
+ * pair decreases gets 32 zero bytes and nothing of the messages is read for it; d_msgs may be NULL when every message is empty.
+ * They are named `_stream` for the reason the signer's entries are; their schedules are in tests/test_gpu_keccak.py.
+ * SBV_EINVAL: a null required pointer, an unknown flag bit, a bad offset table (host-pointer form), and for the `_stream` forms a
+ * device pointer to digests, keys, signatures or addresses that is not 4-byte aligned, a d_msg_offsets that is not 8-byte aligned, a
+ * d_work that is not 16-byte aligned or work_bytes too small; d_msgs may have any alignment.  SBV_ENOTINIT before sbv_init.  n == 0
+ * (m == 0) is SBV_OK and writes nothing.  Nothing here is secret. */
+int
+sbv_keccak256_msgs(const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, uint8_t* digests);
+int
+sbv_keccak256_msgs_stream(const void* d_msgs, const void* d_msg_offsets, size_t n, void* d_digests, void* hip_stream);
+int
+sbv_secp256k1_addresses(const uint8_t* pubs, size_t m, uint8_t* addrs);
+int
+sbv_secp256k1_addresses_stream(const void* d_pubs, size_t m, void* d_addrs, void* hip_stream);
+int
+sbv_secp256k1_recover_addresses(const uint8_t* sigs, const uint8_t* recid, const uint8_t* digests, size_t n, uint32_t flags, uint8_t* addrs,
+                                uint8_t* ok);
+int
+sbv_secp256k1_recover_addresses_stream(const void* d_sigs, const void* d_recid, const void* d_digests, size_t n, uint32_t flags,
+                                       void* d_addrs, void* d_ok, void* d_work, size_t work_bytes, void* hip_stream);
+/* Test only: one case of a unit operation of Keccak per lane on the device, host pointers.
+ *   op 0   in: 200 bytes, the 25 lanes of a state A[x + 5 y], each little-endian   out: 200 bytes, the state after one Keccak-f[1600]
+ * Any other op is SBV_EINVAL. */
+int sbv_debug_keccak_op(int op, const uint8_t* in, uint8_t* out, size_t n);
+
 /* BIP-340 Schnorr signatures over secp256k1 (Bitcoin's since Taproot): batch verification, key expansion and batch signing.  Keys are
  * x-only (32 bytes: the x of the point with even y), messages are 32 bytes, signatures are 64 bytes R.x | s, all big-endian; `ok`
  * is one byte per item (0 or 1), as in the sign, pubkeys and recover family, not a bitmap.
