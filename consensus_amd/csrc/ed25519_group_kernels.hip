@@ -244,11 +244,7 @@ hipError_t launch_ed25519_verify_grouped(const uint8_t* d_tuples, size_t n, cons
                                          u32* d_qtab, const aniels* d_btab, const edcomb& bcomb, uint8_t* d_bitmap, hipStream_t stream,
                                          const GroupSync& y, hipEvent_t* prof, int* prof_pairs) {
     if (n == 0) return hipSuccess;
-    GroupState g;
-    g.ht = b.ht; g.ht_mask = b.ht_mask; g.rep = b.rep; g.cnt = b.cnt; g.slot_of = b.slot_of; g.group_rep = b.group_rep;
-    g.counters = b.counters; g.grp_idx = b.grp_idx; g.ung_idx = b.ung_idx; g.slots = b.slots;
-    g.max_groups = b.max_groups; g.seed = b.seed;
-    g.gcount = b.gcount; g.gcursor = b.gcount ? b.gcount + b.max_groups : nullptr; g.grp_of = b.grp_of; g.ung_cand = b.ung_cand;
+    GroupState g = group_state_of(b);
     // key-sorted grouped list (p256_group.h): the Q phase walks runs of equal keys; the accumulator is tuple-major so that the
     // G phase can still start at once, in tuple order
     const size_t sort_lds = (size_t)b.max_groups * sizeof(u32);
@@ -278,12 +274,14 @@ hipError_t launch_ed25519_verify_grouped(const uint8_t* d_tuples, size_t n, cons
     hipLaunchKernelGGL((k_key_cache_insert_t<128, 64, 8>), dim3((b.max_groups + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, eb.kc, b.tslot);
     const u32 table_slots = eb.kc.cap + b.max_groups;
     // hot keys (ed25519_group.h): only with the cache on, a pool to promote into and the key-sorted list
-    const bool hot_on = eb.wtab && eb.kwide && eb.wide && eb.kc.enabled && g.sorted;
-    const HotKeys hk = {eb.wtab, hot_on ? eb.kwide : nullptr, eb.khits, eb.hot, eb.plist, eb.kc.cap, eb.wide_cap, eb.promote_min, eb.wowner, eb.elist};
+    const HotPool& hp = eb.hp;
+    uint8_t* const wtab = static_cast<uint8_t*>(hp.wtab);
+    const bool hot_on = hp.wtab && hp.kwide && eb.wide && eb.kc.enabled && g.sorted;
+    const HotKeys hk = hot_view(hp, eb.kc, hot_on);
     const uint8_t* wide = hot_on ? eb.wide : nullptr;
     if (hot_on) SBV_TRY(hipEventRecord(y.ev_cache, y.side_a));         // table slots assigned: the class kernel (side_b) reads them
     SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_assign, 0));
-    if (hot_on) SBV_TRY(hipMemsetAsync(eb.hot + 1, 0, 3 * sizeof(u32), y.side_b));       // behind the previous batch's builder, which reads hot[1]
+    if (hot_on) SBV_TRY(hipMemsetAsync(hp.hot + 1, 0, 3 * sizeof(u32), y.side_b));       // behind the previous batch's builder, which reads hot[1]
     if (g.sorted) {
         const unsigned tiles = (unsigned)((n + SBV_SORT_TILE - 1) / SBV_SORT_TILE);
         hipLaunchKernelGGL(k_group_classify, dim3(gn), dim3(256), 0, y.side_b, n, g, b.ung_cand, b.counters + 4);
@@ -358,8 +356,8 @@ hipError_t launch_ed25519_verify_grouped(const uint8_t* d_tuples, size_t n, cons
         // Like the first Q launch it lets the ungrouped list's key check go first.
         SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_class, 0));
         if (g.sorted && keycheck_first) SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_narrow, 0));
-        hipLaunchKernelGGL(k_ed_qphase_wide, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, y.side_b, d_tuples, g, eb.kvalid, b.tslot, wide, eb.kwide, eb.wtab,
-                           eb.hot + 2, b.gacc, eb.okb, b.acc);
+        hipLaunchKernelGGL(k_ed_qphase_wide, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, y.side_b, d_tuples, g, eb.kvalid, b.tslot, wide, hp.kwide, wtab,
+                           hp.hot + 2, b.gacc, eb.okb, b.acc);
         SBV_TRY(hipEventRecord(y.ev_wide, y.side_b));
         SBV_TRY(hipStreamWaitEvent(stream, y.ev_wide, 0));
     }
@@ -372,12 +370,12 @@ hipError_t launch_ed25519_verify_grouped(const uint8_t* d_tuples, size_t n, cons
         // may have built) and behind the wide pass (an evicted comb is rewritten) — stream order: the clock sweep, which slots get a comb, the
         // evictions; then — the next batch's side_a may rewrite tslot from here on — the combs themselves and their publication.
         // The next batch's class kernel queues up behind all of it on this stream: a comb is used only once it is complete.
-        if (eb.hot_tick % SBV_HOT_DECAY_EVERY == SBV_HOT_DECAY_EVERY - 1) hipLaunchKernelGGL(k_hot_decay, dim3((eb.kc.cap + 255) / 256), dim3(256), 0, y.side_b, hk);
+        if (hp.hot_tick % SBV_HOT_DECAY_EVERY == SBV_HOT_DECAY_EVERY - 1) hipLaunchKernelGGL(k_hot_decay, dim3((eb.kc.cap + 255) / 256), dim3(256), 0, y.side_b, hk);
         hipLaunchKernelGGL(k_promote_select, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, eb.kvalid, hk);
         hipLaunchKernelGGL(k_promote_evict, dim3(1), dim3(1024), 0, y.side_b, hk);
         SBV_TRY(hipEventRecord(y.ev_promoted, y.side_b));
-        hipLaunchKernelGGL(k_ed_promote_window, dim3(SBV_ED_HOT_BUILD_BLOCKS), dim3(64), 0, y.side_b, eb.plist, eb.hot, eb.ktab, eb.ptmp, eb.wtab);
-        hipLaunchKernelGGL(k_promote_publish, dim3(1), dim3(64), 0, y.side_b, eb.plist, eb.hot, eb.kwide, eb.wowner);
+        hipLaunchKernelGGL(k_ed_promote_window, dim3(SBV_ED_HOT_BUILD_BLOCKS), dim3(64), 0, y.side_b, hp.plist, hp.hot, eb.ktab, hp.ptmp, wtab);
+        hipLaunchKernelGGL(k_promote_publish, dim3(1), dim3(64), 0, y.side_b, hp.plist, hp.hot, hp.kwide, hp.wowner);
     }
     SBV_TRY(hipStreamWaitEvent(stream, y.ev_generic, 0));
     hipLaunchKernelGGL(k_pack_bitmap, dim3((unsigned)(((n + 7) / 8 + 255) / 256)), dim3(256), 0, stream, b.acc, n, d_bitmap);

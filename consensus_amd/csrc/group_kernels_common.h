@@ -101,6 +101,10 @@ static __global__ __launch_bounds__(64) void k_key_cache_insert_t(const uint8_t*
 // ---- hot keys: the scheme-independent kernels (p256_group.h "hot keys" / "life cycle"; round 6: shared with the Ed25519 step) ----------
 // wtab: the pool of wide combs (a scheme's own entry type: opaque here); kwide == nullptr = feature off / no pool
 struct HotKeys { const void* wtab; u32* kwide; u32* khits; u32* hot; u32* plist; u32 cache_cap, wide_cap, promote_min; u32* wowner; u32* elist; };
+// the kernels' view of a scheme's pool `p` over the slots of its cache `kc`; hot_on = this batch uses it (each launcher's own conditions)
+inline HotKeys hot_view(const HotPool& p, const KeyCache& kc, bool hot_on) {
+    return {p.wtab, hot_on ? p.kwide : nullptr, p.khits, p.hot, p.plist, kc.cap, p.wide_cap, p.promote_min, p.wowner, p.elist};
+}
 static __device__ __forceinline__ u32 promote_live(const u32* hot) { const u32 c = hot[1]; return c < SBV_PROMOTE_MAX ? c : SBV_PROMOTE_MAX; }
 // Life cycle of the hot keys (p256_group.h, round 6): the clock sweep and the evictions.
 static __global__ __launch_bounds__(256) void k_hot_decay(HotKeys hk) {

@@ -196,10 +196,7 @@ __global__ __launch_bounds__(64) void k_k256_promote_build(const u32* __restrict
 hipError_t launch_k256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_in, size_t n, const GroupBuffers& b, const KeyPool& kp, u32* d_qtab,
                                       const kapt* d_gtab, const kapt* d_gcomb, int gcomb_bits, uint8_t* d_bitmap, hipStream_t stream, const GroupSync& y, hipEvent_t* prof, int* prof_pairs) {
     if (n == 0) return hipSuccess;
-    GroupState g;
-    g.ht = b.ht; g.ht_mask = b.ht_mask; g.rep = b.rep; g.cnt = b.cnt; g.slot_of = b.slot_of; g.group_rep = b.group_rep;
-    g.counters = b.counters; g.grp_idx = b.grp_idx; g.ung_idx = b.ung_idx; g.slots = b.slots; g.max_groups = b.max_groups; g.seed = b.seed;
-    g.gcount = b.gcount; g.gcursor = b.gcount + b.max_groups; g.grp_of = b.grp_of; g.ung_cand = b.ung_cand;
+    GroupState g = group_state_of(b);
     g.sorted = k256_group_step_sorted(y, b) ? 1u : 0u;
     group_set_threshold(g, b.min_count);
     Scratch s = s_in;
@@ -225,8 +222,10 @@ hipError_t launch_k256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
     hipLaunchKernelGGL((k_key_cache_lookup_t<160, 96, 16>), dim3((b.max_groups + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, kp.kc, b.tslot, b.cold);
     hipLaunchKernelGGL((k_key_cache_insert_t<160, 96, 16>), dim3((b.max_groups + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, kp.kc, b.tslot);
     // hot keys (k256_group.h): only with a pool to promote into, the cache on and the key-sorted list — the Ed25519 launcher's conditions
-    const bool hot_on = kp.wtab && kp.kwide && kp.wide && kp.build_blocks && kp.kc.enabled && g.sorted;
-    const HotKeys hk = {kp.wtab, hot_on ? kp.kwide : nullptr, kp.khits, kp.hot, kp.plist, kp.kc.cap, kp.wide_cap, kp.promote_min, kp.wowner, kp.elist};
+    const HotPool& hp = kp.hp;
+    kapt* const wtab = static_cast<kapt*>(hp.wtab);
+    const bool hot_on = hp.wtab && hp.kwide && kp.wide && kp.build_blocks && kp.kc.enabled && g.sorted;
+    const HotKeys hk = hot_view(hp, kp.kc, hot_on);
     const uint8_t* wide = hot_on ? kp.wide : nullptr;
     if (hot_on) SBV_TRY(hipEventRecord(y.ev_cache, y.side_a));         // table slots assigned: the class kernel (side_b) reads them
     {   // stage A: SBV_K256_PREP_T tuples per lane share one inversion (Montgomery's trick).  Measured in round 4
@@ -235,7 +234,7 @@ hipError_t launch_k256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
         hipLaunchKernelGGL(k_k256_prep_chunk, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(64), 0, stream, d_tuples, n, s, SBV_K256_PREP_T);
     }
     SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_assign, 0));
-    if (hot_on) SBV_TRY(hipMemsetAsync(kp.hot + 1, 0, 3 * sizeof(u32), y.side_b));       // behind the previous batch's builder, which reads hot[1]
+    if (hot_on) SBV_TRY(hipMemsetAsync(hp.hot + 1, 0, 3 * sizeof(u32), y.side_b));       // behind the previous batch's builder, which reads hot[1]
     hipLaunchKernelGGL(k_group_classify, dim3(gn), dim3(256), 0, y.side_b, n, g, b.ung_cand, b.counters + 4);
     hipLaunchKernelGGL(k_k256_keycheck, dim3(gn), dim3(256), 0, y.side_b, d_tuples, g, b.acc);
     const unsigned tiles = (unsigned)((n + SBV_SORT_TILE - 1) / SBV_SORT_TILE);
@@ -276,18 +275,18 @@ hipError_t launch_k256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
         // on this stream: a comb is used only once it is complete.  (The wave rule reads the valid byte of every lane's slot, a cold group's
         // included: chunk 0's chain writes those, and side_b has waited for it in front of chunk 0's rows — both Q kernels see them final.)
         SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_class, 0));
-        hipLaunchKernelGGL(k_k256_qphase_wide, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, y.side_b, s, g, kvalid, b.tslot, table_slots, wide, kp.kwide,
-                           reinterpret_cast<const kapt*>(kp.wtab), kp.wide_cap, kp.hot + 2, b.gacc, b.acc);
+        hipLaunchKernelGGL(k_k256_qphase_wide, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, y.side_b, s, g, kvalid, b.tslot, table_slots, wide, hp.kwide,
+                           wtab, hp.wide_cap, hp.hot + 2, b.gacc, b.acc);
         SBV_TRY(hipEventRecord(y.ev_wide, y.side_b));
         SBV_TRY(hipStreamWaitEvent(stream, y.ev_wide, 0));
         for (int c = 0; c < chunks; ++c) SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_tables[c], 0));
-        if (kp.hot_tick % SBV_HOT_DECAY_EVERY == SBV_HOT_DECAY_EVERY - 1) hipLaunchKernelGGL(k_hot_decay, dim3((kp.kc.cap + 255) / 256), dim3(256), 0, y.side_b, hk);
+        if (hp.hot_tick % SBV_HOT_DECAY_EVERY == SBV_HOT_DECAY_EVERY - 1) hipLaunchKernelGGL(k_hot_decay, dim3((kp.kc.cap + 255) / 256), dim3(256), 0, y.side_b, hk);
         hipLaunchKernelGGL(k_promote_select, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, kvalid, hk);
         hipLaunchKernelGGL(k_promote_evict, dim3(1), dim3(1024), 0, y.side_b, hk);
         SBV_TRY(hipEventRecord(y.ev_promoted, y.side_b));
-        hipLaunchKernelGGL(k_k256_promote_build, dim3(kp.build_blocks), dim3(64), 0, y.side_b, kp.plist, kp.hot, ktab, kp.kc.cap, kp.ptmp,
-                           reinterpret_cast<kapt*>(kp.wtab), kp.wide_cap);
-        hipLaunchKernelGGL(k_promote_publish, dim3(1), dim3(64), 0, y.side_b, kp.plist, kp.hot, kp.kwide, kp.wowner);
+        hipLaunchKernelGGL(k_k256_promote_build, dim3(kp.build_blocks), dim3(64), 0, y.side_b, hp.plist, hp.hot, ktab, kp.kc.cap, hp.ptmp,
+                           wtab, hp.wide_cap);
+        hipLaunchKernelGGL(k_promote_publish, dim3(1), dim3(64), 0, y.side_b, hp.plist, hp.hot, hp.kwide, hp.wowner);
     }
     hipLaunchKernelGGL(k_pack_bitmap, dim3((unsigned)(((n + 7) / 8 + 255) / 256)), dim3(256), 0, stream, b.acc, n, d_bitmap);
 #undef SBV_TRY

@@ -462,6 +462,20 @@ SBV_HD int group_wave_class(bool all_dead, bool all_dead_or_wide, bool all_dead_
 #define SBV_PROMOTE_MAX 64u
 #define SBV_HOT_BITS 16
 #define SBV_HOT_HITS_MAX 0x3FFFFFFFu
+// The host's handle on one scheme's hot-key pool: the device arrays above and the settings the launchers read.  One per scheme, beside
+// the KeyCache whose slots it serves (GroupBuffers, EdGroupBuffers, KeyPool); the kernels see it as a HotKeys view
+// (group_kernels_common.h).  wtab == nullptr = no pool: the feature is off.
+struct HotPool {
+    void* wtab = nullptr;         // [wide_cap] combs of the scheme's own entry type and size: cast where it is used
+    u32 *kwide = nullptr, *khits = nullptr;     // [kc.cap]
+    u32* hot = nullptr;           // [4] combs handed out | promotions of this batch | lanes of the wide pass | eviction candidates
+    u32* plist = nullptr;         // [2 x SBV_PROMOTE_MAX] (slot, comb) of this batch's promotions
+    u32* wowner = nullptr;        // [wide_cap] the cache slot that owns comb w, SBV_WIDE_NONE before its first owner
+    u32* elist = nullptr;         // [SBV_PROMOTE_MAX] slots that found the pool full in this batch: the eviction candidates
+    u32* ptmp = nullptr;          // the scheme's comb builder's scratch
+    u32 wide_cap = 0, promote_min = 4096;
+    u32 hot_tick = 0;             // grouped batches with hot keys on so far: every SBV_HOT_DECAY_EVERY-th halves the hit counters
+};
 SBV_HD void group_hot_class_lane(u32 k, const GroupState& g, const u32* tslot, const uint8_t* cold, u32 cache_cap, const u32* kwide, u32* khits,
                                  uint8_t* wide) {
     const u32 slot = tslot[k];

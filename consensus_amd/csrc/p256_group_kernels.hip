@@ -573,11 +573,7 @@ hipError_t launch_p256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
                                       u32* d_qtab, const apt* d_g16, const gcomb& d_g16r, uint8_t* d_bitmap, hipStream_t stream,
                                       const GroupSync& y, hipEvent_t after_prep, hipEvent_t* prof, int* prof_pairs) {
     if (n == 0) return hipSuccess;
-    GroupState g;
-    g.ht = b.ht; g.ht_mask = b.ht_mask; g.rep = b.rep; g.cnt = b.cnt; g.slot_of = b.slot_of; g.group_rep = b.group_rep;
-    g.counters = b.counters; g.grp_idx = b.grp_idx; g.ung_idx = b.ung_idx; g.slots = b.slots;
-    g.max_groups = b.max_groups; g.seed = b.seed;
-    g.gcount = b.gcount; g.gcursor = b.gcount ? b.gcount + b.max_groups : nullptr; g.grp_of = b.grp_of; g.ung_cand = b.ung_cand;
+    GroupState g = group_state_of(b);
     // key-sorted grouped list: needs the per-tuple records of stage A; one LDS word per group while the histogram fits (<= 16 384
     // groups), plain global atomics beyond (the kernels decide: group_kernels_common.h)
     const size_t sort_lds = (size_t)(b.max_groups > SBV_SORT_LDS_GROUPS ? SBV_SORT_LDS_GROUPS : b.max_groups) * sizeof(u32);
@@ -593,9 +589,11 @@ hipError_t launch_p256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
     const u32 full_min = coop ? 0u : b.full_min;
     const u32 table_slots = b.kc.cap + b.max_groups;
     // hot keys (p256_group.h): only with the cache on, a pool to promote into and the key-sorted list
-    const bool hot_on = b.wtab && b.kwide && b.kc.enabled && g.sorted;
-    const HotKeys hk = {b.wtab, hot_on ? b.kwide : nullptr, b.khits, b.hot, b.plist, b.kc.cap, b.wide_cap, b.promote_min, b.wowner, b.elist};
-    const widekeys wk = hot_on ? widekeys_make(b.wtab, b.kwide, SBV_HOT_BITS) : widekeys_none();
+    const HotPool& hp = b.hp;
+    apt* const wtab = static_cast<apt*>(hp.wtab);
+    const bool hot_on = hp.wtab && hp.kwide && b.kc.enabled && g.sorted;
+    const HotKeys hk = hot_view(hp, b.kc, hot_on);
+    const widekeys wk = hot_on ? widekeys_make(wtab, hp.kwide, SBV_HOT_BITS) : widekeys_none();
     static const bool q_lds = [] { const char* v = getenv("SBV_QPHASE_LDS"); return v && v[0] == '1'; }();      // the LDS-staged form of the chunks' launches (opt-in)
     hipError_t e;
 #define SBV_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
@@ -623,7 +621,7 @@ hipError_t launch_p256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
     SBV_TRY(launch_p256_prep_blocks(d_tuples, n, s, stream, 0, pblocks));
     // side_b: split
     SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_assign, 0));
-    if (hot_on) SBV_TRY(hipMemsetAsync(b.hot + 1, 0, 3 * sizeof(u32), y.side_b));        // promotions and wide-pass lanes of THIS batch: behind the previous batch's builder, which reads hot[1]
+    if (hot_on) SBV_TRY(hipMemsetAsync(hp.hot + 1, 0, 3 * sizeof(u32), y.side_b));        // promotions and wide-pass lanes of THIS batch: behind the previous batch's builder, which reads hot[1]
     if (!g.sorted) hipLaunchKernelGGL(k_group_split, dim3(gn), dim3(256), 0, y.side_b, d_tuples, n, g, b.acc);
     if (g.sorted) {             // classify, check the ungrouped candidates' keys, counting sort of the grouped tuples by key;
                                 // ev_split then also stands for "the sorted list is final"
@@ -676,7 +674,7 @@ hipError_t launch_p256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
             // latency chain at low occupancy, timeline_hot_4096_r05q.txt), as soon as the G phase is done.
             SBV_TRY(hipStreamWaitEvent(y.side_a, y.ev_generic, 0));
             SBV_TRY(hipStreamWaitEvent(y.side_a, y.ev_class, 0));
-            hipLaunchKernelGGL((k_verify_keyed_q<SBV_Q_WIDE, true>), dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, y.side_a, s, g, b.ktab, b.kvalid, b.tslot, b.full, b.wide, wk, b.hot + 2,
+            hipLaunchKernelGGL((k_verify_keyed_q<SBV_Q_WIDE, true>), dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, y.side_a, s, g, b.ktab, b.kvalid, b.tslot, b.full, b.wide, wk, hp.hot + 2,
                                table_slots, b.gacc, b.acc, 0, SBV_GTAB_WINDOWS);
             SBV_TRY(hipEventRecord(y.ev_wide, y.side_a));
         }
@@ -706,7 +704,7 @@ hipError_t launch_p256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
             // the rows of every chunk (side_b has its own in stream order and waits for the other table stream's).
             SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_generic, 0));
             for (int cc = 0; cc < chunks; ++cc) SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_tables[cc], 0));
-            if (g.sorted) hipLaunchKernelGGL((k_verify_keyed_q<SBV_Q_NARROW, true>), dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, y.side_b, s, g, b.ntab, b.kvalid, b.tslot, b.full, b.wide, wk, b.hot + 2,
+            if (g.sorted) hipLaunchKernelGGL((k_verify_keyed_q<SBV_Q_NARROW, true>), dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, y.side_b, s, g, b.ntab, b.kvalid, b.tslot, b.full, b.wide, wk, hp.hot + 2,
                                              table_slots, b.gacc, b.acc, 0, SBV_GTAB_WINDOWS);
             else hipLaunchKernelGGL(k_verify_keyed_q_list<SBV_Q_NARROW>, dim3(gv), dim3(SBV_VERIFY_BLOCK), 0, y.side_b, s, g, b.ntab, b.kvalid, b.tslot, b.full,
                                     table_slots, b.gacc, b.acc, 0, SBV_GTAB_WINDOWS, 1);
@@ -719,9 +717,9 @@ hipError_t launch_p256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
                                                    table_slots, b.gacc, b.acc, j_first, j_end);
         else if (q_lds) hipLaunchKernelGGL((k_verify_keyed_q_lds<false>), dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, s, g, b.ktab, b.kvalid, b.tslot, b.full, b.wide,
                                            table_slots, b.gacc, b.acc, j_first, j_end);
-        else if (last) hipLaunchKernelGGL((k_verify_keyed_q<SBV_Q_FULL, true>), dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, s, g, b.ktab, b.kvalid, b.tslot, b.full, b.wide, wk, b.hot + 2,
+        else if (last) hipLaunchKernelGGL((k_verify_keyed_q<SBV_Q_FULL, true>), dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, s, g, b.ktab, b.kvalid, b.tslot, b.full, b.wide, wk, hp.hot + 2,
                                           table_slots, b.gacc, b.acc, j_first, j_end);
-        else hipLaunchKernelGGL((k_verify_keyed_q<SBV_Q_FULL, false>), dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, s, g, b.ktab, b.kvalid, b.tslot, b.full, b.wide, wk, b.hot + 2,
+        else hipLaunchKernelGGL((k_verify_keyed_q<SBV_Q_FULL, false>), dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, s, g, b.ktab, b.kvalid, b.tslot, b.full, b.wide, wk, hp.hot + 2,
                                 table_slots, b.gacc, b.acc, j_first, j_end);
         if (prof) SBV_TRY(hipEventRecord(prof[2 * c + 1], stream));
     }
@@ -734,13 +732,13 @@ hipError_t launch_p256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
     hipLaunchKernelGGL(k_group_table_mark, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, b.cold, b.full, b.needfill, table_slots, b.kfull);
     if (hot_on) {
         // the life cycle (round 6): the clock sweep every SBV_HOT_DECAY_EVERY-th batch
-        if (b.hot_tick % SBV_HOT_DECAY_EVERY == SBV_HOT_DECAY_EVERY - 1) hipLaunchKernelGGL(k_hot_decay, dim3((b.kc.cap + 255) / 256), dim3(256), 0, y.side_b, hk);
+        if (hp.hot_tick % SBV_HOT_DECAY_EVERY == SBV_HOT_DECAY_EVERY - 1) hipLaunchKernelGGL(k_hot_decay, dim3((b.kc.cap + 255) / 256), dim3(256), 0, y.side_b, hk);
         // promotions (p256_group.h: hot keys): which slots (the evictions when the pool is full), and their base points (tiny launches
         // that read tslot and the tables)
         hipLaunchKernelGGL(k_promote_select, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, b.kvalid, hk);
         hipLaunchKernelGGL(k_promote_evict, dim3(1), dim3(1024), 0, y.side_b, hk);
         const widebuild wb = widebuild_make(SBV_HOT_BITS);
-        hipLaunchKernelGGL(k_promote_bases, dim3((SBV_PROMOTE_MAX * 2 * (u32)wb.windows + 63) / 64), dim3(64), 0, y.side_b, b.plist, b.hot, b.ktab, b.pbases);
+        hipLaunchKernelGGL(k_promote_bases, dim3((SBV_PROMOTE_MAX * 2 * (u32)wb.windows + 63) / 64), dim3(64), 0, y.side_b, hp.plist, hp.hot, b.ktab, b.pbases);
     }
     // ev_promoted: the tail no longer reads tslot, the class bytes or the per-batch tables — the next batch's side_a (which rewrites them)
     // waits for it; the builder and the publication follow on side_b, in front of the next batch's own side_b work (its table classes
@@ -749,10 +747,10 @@ hipError_t launch_p256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
     if (hot_on) {
         const widebuild wb = widebuild_make(SBV_HOT_BITS);
         const size_t stride = gcomb_entries(SBV_HOT_BITS);
-        hipLaunchKernelGGL(k_promote_chains, dim3((SBV_PROMOTE_MAX * (u32)wb.windows * 2u + 63) / 64), dim3(64), 0, y.side_b, b.pbases, b.plist, b.hot, wb, stride, b.ptmp, b.wtab);
+        hipLaunchKernelGGL(k_promote_chains, dim3((SBV_PROMOTE_MAX * (u32)wb.windows * 2u + 63) / 64), dim3(64), 0, y.side_b, b.pbases, hp.plist, hp.hot, wb, stride, hp.ptmp, wtab);
         const size_t fill_lanes = (size_t)SBV_PROMOTE_MAX * wb.windows * (wb.giants - 1) * widebuild_fill_chunks(wb);
-        hipLaunchKernelGGL(k_promote_fill, dim3((unsigned)((fill_lanes + 255) / 256)), dim3(256), 0, y.side_b, b.plist, b.hot, wb, stride, b.wtab);
-        hipLaunchKernelGGL(k_promote_publish, dim3(1), dim3(64), 0, y.side_b, b.plist, b.hot, b.kwide, b.wowner);
+        hipLaunchKernelGGL(k_promote_fill, dim3((unsigned)((fill_lanes + 255) / 256)), dim3(256), 0, y.side_b, hp.plist, hp.hot, wb, stride, wtab);
+        hipLaunchKernelGGL(k_promote_publish, dim3(1), dim3(64), 0, y.side_b, hp.plist, hp.hot, hp.kwide, hp.wowner);
     }
 #undef SBV_TRY
     if (prof && prof_pairs) *prof_pairs = coop ? 1 : chunks;

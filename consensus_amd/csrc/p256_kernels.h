@@ -73,18 +73,10 @@ struct GroupBuffers {
     // [kc.cap + max_groups] what a table slot holds across batches; the per-key signature count from which a full table pays
     uint8_t *full = nullptr, *needfill = nullptr, *kfull = nullptr;
     u32 full_min = 256;
-    // hot keys (p256_group.h, round 5): wide combs of promoted cache slots and their bookkeeping; wtab == nullptr = off
-    apt* wtab = nullptr;          // [wide_cap][gcomb_entries(SBV_HOT_BITS)]
-    u32 *kwide = nullptr, *khits = nullptr;     // [kc.cap]
-    u32* hot = nullptr;           // [4] wide combs handed out | promotions of this batch | lanes of the wide pass | spare
-    u32* plist = nullptr;         // [2 x SBV_PROMOTE_MAX] (slot, wide index)
-    u32* wowner = nullptr;        // [wide_cap] the cache slot that owns comb w (round 6: evictions), SBV_WIDE_NONE before its first owner
-    u32* elist = nullptr;         // [SBV_PROMOTE_MAX] slots that found the pool full in this batch: the eviction candidates
-    u32 hot_tick = 0;             // grouped batches with hot keys on so far: every SBV_HOT_DECAY_EVERY-th halves the hit counters
-    apt* pbases = nullptr;        // [SBV_PROMOTE_MAX][2 x 17] base points of the promotions under construction
-    u32* ptmp = nullptr;          // the builder's chain scratch for SBV_PROMOTE_MAX keys
-    uint8_t* wide = nullptr;      // [max_groups] this batch's groups that may take the wide pass
-    u32 wide_cap = 0, promote_min = 4096;
+    // hot keys (p256_group.h, round 5): combs of gcomb_entries(SBV_HOT_BITS) apt entries; ptmp = the builder's chain scratch for SBV_PROMOTE_MAX keys
+    HotPool hp;
+    apt* pbases = nullptr;        // [SBV_PROMOTE_MAX][2 x 17] base points of the promotions under construction.  Here, not in HotPool: only this scheme's builder takes its base points from a kernel of their own
+    uint8_t* wide = nullptr;      // [max_groups] this batch's groups that may take the wide pass.  Here, not in HotPool: per batch, and allocated with the per-tuple arrays whether or not there is a pool (the table-class kernel always writes it)
     size_t cap = 0;
     size_t gacc_cap = 0;        // the scratch capacity gacc was sized for
 };
@@ -96,18 +88,11 @@ struct KeyPool {
     uint8_t* kvalid = nullptr;  // (kc.cap + max_groups)
     KeyCache kc = {};
     u32 max_groups = 0;
-    // hot keys of this scheme (k256_group.h; sbv_secp256k1_hot_keys): 16-bit combs for promoted cache slots and the bookkeeping of
-    // EdGroupBuffers (same meaning, same kernels: group_kernels_common.h); wtab == nullptr = off, which is the default
-    void* wtab = nullptr;       // [wide_cap] combs of 17 x 32 768 64-byte affine entries (k256_keyed.h: SBV_K256_WIDE_*)
-    u32 *kwide = nullptr, *khits = nullptr;     // [kc.cap]
-    u32* hot = nullptr;         // [4] combs handed out | promotions of this batch | lanes of the wide pass | eviction candidates
-    u32* plist = nullptr;       // [2 x SBV_PROMOTE_MAX] (slot, comb)
-    u32* wowner = nullptr;      // [wide_cap]
-    u32* elist = nullptr;       // [SBV_PROMOTE_MAX]
-    u32* ptmp = nullptr;        // the builder's scratch: SBV_K256_WIDE_TMP_WORDS per lane of its grid
-    uint8_t* wide = nullptr;    // [max_groups] this batch's groups whose slot owns a comb
-    u32 wide_cap = 0, promote_min = 4096, hot_tick = 0;
-    u32 build_blocks = 0;       // workgroups of the builder's grid (k256_keyed.h: k256_hot_build_blocks); ptmp holds their lanes' scratch
+    // hot keys of this scheme (k256_group.h; sbv_secp256k1_hot_keys), off by default: combs of 17 x 32 768 64-byte affine entries
+    // (k256_keyed.h: SBV_K256_WIDE_*); ptmp = SBV_K256_WIDE_TMP_WORDS per lane of the builder's grid
+    HotPool hp;
+    uint8_t* wide = nullptr;    // [max_groups] this batch's groups whose slot owns a comb.  Here, not in HotPool: per batch; it exists only with the pool
+    u32 build_blocks = 0;       // workgroups of the builder's grid (k256_keyed.h: k256_hot_build_blocks).  Here, not in HotPool: only this scheme's builder sizes its grid, and so ptmp, by the pool
 };
 // streams and events of the grouped step; owned by the context.  `chunks` (1..SBV_GROUP_MAX_CHUNKS) = how
 // many pieces the 33 key-comb windows are built and consumed in.
@@ -135,6 +120,16 @@ struct GroupSync {
 inline bool p256_group_step_sorted(const GroupSync& y, const Scratch& s, const GroupBuffers& b) { return y.sorted && s.rec && b.gcount && b.grp_of && b.ung_cand; }
 inline bool ed25519_group_step_sorted(const GroupSync& y, const GroupBuffers& b) { return y.sorted && b.gcount && b.grp_of && (size_t)b.max_groups * sizeof(u32) <= 64 * 1024; }
 inline bool k256_group_step_sorted(const GroupSync&, const GroupBuffers&) { return true; }
+// What every scheme's grouped launcher copies from the buffers into the kernels' GroupState; sorted and the threshold are the launcher's to
+// set.  The scatter cursors lie behind the max_groups counts of THESE buffers (a scheme's view may hold fewer groups than were allocated).
+inline GroupState group_state_of(const GroupBuffers& b) {
+    GroupState g{};
+    g.ht = b.ht; g.ht_mask = b.ht_mask; g.rep = b.rep; g.cnt = b.cnt; g.slot_of = b.slot_of; g.group_rep = b.group_rep;
+    g.counters = b.counters; g.grp_idx = b.grp_idx; g.ung_idx = b.ung_idx; g.slots = b.slots;
+    g.max_groups = b.max_groups; g.seed = b.seed;
+    g.gcount = b.gcount; g.gcursor = b.gcount ? b.gcount + b.max_groups : nullptr; g.grp_of = b.grp_of; g.ung_cand = b.ung_cand;
+    return g;
+}
 // Enqueues stage A AND stage B of a grouped batch.  ev_fork must have been recorded on `stream` first.  after_prep
 // (optional) is recorded on `stream` once stage A is ordered before it.  prof (optional): 2 * chunks
 // events, a pair around every Q-phase launch; *prof_pairs = the number of pairs used.

@@ -119,9 +119,8 @@ struct Context {
     u32 group_min_count = 0, group_max = 65536, group_full_min = 256;
     int group_sample_shift = SBV_GROUP_SAMPLE_SHIFT_DEFAULT;     // SBV_GROUP_SAMPLE_SHIFT (0..6): the P-256 default threshold's sampling rate
     // hot keys (p256_group.h): wide combs for cache slots that keep being hit — how many (0 = off; 35.7 MB each) and from how many tuples on
-    u32 hot_keys = 1024, hot_min_hits = 4096;
-    u32 ed_hot_keys = 1024, ed_hot_min_hits = 4096;
-    u32 k256_hot_keys = 0, k256_hot_min_hits = 4096;      // secp256k1: off unless sbv_secp256k1_hot_keys / SBV_K256_HOT_KEYS asks for a pool
+    // per scheme (SBV_SCHEME_*): secp256k1 is off unless sbv_secp256k1_hot_keys / SBV_K256_HOT_KEYS asks for a pool
+    u32 hot_keys[3] = {1024, 0, 1024}, hot_min_hits[3] = {4096, 4096, 4096};
     bool pools_shrunk = false;          // fit_group_pools() gave this device smaller pools than asked for (sbv_p256_pool_stats)
     unsigned group_nomem_events = 0;    // how often a grouped batch fell back to the one-lane kernel for lack of memory (sbv_p256_pool_stats)
     unsigned group_nomem_skip = 0;      // grouped batches to run ungrouped before the pools are tried again (after an SBV_ENOMEM)
@@ -186,11 +185,11 @@ struct Settings {
     bool kc_on[3] = {true, true, true}; u32 kc_caps[3] = {16384, 1024, 1024};
     int profiling = 0;
     int wide_bits = SBV_WIDE_BITS_AUTO; u32 wide_max = 64;          // sbv_p256_wide_keys; env SBV_KEYED_WIDE_BITS (0 = off, 1 = auto), SBV_KEYED_WIDE_MAX
-    u32 hot_keys = 1024, hot_min_hits = 4096;                       // sbv_p256_hot_keys; env SBV_HOT_KEYS (0 = off), SBV_HOT_MIN_HITS
-    u32 ed_hot_keys = 1024, ed_hot_min_hits = 4096;                 // sbv_ed25519_hot_keys; env SBV_ED_HOT_KEYS (0 = off), SBV_ED_HOT_MIN_HITS
-    u32 k256_hot_keys = 0, k256_hot_min_hits = 4096;                // sbv_secp256k1_hot_keys; env SBV_K256_HOT_KEYS (default 0 = off), SBV_K256_HOT_MIN_HITS
+    u32 hot_keys[3] = {1024, 0, 1024}, hot_min_hits[3] = {4096, 4096, 4096};     // sbv_*_hot_keys per scheme (0 keys = off); env: kHotEnv
 } g_settings;
 std::mutex g_set_mu;
+// environment overrides of hot_keys / hot_min_hits, read when a context is initialised: [SBV_SCHEME_*] = {pool size (0..4096), hits (>= 1)}
+constexpr const char* kHotEnv[3][2] = {{"SBV_HOT_KEYS", "SBV_HOT_MIN_HITS"}, {"SBV_K256_HOT_KEYS", "SBV_K256_HOT_MIN_HITS"}, {"SBV_ED_HOT_KEYS", "SBV_ED_HOT_MIN_HITS"}};
 std::unique_ptr<Context> g_ctxs[kMaxDevices];
 Context g_null;                      // stand-in before sbv_init: ready == false
 Context* g_def = nullptr;
@@ -407,52 +406,59 @@ hipError_t key_cache_forget(sbv::KeyCache& kc) {
     return e;
 }
 
-// the P-256 cache was emptied: its slots' wide combs belong to nobody any more
-hipError_t hot_forget(sbv::GroupBuffers& b) {
-    if (!b.kwide) return hipSuccess;
-    hipError_t e = memset_now(b.kwide, 0xFF, (size_t)b.kc.cap * sizeof(u32));
-    if (e == hipSuccess) e = memset_now(b.khits, 0, (size_t)b.kc.cap * sizeof(u32));
-    if (e == hipSuccess) e = memset_now(b.hot, 0, 4 * sizeof(u32));
-    if (e == hipSuccess && b.wowner) e = memset_now(b.wowner, 0xFF, (size_t)b.wide_cap * sizeof(u32));
+// ---- a scheme's hot-key pool (p256_group.h: HotPool) beside its key-table cache `kc` ----
+// the cache was emptied: its slots' wide combs belong to nobody any more
+hipError_t hot_pool_forget(sbv::HotPool& p, const sbv::KeyCache& kc) {
+    if (!p.kwide) return hipSuccess;
+    hipError_t e = memset_now(p.kwide, 0xFF, (size_t)kc.cap * sizeof(u32));
+    if (e == hipSuccess) e = memset_now(p.khits, 0, (size_t)kc.cap * sizeof(u32));
+    if (e == hipSuccess) e = memset_now(p.hot, 0, 4 * sizeof(u32));
+    if (e == hipSuccess && p.wowner) e = memset_now(p.wowner, 0xFF, (size_t)p.wide_cap * sizeof(u32));
     return e;
 }
-
-// the same for the Ed25519 scheme's pool (ed25519_group.h: hot keys)
-hipError_t ed_hot_forget(sbv::EdGroupBuffers& e) {
-    if (!e.kwide) return hipSuccess;
-    hipError_t r = memset_now(e.kwide, 0xFF, (size_t)e.kc.cap * sizeof(u32));
-    if (r == hipSuccess) r = memset_now(e.khits, 0, (size_t)e.kc.cap * sizeof(u32));
-    if (r == hipSuccess) r = memset_now(e.hot, 0, 4 * sizeof(u32));
-    if (r == hipSuccess) r = memset_now(e.wowner, 0xFF, (size_t)e.wide_cap * sizeof(u32));
-    return r;
-}
-void ed_hot_free(sbv::EdGroupBuffers& e) {
-    void* part[] = {e.wtab, e.kwide, e.khits, e.hot, e.plist, e.wowner, e.elist, e.ptmp, e.wide};
+// everything the pool owns; what a scheme keeps beside it (GroupBuffers::pbases, the `wide` bytes, KeyPool::build_blocks) is the caller's
+void hot_pool_free(sbv::HotPool& p) {
+    void* part[] = {p.wtab, p.kwide, p.khits, p.hot, p.plist, p.wowner, p.elist, p.ptmp};
     for (void* q : part) if (q) (void)hipFree(q);
-    e.wtab = nullptr; e.kwide = nullptr; e.khits = nullptr; e.hot = nullptr; e.plist = nullptr; e.wowner = nullptr; e.elist = nullptr;
-    e.ptmp = nullptr; e.wide = nullptr; e.wide_cap = 0;
+    p = sbv::HotPool();
+}
+bool wide_pool_fits(const Context& c, size_t extra_bytes, unsigned percent = 15);
+// An OPTIONAL pool of `want` combs of comb_bytes each for the K slots of `kc`, with scratch_of(combs) bytes for the scheme's builder:
+// as large as asked for if that leaves the device its reserve (wide_pool_fits: `percent` of it at most; fit_scratch: the scratch counts
+// too), halved until it does, absent otherwise.  At most 4096 combs: k_promote_evict's bitmap of the combs handed out in a batch covers
+// that many.  A failed allocation or fill leaves the feature off (false, nothing allocated) and never fails the batch: verdicts do not
+// depend on the pool.
+bool hot_pool_alloc(const Context& c, sbv::HotPool& p, const sbv::KeyCache& kc, size_t want, size_t comb_bytes, size_t (*scratch_of)(size_t combs),
+                    unsigned percent, bool fit_scratch) {
+    const size_t K = kc.cap;
+    if (!want || !K) return false;
+    if (want > 4096) want = 4096;
+    while (want && !wide_pool_fits(c, want * comb_bytes + (fit_scratch ? scratch_of(want) : 0), percent)) want /= 2;
+    if (!want) return false;
+    p.wide_cap = (u32)want;
+    const bool got = hipMalloc(&p.wtab, want * comb_bytes) == hipSuccess && hipMalloc(&p.kwide, K * sizeof(u32)) == hipSuccess &&
+                     hipMalloc(&p.khits, K * sizeof(u32)) == hipSuccess && hipMalloc(&p.hot, 4 * sizeof(u32)) == hipSuccess &&
+                     hipMalloc(&p.plist, 2 * SBV_PROMOTE_MAX * sizeof(u32)) == hipSuccess && hipMalloc(&p.ptmp, scratch_of(want)) == hipSuccess &&
+                     hipMalloc(&p.wowner, want * sizeof(u32)) == hipSuccess && hipMalloc(&p.elist, SBV_PROMOTE_MAX * sizeof(u32)) == hipSuccess;
+    if (got && hot_pool_forget(p, kc) == hipSuccess) return true;
+    (void)hipGetLastError();
+    hot_pool_free(p);
+    return false;
 }
 
-// the same for the secp256k1 scheme's pool (k256_group.h: hot keys)
-hipError_t k256_hot_forget(sbv::KeyPool& kp) {
-    if (!kp.kwide) return hipSuccess;
-    hipError_t r = memset_now(kp.kwide, 0xFF, (size_t)kp.kc.cap * sizeof(u32));
-    if (r == hipSuccess) r = memset_now(kp.khits, 0, (size_t)kp.kc.cap * sizeof(u32));
-    if (r == hipSuccess) r = memset_now(kp.hot, 0, 4 * sizeof(u32));
-    if (r == hipSuccess) r = memset_now(kp.wowner, 0xFF, (size_t)kp.wide_cap * sizeof(u32));
-    return r;
-}
-void k256_hot_free(sbv::KeyPool& kp) {
-    void* part[] = {kp.wtab, kp.kwide, kp.khits, kp.hot, kp.plist, kp.wowner, kp.elist, kp.ptmp, kp.wide};
+// a scheme's comb pool with its key-table cache and hot keys (the P-256 step's go with its other buffers: free_group_buffers)
+void ed_pool_free(sbv::EdGroupBuffers& e) {
+    void* part[] = {e.ktab, e.okb, e.ungxy, e.kvalid, e.wide};
     for (void* q : part) if (q) (void)hipFree(q);
-    kp.wtab = nullptr; kp.kwide = nullptr; kp.khits = nullptr; kp.hot = nullptr; kp.plist = nullptr; kp.wowner = nullptr; kp.elist = nullptr;
-    kp.ptmp = nullptr; kp.wide = nullptr; kp.wide_cap = 0; kp.build_blocks = 0;
+    key_cache_free(e.kc);
+    hot_pool_free(e.hp);
+    e = sbv::EdGroupBuffers();
 }
 void k256_pool_free(sbv::KeyPool& kp) {
-    if (kp.ktab) (void)hipFree(kp.ktab);
-    if (kp.kvalid) (void)hipFree(kp.kvalid);
+    void* part[] = {kp.ktab, kp.kvalid, kp.wide};
+    for (void* q : part) if (q) (void)hipFree(q);
     key_cache_free(kp.kc);
-    k256_hot_free(kp);
+    hot_pool_free(kp.hp);
     kp = sbv::KeyPool();
 }
 
@@ -463,33 +469,22 @@ void free_group_buffers(Context& c, bool keep_pools = false) {
     void* ptrs[] = {b.ht, b.rep, b.cnt, b.slot_of, b.group_rep, b.counters, b.grp_idx, b.ung_idx, b.slots, b.jbases, b.bases, b.jstate, b.tmp, b.acc, b.gacc,
                     b.gcount, b.grp_of, b.ung_cand, b.rec, b.tslot, b.cold, b.full, b.needfill, b.wide};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    sbv::apt* const ktab = b.ktab;
-    sbv::apt* const ntab = b.ntab;
-    uint8_t* const kvalid = b.kvalid;
-    uint8_t* const kfull = b.kfull;
-    const sbv::KeyCache kc = b.kc;
-    const sbv::GroupBuffers old = b;                 // the hot-key pool travels with the other pools
-    b = sbv::GroupBuffers();
-    if (keep_pools) {
-        b.ktab = ktab; b.ntab = ntab; b.kvalid = kvalid; b.kfull = kfull; b.kc = kc;
-        b.wtab = old.wtab; b.kwide = old.kwide; b.khits = old.khits; b.hot = old.hot; b.plist = old.plist; b.pbases = old.pbases; b.ptmp = old.ptmp;
-        b.wowner = old.wowner; b.elist = old.elist; b.hot_tick = old.hot_tick;
-        b.wide_cap = old.wide_cap; b.promote_min = old.promote_min;
+    if (keep_pools) {           // the hot-key pool travels with the other pools
+        sbv::GroupBuffers kept;
+        kept.ktab = b.ktab; kept.ntab = b.ntab; kept.kvalid = b.kvalid; kept.kfull = b.kfull; kept.kc = b.kc;
+        kept.hp = b.hp; kept.pbases = b.pbases;
+        b = kept;
         return;
     }
-    void* pool[] = {ktab, ntab, kvalid, kfull, kc.ht, kc.keys, kc.count, old.wtab, old.kwide, old.khits, old.hot, old.plist, old.pbases, old.ptmp, old.wowner, old.elist};
+    void* pool[] = {b.ktab, b.ntab, b.kvalid, b.kfull, b.pbases};
     for (void* p : pool) if (p) (void)hipFree(p);
-    if (c.edgrp.ktab) (void)hipFree(c.edgrp.ktab);
-    if (c.edgrp.okb) (void)hipFree(c.edgrp.okb);
-    if (c.edgrp.ungxy) (void)hipFree(c.edgrp.ungxy);
-    if (c.edgrp.kvalid) (void)hipFree(c.edgrp.kvalid);
-    key_cache_free(c.edgrp.kc);
-    ed_hot_free(c.edgrp);
-    c.edgrp = sbv::EdGroupBuffers();
+    key_cache_free(b.kc);
+    hot_pool_free(b.hp);
+    b = sbv::GroupBuffers();
+    ed_pool_free(c.edgrp);
     k256_pool_free(c.k256pool);
 }
 
-bool wide_pool_fits(const Context& c, size_t extra_bytes, unsigned percent = 15);
 // HBM that everything sized by (cache capacity K, groups per batch G) takes: the comb pool (270 KiB per slot), the compact rows
 // (33 KiB), the class bytes, and per group the builder's base records and chain state.
 size_t group_pool_bytes(size_t K, size_t G) {
@@ -525,7 +520,7 @@ int ensure_group_buffers(Context& c, size_t n) {
         b.min_count = c.group_min_count ? c.group_min_count : SBV_GROUP_MIN_COUNT_DEFAULT;
         b.sample_shift = c.group_min_count ? -1 : c.group_sample_shift;
         b.full_min = c.group_full_min;
-        b.promote_min = c.hot_min_hits;
+        b.hp.promote_min = c.hot_min_hits[SBV_SCHEME_P256];
         b.kc.enabled = c.kc_on[0] ? 1u : 0u;
         return SBV_OK;
     }
@@ -573,38 +568,18 @@ int ensure_group_buffers(Context& c, size_t n) {
         HIP_TRY(SBV_EDEVICE, memset_now(b.kfull, 0, K + G));
         const int krc = key_cache_alloc(b.kc, K, c.kc_on[0]);
         if (krc != SBV_OK) return krc;
-        // hot keys: the pool of wide combs for promoted cache slots (p256_group.h), as large as asked for if that leaves the reserve free
-        // (wide_pool_fits: 1024 keys x 35.7 MB = 36.5 GB of the 288), smaller or absent otherwise — verdicts never depend on it
-        b.wide_cap = 0;
-        if (c.hot_keys && K) {
-            const size_t per = sbv::gcomb_entries(SBV_HOT_BITS) * sizeof(sbv::apt);
-            size_t want = c.hot_keys > 4096 ? 4096 : c.hot_keys;        // k_promote_evict's bitmap of the combs handed out in a batch covers 4096
-            while (want && !wide_pool_fits(c, want * per)) want /= 2;
-            if (want) {
-                // an OPTIONAL pool: a failed allocation leaves the hot keys off (same verdicts), it never fails the batch
-                const size_t W = (257 + SBV_HOT_BITS - 1) / SBV_HOT_BITS;
-                const bool got = hipMalloc(&b.wtab, want * per) == hipSuccess && hipMalloc(&b.kwide, K * sizeof(u32)) == hipSuccess &&
-                                 hipMalloc(&b.khits, K * sizeof(u32)) == hipSuccess && hipMalloc(&b.hot, 4 * sizeof(u32)) == hipSuccess &&
-                                 hipMalloc(&b.plist, 2 * SBV_PROMOTE_MAX * sizeof(u32)) == hipSuccess &&
-                                 hipMalloc(&b.pbases, SBV_PROMOTE_MAX * 2 * W * sizeof(sbv::apt)) == hipSuccess &&
-                                 hipMalloc(&b.ptmp, sbv::widetab_tmp_words(SBV_PROMOTE_MAX, SBV_HOT_BITS) * sizeof(u32)) == hipSuccess &&
-                                 hipMalloc(&b.wowner, want * sizeof(u32)) == hipSuccess && hipMalloc(&b.elist, SBV_PROMOTE_MAX * sizeof(u32)) == hipSuccess &&
-                                 memset_now(b.wowner, 0xFF, want * sizeof(u32)) == hipSuccess &&
-                                 memset_now(b.kwide, 0xFF, K * sizeof(u32)) == hipSuccess && memset_now(b.khits, 0, K * sizeof(u32)) == hipSuccess &&
-                                 memset_now(b.hot, 0, 4 * sizeof(u32)) == hipSuccess;
-                if (got) {
-                    b.wide_cap = (u32)want;
-                } else {
-                    (void)hipGetLastError();
-                    void* part[] = {b.wtab, b.kwide, b.khits, b.hot, b.plist, b.pbases, b.ptmp, b.wowner, b.elist};
-                    for (void* q : part) if (q) (void)hipFree(q);
-                    b.wtab = nullptr; b.kwide = nullptr; b.khits = nullptr; b.hot = nullptr; b.plist = nullptr; b.pbases = nullptr; b.ptmp = nullptr;
-                    b.wowner = nullptr; b.elist = nullptr;
-                }
-            }
+        // hot keys: the optional pool (hot_pool_alloc) of wide combs for promoted cache slots (p256_group.h; 1024 keys x 35.7 MB = 36.5 GB of the
+        // 288; the fit has never counted the builder's few MB of scratch), and the builder's base points beside it
+        const size_t W = (257 + SBV_HOT_BITS - 1) / SBV_HOT_BITS;
+        if (hot_pool_alloc(c, b.hp, b.kc, c.hot_keys[SBV_SCHEME_P256], sbv::gcomb_entries(SBV_HOT_BITS) * sizeof(sbv::apt),
+                           [](size_t) { return sbv::widetab_tmp_words(SBV_PROMOTE_MAX, SBV_HOT_BITS) * sizeof(u32); }, 15, false) &&
+            hipMalloc(&b.pbases, SBV_PROMOTE_MAX * 2 * W * sizeof(sbv::apt)) != hipSuccess) {
+            (void)hipGetLastError();
+            b.pbases = nullptr;
+            hot_pool_free(b.hp);
         }
     }
-    b.promote_min = c.hot_min_hits;
+    b.hp.promote_min = c.hot_min_hits[SBV_SCHEME_P256];
     HIP_TRY(SBV_ENOMEM, hipMalloc(&b.wide, G));
     b.kc.enabled = c.kc_on[0] ? 1u : 0u;
     {   // scratch of the table kernels: P-256 indexes it by resident lane (two table streams x SBV_TABLE_GRID_BLOCKS x 64 lanes x 675 words,
@@ -658,7 +633,7 @@ int ensure_ed_group_buffers(Context& c, size_t n) {
     // (found on the GPU in round 4: the warm batch of the cache test was 384 tuples longer than the cold one and missed every key).
     const u32 vg = variant_groups(c);
     const bool pool_ok = e.ktab && e.max_groups == vg && e.kc.ht && e.kc.cap == K;
-    e.promote_min = c.ed_hot_min_hits;
+    e.hp.promote_min = c.hot_min_hits[SBV_SCHEME_ED25519];
     if (pool_ok && e.okb && e.cap >= c.grp.cap) {
         e.kc.enabled = c.kc_on[2] ? 1u : 0u;
         return SBV_OK;
@@ -668,40 +643,27 @@ int ensure_ed_group_buffers(Context& c, size_t n) {
     if (e.ungxy) (void)hipFree(e.ungxy);
     e.okb = nullptr; e.ungxy = nullptr; e.cap = 0;
     if (!pool_ok) {
-        if (e.ktab) (void)hipFree(e.ktab);
-        if (e.kvalid) (void)hipFree(e.kvalid);
-        key_cache_free(e.kc);
-        ed_hot_free(e);
-        e = sbv::EdGroupBuffers();
+        ed_pool_free(e);
         // comb pool of this scheme: slots [0, K) = its persistent key-table cache, [K, K + max_groups) per batch
         HIP_TRY(SBV_ENOMEM, hipMalloc(&e.ktab, (K + vg) * (size_t)SBV_ED_KEYTAB_ENTRIES_PER_KEY * sizeof(sbv::aniels)));
         HIP_TRY(SBV_ENOMEM, hipMalloc(&e.kvalid, K + vg));
         rc = key_cache_alloc(e.kc, K, c.kc_on[2]);
         if (rc != SBV_OK) return rc;
         e.max_groups = vg;
-        // hot keys of this scheme: an OPTIONAL pool of 64 MiB combs, as large as asked for if the device has the room (wide_pool_fits),
-        // smaller or absent otherwise — a failed allocation leaves the feature off, it never fails the batch; verdicts never depend on it
-        if (c.ed_hot_keys && K) {
-            size_t want = c.ed_hot_keys > 4096 ? 4096 : c.ed_hot_keys;
-            const size_t scratch = (size_t)SBV_ED_HOT_BUILD_BLOCKS * 64 * SBV_ED_HOT_TMP_WORDS * sizeof(u32);
-            while (want && !wide_pool_fits(c, want * SBV_ED_HOT_COMB_BYTES + scratch, 25)) want /= 2;       // an opt-in pool: 1024 combs are 64 GiB of the 288
-            if (want) {
-                const bool got = hipMalloc(&e.wtab, want * SBV_ED_HOT_COMB_BYTES) == hipSuccess && hipMalloc(&e.kwide, K * sizeof(u32)) == hipSuccess &&
-                                 hipMalloc(&e.khits, K * sizeof(u32)) == hipSuccess && hipMalloc(&e.hot, 4 * sizeof(u32)) == hipSuccess &&
-                                 hipMalloc(&e.plist, 2 * SBV_PROMOTE_MAX * sizeof(u32)) == hipSuccess && hipMalloc(&e.ptmp, scratch) == hipSuccess &&
-                                 hipMalloc(&e.wowner, want * sizeof(u32)) == hipSuccess && hipMalloc(&e.elist, SBV_PROMOTE_MAX * sizeof(u32)) == hipSuccess &&
-                                 hipMalloc(&e.wide, vg) == hipSuccess;
-                if (got) e.wide_cap = (u32)want;
-                if (!got || ed_hot_forget(e) != hipSuccess || memset_now(e.wide, 0, vg) != hipSuccess) {
-                    (void)hipGetLastError();
-                    ed_hot_free(e);
-                }
-            }
+        // hot keys of this scheme: the optional pool (hot_pool_alloc) of 64 MiB combs — 1024 of them are 64 GiB of the 288, hence a quarter
+        // of the device at most — and the class bytes that exist only with it
+        if (hot_pool_alloc(c, e.hp, e.kc, c.hot_keys[SBV_SCHEME_ED25519], SBV_ED_HOT_COMB_BYTES,
+                           [](size_t) { return (size_t)SBV_ED_HOT_BUILD_BLOCKS * 64 * SBV_ED_HOT_TMP_WORDS * sizeof(u32); }, 25, true) &&
+            (hipMalloc(&e.wide, vg) != hipSuccess || memset_now(e.wide, 0, vg) != hipSuccess)) {
+            (void)hipGetLastError();
+            if (e.wide) (void)hipFree(e.wide);
+            e.wide = nullptr;
+            hot_pool_free(e.hp);
         }
     }
     HIP_TRY(SBV_ENOMEM, hipMalloc(&e.okb, c.grp.cap));
     HIP_TRY(SBV_ENOMEM, hipMalloc(&e.ungxy, c.grp.cap * (size_t)SBV_ED_UNGXY_WORDS * sizeof(u32)));
-    e.promote_min = c.ed_hot_min_hits;
+    e.hp.promote_min = c.hot_min_hits[SBV_SCHEME_ED25519];
     e.cap = c.grp.cap;
     e.kc.enabled = c.kc_on[2] ? 1u : 0u;
     return SBV_OK;
@@ -714,7 +676,7 @@ int ensure_k256_group_buffers(Context& c, size_t n) {
     sbv::KeyPool& kp = c.k256pool;
     const size_t K = c.kc_caps[1];
     const u32 vg = variant_groups(c);
-    kp.promote_min = c.k256_hot_min_hits;
+    kp.hp.promote_min = c.hot_min_hits[SBV_SCHEME_SECP256K1];
     if (kp.ktab && kp.max_groups == vg && kp.kc.cap == K) {
         kp.kc.enabled = c.kc_on[1] ? 1u : 0u;
         return SBV_OK;
@@ -726,29 +688,20 @@ int ensure_k256_group_buffers(Context& c, size_t n) {
     rc = key_cache_alloc(kp.kc, K, c.kc_on[1]);
     if (rc != SBV_OK) return rc;
     kp.max_groups = vg;
-    kp.promote_min = c.k256_hot_min_hits;
-    // hot keys of this scheme: an OPTIONAL pool of 35.7 MB combs, off unless asked for (sbv_secp256k1_hot_keys), as large as asked for if the
-    // device has the room (wide_pool_fits), smaller or absent otherwise — a failed allocation leaves the feature off, it never fails the
-    // batch; verdicts never depend on it.  The pool is zeroed once: a comb's top window holds one entry, the builder writes no other of it.
-    if (c.k256_hot_keys && K) {
-        size_t want = c.k256_hot_keys > 4096 ? 4096 : c.k256_hot_keys;
-        auto scratch_of = [](size_t w) { return (size_t)sbv::k256_hot_build_blocks((u32)w) * 64 * SBV_K256_WIDE_TMP_WORDS * sizeof(u32); };
-        while (want && !wide_pool_fits(c, want * SBV_K256_WIDE_COMB_BYTES + scratch_of(want))) want /= 2;
-        if (want) {
-            const size_t scratch = scratch_of(want);
-            const bool got = hipMalloc(&kp.wtab, want * SBV_K256_WIDE_COMB_BYTES) == hipSuccess && hipMalloc(&kp.kwide, K * sizeof(u32)) == hipSuccess &&
-                             hipMalloc(&kp.khits, K * sizeof(u32)) == hipSuccess && hipMalloc(&kp.hot, 4 * sizeof(u32)) == hipSuccess &&
-                             hipMalloc(&kp.plist, 2 * SBV_PROMOTE_MAX * sizeof(u32)) == hipSuccess && hipMalloc(&kp.ptmp, scratch) == hipSuccess &&
-                             hipMalloc(&kp.wowner, want * sizeof(u32)) == hipSuccess && hipMalloc(&kp.elist, SBV_PROMOTE_MAX * sizeof(u32)) == hipSuccess &&
-                             hipMalloc(&kp.wide, vg) == hipSuccess;
-            if (got) { kp.wide_cap = (u32)want; kp.build_blocks = sbv::k256_hot_build_blocks((u32)want); }
-            if (!got || k256_hot_forget(kp) != hipSuccess || memset_now(kp.wide, 0, vg) != hipSuccess ||
-                memset_now(kp.wtab, 0, want * SBV_K256_WIDE_COMB_BYTES) != hipSuccess) {
-                (void)hipGetLastError();
-                k256_hot_free(kp);
-            }
+    // hot keys of this scheme: the optional pool (hot_pool_alloc) of 35.7 MB combs, off unless asked for (sbv_secp256k1_hot_keys); the builder's
+    // grid and scratch follow the pool's final size.  The pool is zeroed once: a comb's top window holds one entry, the builder writes no other of it.
+    if (hot_pool_alloc(c, kp.hp, kp.kc, c.hot_keys[SBV_SCHEME_SECP256K1], SBV_K256_WIDE_COMB_BYTES,
+                       [](size_t combs) { return (size_t)sbv::k256_hot_build_blocks((u32)combs) * 64 * SBV_K256_WIDE_TMP_WORDS * sizeof(u32); }, 15, true)) {
+        const size_t pool_bytes = (size_t)kp.hp.wide_cap * SBV_K256_WIDE_COMB_BYTES;
+        kp.build_blocks = sbv::k256_hot_build_blocks(kp.hp.wide_cap);
+        if (hipMalloc(&kp.wide, vg) != hipSuccess || memset_now(kp.wide, 0, vg) != hipSuccess || memset_now(kp.hp.wtab, 0, pool_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            if (kp.wide) (void)hipFree(kp.wide);
+            kp.wide = nullptr; kp.build_blocks = 0;
+            hot_pool_free(kp.hp);
         }
     }
+    kp.hp.promote_min = c.hot_min_hits[SBV_SCHEME_SECP256K1];
     return SBV_OK;
 }
 
@@ -781,14 +734,14 @@ int enqueue_ed25519(Context& c, const uint8_t* d_tuples, size_t n, uint8_t* d_bi
     if (grouped && !group_buffers_or_fallback(c, n, [&] { const int r = ensure_ed_group_buffers(c, n); return r != SBV_OK ? r : ensure_ed_bcomb(c); }, grouped)) return g_last_rc;
     if (grouped) {
         HIP_TRY(SBV_EDEVICE, hipEventRecord(c.gsync.ev_fork, stream));
-        if (c.edgrp.wtab && c.edgrp.kc.enabled) ++c.edgrp.hot_tick;     // the clock of the hot keys' decay
+        if (c.edgrp.hp.wtab && c.edgrp.kc.enabled) ++c.edgrp.hp.hot_tick;     // the clock of the hot keys' decay
         const sbv::GroupBuffers bv = variant_view(c, n);
         note_grouped_launch(c, SBV_SCHEME_ED25519, n, bv, sbv::ed25519_group_step_sorted(c.gsync, bv));
         const hipError_t ge = sbv::launch_ed25519_verify_grouped(d_tuples, n, bv, c.edgrp, c.d_qtab, c.d_btab, sbv::edcomb_make(c.d_ed_bcomb, c.ed_bbits, c.ed_bpitch), d_bitmap, stream, c.gsync, dom, dom_pairs);
         if (ge != hipSuccess) {          // a slot is published before its tables are built (see enqueue()): forget the cache
             (void)hipDeviceSynchronize();
             (void)key_cache_forget(c.edgrp.kc);
-            (void)ed_hot_forget(c.edgrp);
+            (void)hot_pool_forget(c.edgrp.hp, c.edgrp.kc);
             return fail(SBV_EDEVICE, "launch_ed25519_verify_grouped", ge);
         }
         return SBV_OK;
@@ -825,7 +778,7 @@ int enqueue(Context& c, const uint8_t* d_tuples, size_t n, uint8_t* d_bitmap, hi
         sbv::GroupSync y = c.gsync;
         if (y.tstreams > 1 && stream != c.stream) y.side_t = c.stream;
         else y.tstreams = 1;
-        if (c.grp.wtab && c.grp.kc.enabled) ++c.grp.hot_tick;           // the clock of the hot keys' decay (p256_group.h)
+        if (c.grp.hp.wtab && c.grp.kc.enabled) ++c.grp.hp.hot_tick;           // the clock of the hot keys' decay (p256_group.h)
         note_grouped_launch(c, SBV_SCHEME_P256, n, c.grp, sbv::p256_group_step_sorted(y, sg, c.grp));
         const hipError_t ge = sbv::launch_p256_verify_grouped(d_tuples, sg, n, c.grp, c.d_qtab, c.d_gtab, sbv::gcomb_make(c.d_g16r, c.g_bits), d_bitmap, stream, y,
                                                               after_prep, dom, dom_pairs);
@@ -834,7 +787,7 @@ int enqueue(Context& c, const uint8_t* d_tuples, size_t n, uint8_t* d_bitmap, hi
             // whose combs never were.  Forget the whole cache (best effort, after draining what did get enqueued).
             (void)hipDeviceSynchronize();
             (void)key_cache_forget(c.grp.kc);
-            (void)hot_forget(c.grp);
+            (void)hot_pool_forget(c.grp.hp, c.grp.kc);
             return fail(SBV_EDEVICE, "launch_p256_verify_grouped", ge);
         }
         return SBV_OK;
@@ -1105,16 +1058,12 @@ int init_context(Context& c, int device) {
         for (int k = 0; k < 3; ++k) { c.kc_on[k] = g_settings.kc_on[k]; c.kc_caps[k] = g_settings.kc_caps[k]; }
         c.profiling = g_settings.profiling;
         c.kwide_auto = g_settings.wide_bits == SBV_WIDE_BITS_AUTO; c.kwide_bits = c.kwide_auto ? 20 : g_settings.wide_bits; c.kwide_max = g_settings.wide_max;
-        c.hot_keys = g_settings.hot_keys; c.hot_min_hits = g_settings.hot_min_hits;
-        c.ed_hot_keys = g_settings.ed_hot_keys; c.ed_hot_min_hits = g_settings.ed_hot_min_hits;
-        c.k256_hot_keys = g_settings.k256_hot_keys; c.k256_hot_min_hits = g_settings.k256_hot_min_hits;
+        for (int k = 0; k < 3; ++k) { c.hot_keys[k] = g_settings.hot_keys[k]; c.hot_min_hits[k] = g_settings.hot_min_hits[k]; }
     }
-    if (const char* e = getenv("SBV_HOT_KEYS")) { const long v = atol(e); if (v >= 0 && v <= 4096) c.hot_keys = (u32)v; }
-    if (const char* e = getenv("SBV_HOT_MIN_HITS")) { const long v = atol(e); if (v >= 1) c.hot_min_hits = (u32)v; }
-    if (const char* e = getenv("SBV_ED_HOT_KEYS")) { const long v = atol(e); if (v >= 0 && v <= 4096) c.ed_hot_keys = (u32)v; }
-    if (const char* e = getenv("SBV_ED_HOT_MIN_HITS")) { const long v = atol(e); if (v >= 1) c.ed_hot_min_hits = (u32)v; }
-    if (const char* e = getenv("SBV_K256_HOT_KEYS")) { const long v = atol(e); if (v >= 0 && v <= 4096) c.k256_hot_keys = (u32)v; }
-    if (const char* e = getenv("SBV_K256_HOT_MIN_HITS")) { const long v = atol(e); if (v >= 1) c.k256_hot_min_hits = (u32)v; }
+    for (int k = 0; k < 3; ++k) {
+        if (const char* e = getenv(kHotEnv[k][0])) { const long v = atol(e); if (v >= 0 && v <= 4096) c.hot_keys[k] = (u32)v; }
+        if (const char* e = getenv(kHotEnv[k][1])) { const long v = atol(e); if (v >= 1) c.hot_min_hits[k] = (u32)v; }
+    }
     if (const char* e = getenv("SBV_KEYED_WIDE_BITS")) { const int v = atoi(e); if (v == 0) c.kwide_max = 0; else if (v == SBV_WIDE_BITS_AUTO) c.kwide_auto = true; else if (v >= 10 && v <= 20) { c.kwide_bits = v; c.kwide_auto = false; } }
     if (const char* e = getenv("SBV_KEYED_WIDE_MAX")) { const long v = atol(e); if (v >= 0 && v <= 4096) c.kwide_max = (u32)v; }
     if (const char* e = getenv("SBV_GROUP_SAMPLE_SHIFT")) { const int v = atoi(e); if (v >= 0 && v <= 6) c.group_sample_shift = v; }
@@ -1974,14 +1923,14 @@ int enqueue_k256(Context& c, const uint8_t* d_tuples, size_t m, uint8_t* d_bitma
         sbv::GroupSync y = c.gsync;                 // second table stream: the context's own, when the caller's runs the step (enqueue() says why)
         if (y.tstreams > 1 && stream != c.stream) y.side_t = c.stream;
         else y.tstreams = 1;
-        if (c.k256pool.wtab && c.k256pool.kc.enabled) ++c.k256pool.hot_tick;     // the clock of the hot keys' decay
+        if (c.k256pool.hp.wtab && c.k256pool.kc.enabled) ++c.k256pool.hp.hot_tick;     // the clock of the hot keys' decay
         const sbv::GroupBuffers bv = variant_view(c, m);
         note_grouped_launch(c, SBV_SCHEME_SECP256K1, m, bv, sbv::k256_group_step_sorted(y, bv));
         const hipError_t ge = sbv::launch_k256_verify_grouped(d_tuples, s, m, bv, c.k256pool, c.d_qtab, c.d_k256_gtab, c.d_k256_gcomb, c.k256_gbits, d_bitmap, stream, y, dom, dom_pairs);
         if (ge != hipSuccess) {
             (void)hipDeviceSynchronize();
             (void)key_cache_forget(c.k256pool.kc);
-            (void)k256_hot_forget(c.k256pool);
+            (void)hot_pool_forget(c.k256pool.hp, c.k256pool.kc);
             return fail(SBV_EDEVICE, "launch_k256_verify_grouped", ge);
         }
         return SBV_OK;
@@ -3328,6 +3277,9 @@ namespace {
 sbv::KeyCache* scheme_cache(Context& c, int scheme) {
     return scheme == SBV_SCHEME_P256 ? &c.grp.kc : scheme == SBV_SCHEME_SECP256K1 ? &c.k256pool.kc : &c.edgrp.kc;
 }
+sbv::HotPool* scheme_hot_pool(Context& c, int scheme) {
+    return scheme == SBV_SCHEME_P256 ? &c.grp.hp : scheme == SBV_SCHEME_SECP256K1 ? &c.k256pool.hp : &c.edgrp.hp;
+}
 }  // namespace
 
 extern "C" int sbv_key_cache(int scheme, int enabled, uint32_t capacity) {
@@ -3351,9 +3303,7 @@ extern "C" int sbv_key_cache(int scheme, int enabled, uint32_t capacity) {
             if (e == hipSuccess) e = hipDeviceSynchronize();
             kc.enabled = c.kc_on[scheme] ? 1u : 0u;
             if (e == hipSuccess && !c.kc_on[scheme]) e = key_cache_forget(kc);   // switching it off forgets everything: the next "on" starts cold
-            if (e == hipSuccess && !c.kc_on[scheme] && scheme == SBV_SCHEME_P256) e = hot_forget(c.grp);
-            if (e == hipSuccess && !c.kc_on[scheme] && scheme == SBV_SCHEME_ED25519) e = ed_hot_forget(c.edgrp);
-            if (e == hipSuccess && !c.kc_on[scheme] && scheme == SBV_SCHEME_SECP256K1) e = k256_hot_forget(c.k256pool);
+            if (e == hipSuccess && !c.kc_on[scheme]) e = hot_pool_forget(*scheme_hot_pool(c, scheme), kc);
             if (e != hipSuccess) rc = fail(SBV_EDEVICE, "sbv_key_cache", e);
         }
     }
@@ -3425,111 +3375,87 @@ extern "C" int sbv_p256_last_group_stats(uint32_t out[4]) {
     return SBV_OK;
 }
 
-extern "C" int sbv_p256_hot_keys(uint32_t max_keys, uint32_t min_hits) {
+namespace {
+// sbv_*_hot_keys: the pool size and the promotion threshold of one scheme, for every context and for those still to come
+int set_hot_keys(int scheme, const char* entry, uint32_t max_keys, uint32_t min_hits) {
     if (max_keys > 4096) return SBV_EINVAL;
     {
         std::lock_guard<std::mutex> lk(g_set_mu);
-        g_settings.hot_keys = max_keys;
-        if (min_hits) g_settings.hot_min_hits = min_hits;
+        g_settings.hot_keys[scheme] = max_keys;
+        if (min_hits) g_settings.hot_min_hits[scheme] = min_hits;
     }
     int rc = SBV_OK;
     for (Context* cp : live_contexts()) {
         std::lock_guard<std::mutex> lk(cp->mu);
         Context& c = *cp;
-        if (min_hits) c.hot_min_hits = min_hits;
-        if (c.hot_keys == max_keys) continue;
-        c.hot_keys = max_keys;
-        if (!c.ready || !c.grp.ktab) continue;
-        // another pool size: the comb pools are rebuilt (with the cache) by the next grouped batch
+        if (min_hits) c.hot_min_hits[scheme] = min_hits;
+        if (c.hot_keys[scheme] == max_keys) continue;          // the size it has: nothing is freed, nobody waits for the device
+        c.hot_keys[scheme] = max_keys;
+        const bool built = scheme == SBV_SCHEME_P256 ? c.grp.ktab != nullptr : scheme == SBV_SCHEME_SECP256K1 ? c.k256pool.ktab != nullptr : c.edgrp.ktab != nullptr;
+        if (!c.ready || !built) continue;
         hipError_t e = hipSetDevice(c.hip_dev);
         if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) { rc = fail(SBV_EDEVICE, "sbv_p256_hot_keys", e); continue; }
-        free_group_buffers(c);
+        if (e != hipSuccess) { rc = fail(SBV_EDEVICE, entry, e); continue; }
+        // Another pool size: the scheme's comb pool goes, with its cache, and the next grouped batch rebuilds both.  The Ed25519 and secp256k1
+        // pools are their own; the P-256 pool is freed with the grouping arrays that all three steps share, and with them go the other two
+        // schemes' pools and caches as well (tests/test_gpu_configs.py: test_hot_key_setters_drop_only_what_they_own holds both).
+        if (scheme == SBV_SCHEME_P256) free_group_buffers(c);
+        else if (scheme == SBV_SCHEME_SECP256K1) k256_pool_free(c.k256pool);
+        else ed_pool_free(c.edgrp);
     }
     return rc;
 }
-
-extern "C" int sbv_p256_hot_key_stats(uint32_t out[4]) {
+// sbv_*_hot_key_stats; without a pool {0, 0, 0, min_hits} and the device is left alone
+int hot_key_stats(int scheme, uint32_t out[4]) {
     SBV_ENTER(c);
     if (!c.ready) return SBV_ENOTINIT;
     if (!out) return SBV_EINVAL;
+    const sbv::HotPool& p = *scheme_hot_pool(c, scheme);
     out[0] = out[2] = 0;
-    out[1] = c.grp.wide_cap;
-    out[3] = c.hot_min_hits;
-    if (!c.grp.hot) return SBV_OK;
+    out[1] = p.wide_cap;
+    out[3] = c.hot_min_hits[scheme];
+    if (!p.hot) return SBV_OK;
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
     uint32_t h[4];
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(h, c.grp.hot, sizeof h, hipMemcpyDeviceToHost));
-    out[0] = h[0] < c.grp.wide_cap ? h[0] : c.grp.wide_cap;
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(h, p.hot, sizeof h, hipMemcpyDeviceToHost));
+    out[0] = h[0] < p.wide_cap ? h[0] : p.wide_cap;
     out[2] = h[2];
     return SBV_OK;
 }
+// The preamble of sbv_*_hot_selfcheck: waits for the device and copies the first key_bytes of the key whose cache slot owns comb `index` of
+// the scheme's pool.  SBV_OK, or what the entry returns (g_err set).
+int hot_comb_key(Context& c, int scheme, const char* entry, uint32_t index, void* key, size_t key_bytes) {
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    const sbv::HotPool& p = *scheme_hot_pool(c, scheme);
+    const sbv::KeyCache& kc = *scheme_cache(c, scheme);
+    if (!p.wtab || !p.kwide || index >= p.wide_cap) { g_err = std::string(entry) + ": no such comb in the hot-key pool"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+    std::vector<u32> kw(kc.cap);
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(kw.data(), p.kwide, kw.size() * sizeof(u32), hipMemcpyDeviceToHost));
+    size_t slot = kw.size();
+    for (size_t i = 0; i < kw.size(); ++i) if (kw[i] == index) slot = i;
+    if (slot == kw.size()) { g_err = std::string(entry) + ": no promoted key has this index"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(key, kc.keys + slot * 16, key_bytes, hipMemcpyDeviceToHost));
+    return SBV_OK;
+}
+}  // namespace
 
+extern "C" int sbv_p256_hot_keys(uint32_t max_keys, uint32_t min_hits) { return set_hot_keys(SBV_SCHEME_P256, "sbv_p256_hot_keys", max_keys, min_hits); }
+extern "C" int sbv_p256_hot_key_stats(uint32_t out[4]) { return hot_key_stats(SBV_SCHEME_P256, out); }
 // Hot keys of the Ed25519 scheme (ed25519_group.h): the pool of 16-bit combs of -A
-extern "C" int sbv_ed25519_hot_keys(uint32_t max_keys, uint32_t min_hits) {
-    if (max_keys > 4096) return SBV_EINVAL;
-    {
-        std::lock_guard<std::mutex> lk(g_set_mu);
-        g_settings.ed_hot_keys = max_keys;
-        if (min_hits) g_settings.ed_hot_min_hits = min_hits;
-    }
-    int rc = SBV_OK;
-    for (Context* cp : live_contexts()) {
-        std::lock_guard<std::mutex> lk(cp->mu);
-        Context& c = *cp;
-        if (min_hits) c.ed_hot_min_hits = min_hits;
-        if (c.ed_hot_keys == max_keys) continue;
-        c.ed_hot_keys = max_keys;
-        if (!c.ready || !c.edgrp.ktab) continue;
-        // another pool size: this scheme's comb pool (with its cache) is rebuilt by the next grouped batch
-        hipError_t e = hipSetDevice(c.hip_dev);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) { rc = fail(SBV_EDEVICE, "sbv_ed25519_hot_keys", e); continue; }
-        sbv::EdGroupBuffers& eb = c.edgrp;
-        if (eb.ktab) (void)hipFree(eb.ktab);
-        if (eb.okb) (void)hipFree(eb.okb);
-        if (eb.ungxy) (void)hipFree(eb.ungxy);
-        if (eb.kvalid) (void)hipFree(eb.kvalid);
-        key_cache_free(eb.kc);
-        ed_hot_free(eb);
-        eb = sbv::EdGroupBuffers();
-    }
-    return rc;
-}
-
-extern "C" int sbv_ed25519_hot_key_stats(uint32_t out[4]) {
-    SBV_ENTER(c);
-    if (!c.ready) return SBV_ENOTINIT;
-    if (!out) return SBV_EINVAL;
-    out[0] = out[2] = 0;
-    out[1] = c.edgrp.wide_cap;
-    out[3] = c.ed_hot_min_hits;
-    if (!c.edgrp.hot) return SBV_OK;
-    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    uint32_t h[4];
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(h, c.edgrp.hot, sizeof h, hipMemcpyDeviceToHost));
-    out[0] = h[0] < c.edgrp.wide_cap ? h[0] : c.edgrp.wide_cap;
-    out[2] = h[2];
-    return SBV_OK;
-}
+extern "C" int sbv_ed25519_hot_keys(uint32_t max_keys, uint32_t min_hits) { return set_hot_keys(SBV_SCHEME_ED25519, "sbv_ed25519_hot_keys", max_keys, min_hits); }
+extern "C" int sbv_ed25519_hot_key_stats(uint32_t out[4]) { return hot_key_stats(SBV_SCHEME_ED25519, out); }
+// Hot keys of the secp256k1 scheme (k256_group.h): the pool of 16-bit combs of Q; off by default
+extern "C" int sbv_secp256k1_hot_keys(uint32_t max_keys, uint32_t min_hits) { return set_hot_keys(SBV_SCHEME_SECP256K1, "sbv_secp256k1_hot_keys", max_keys, min_hits); }
+extern "C" int sbv_secp256k1_hot_key_stats(uint32_t out[4]) { return hot_key_stats(SBV_SCHEME_SECP256K1, out); }
 
 // 1 = promoted comb `index` equals the host builder's comb of -A for its key, entry by entry (canonical affine-Niels entries)
 extern "C" int sbv_ed25519_hot_selfcheck(uint32_t index) {
     SBV_ENTER(c);
-    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
-    sbv::EdGroupBuffers& b = c.edgrp;
-    if (!b.wtab || !b.kwide || index >= b.wide_cap) { g_err = "no such comb in the Ed25519 hot-key pool"; return SBV_EINVAL; }
-    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    std::vector<u32> kw(b.kc.cap);
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(kw.data(), b.kwide, kw.size() * sizeof(u32), hipMemcpyDeviceToHost));
-    size_t slot = kw.size();
-    for (size_t i = 0; i < kw.size(); ++i) if (kw[i] == index) slot = i;
-    if (slot == kw.size()) { g_err = "sbv_ed25519_hot_selfcheck: no promoted key has this index"; return SBV_EINVAL; }
     u32 key[8];
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(key, b.kc.keys + slot * 16, 32, hipMemcpyDeviceToHost));
+    if (const int rc = hot_comb_key(c, SBV_SCHEME_ED25519, "sbv_ed25519_hot_selfcheck", index, key, sizeof key)) return rc;
     sbv::ept A;
     if (!sbv::ed_decompress(A, key)) return 0;                          // only valid keys are promoted
     sbv::fe25_neg(A.X, A.X);
@@ -3542,72 +3468,20 @@ extern "C" int sbv_ed25519_hot_selfcheck(uint32_t index) {
         for (auto& t : th) t.join();
     }
     std::vector<uint8_t> got(SBV_ED_HOT_COMB_BYTES);
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), b.wtab + (size_t)index * SBV_ED_HOT_COMB_BYTES, got.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), static_cast<const uint8_t*>(c.edgrp.hp.wtab) + (size_t)index * SBV_ED_HOT_COMB_BYTES, got.size(), hipMemcpyDeviceToHost));
     for (size_t e = 0; e < want.size(); ++e)
         if (memcmp(got.data() + e * SBV_ED_HOT_PITCH, &want[e], sizeof(sbv::aniels)) != 0) return 0;
     return 1;
 }
 
-// Hot keys of the secp256k1 scheme (k256_group.h): the pool of 16-bit combs of Q; off by default
-extern "C" int sbv_secp256k1_hot_keys(uint32_t max_keys, uint32_t min_hits) {
-    if (max_keys > 4096) return SBV_EINVAL;
-    {
-        std::lock_guard<std::mutex> lk(g_set_mu);
-        g_settings.k256_hot_keys = max_keys;
-        if (min_hits) g_settings.k256_hot_min_hits = min_hits;
-    }
-    int rc = SBV_OK;
-    for (Context* cp : live_contexts()) {
-        std::lock_guard<std::mutex> lk(cp->mu);
-        Context& c = *cp;
-        if (min_hits) c.k256_hot_min_hits = min_hits;
-        if (c.k256_hot_keys == max_keys) continue;
-        c.k256_hot_keys = max_keys;
-        if (!c.ready || !c.k256pool.ktab) continue;
-        // another pool size: this scheme's comb pool (with its cache) is rebuilt by the next grouped batch
-        hipError_t e = hipSetDevice(c.hip_dev);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) { rc = fail(SBV_EDEVICE, "sbv_secp256k1_hot_keys", e); continue; }
-        k256_pool_free(c.k256pool);
-    }
-    return rc;
-}
-
-extern "C" int sbv_secp256k1_hot_key_stats(uint32_t out[4]) {
-    SBV_ENTER(c);
-    if (!c.ready) return SBV_ENOTINIT;
-    if (!out) return SBV_EINVAL;
-    out[0] = out[2] = 0;
-    out[1] = c.k256pool.wide_cap;
-    out[3] = c.k256_hot_min_hits;
-    if (!c.k256pool.hot) return SBV_OK;
-    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    uint32_t h[4];
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(h, c.k256pool.hot, sizeof h, hipMemcpyDeviceToHost));
-    out[0] = h[0] < c.k256pool.wide_cap ? h[0] : c.k256pool.wide_cap;
-    out[2] = h[2];
-    return SBV_OK;
-}
-
 // 1 = promoted comb `index` equals the host builder's comb of its owner's key, byte for byte (K256Reg::wide_matches' builder)
 extern "C" int sbv_secp256k1_hot_selfcheck(uint32_t index) {
     SBV_ENTER(c);
-    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
-    sbv::KeyPool& kp = c.k256pool;
-    if (!kp.wtab || !kp.kwide || index >= kp.wide_cap) { g_err = "no such comb in the secp256k1 hot-key pool"; return SBV_EINVAL; }
-    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    std::vector<u32> kw(kp.kc.cap);
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(kw.data(), kp.kwide, kw.size() * sizeof(u32), hipMemcpyDeviceToHost));
-    size_t slot = kw.size();
-    for (size_t i = 0; i < kw.size(); ++i) if (kw[i] == index) slot = i;
-    if (slot == kw.size()) { g_err = "sbv_secp256k1_hot_selfcheck: no promoted key has this index"; return SBV_EINVAL; }
     uint8_t key[SBV_K256_KEY_BYTES];
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(key, kp.kc.keys + slot * 16, sizeof key, hipMemcpyDeviceToHost));
+    if (const int rc = hot_comb_key(c, SBV_SCHEME_SECP256K1, "sbv_secp256k1_hot_selfcheck", index, key, sizeof key)) return rc;
     std::vector<sbv::kapt> want(SBV_K256_WIDE_ENTRIES), got(SBV_K256_WIDE_ENTRIES);
     if (!sbv::host_build_k256_wide_comb(key, want.data())) return 0;        // only points are promoted
-    HIP_TRY(SBV_EDEVICE, hipMemcpy((void*)got.data(), reinterpret_cast<const sbv::kapt*>(kp.wtab) + (size_t)index * SBV_K256_WIDE_ENTRIES, SBV_K256_WIDE_COMB_BYTES, hipMemcpyDeviceToHost));
+    HIP_TRY(SBV_EDEVICE, hipMemcpy((void*)got.data(), static_cast<const sbv::kapt*>(c.k256pool.hp.wtab) + (size_t)index * SBV_K256_WIDE_ENTRIES, SBV_K256_WIDE_COMB_BYTES, hipMemcpyDeviceToHost));
     return memcmp((const void*)got.data(), (const void*)want.data(), SBV_K256_WIDE_COMB_BYTES) == 0 ? 1 : 0;
 }
 
@@ -3623,14 +3497,15 @@ extern "C" int sbv_debug_hot_check(int device, uint32_t out[8]) {
     Context& c = *cp;
     if (!c.ready) return SBV_ENOTINIT;
     sbv::GroupBuffers& b = c.grp;
+    const sbv::HotPool& hp = b.hp;
     for (int i = 0; i < 8; ++i) out[i] = 0;
-    if (!b.wtab || !b.kwide) return SBV_OK;
+    if (!hp.wtab || !hp.kwide) return SBV_OK;
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    std::vector<u32> kw(b.kc.cap), wo(b.wide_cap), hot(4);
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(kw.data(), b.kwide, kw.size() * sizeof(u32), hipMemcpyDeviceToHost));
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(wo.data(), b.wowner, wo.size() * sizeof(u32), hipMemcpyDeviceToHost));
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(hot.data(), b.hot, 4 * sizeof(u32), hipMemcpyDeviceToHost));
+    std::vector<u32> kw(b.kc.cap), wo(hp.wide_cap), hot(4);
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(kw.data(), hp.kwide, kw.size() * sizeof(u32), hipMemcpyDeviceToHost));
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(wo.data(), hp.wowner, wo.size() * sizeof(u32), hipMemcpyDeviceToHost));
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(hot.data(), hp.hot, 4 * sizeof(u32), hipMemcpyDeviceToHost));
     out[7] = hot[0];
     if (getenv("SBV_DEBUG_HOT_DUMP")) {          // tools/stress_logical.py: the whole bookkeeping of the context on stderr
         u32 cnt[4] = {0, 0, 0, 0};
@@ -3639,10 +3514,10 @@ extern "C" int sbv_debug_hot_check(int device, uint32_t out[8]) {
         std::vector<u32> keys((size_t)entries * 16), kh(b.kc.cap);
         std::vector<uint8_t> kv(entries), kf(entries);
         (void)hipMemcpy(keys.data(), b.kc.keys, keys.size() * sizeof(u32), hipMemcpyDeviceToHost);
-        (void)hipMemcpy(kh.data(), b.khits, kh.size() * sizeof(u32), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(kh.data(), hp.khits, kh.size() * sizeof(u32), hipMemcpyDeviceToHost);
         (void)hipMemcpy(kv.data(), b.kvalid, entries, hipMemcpyDeviceToHost);
         (void)hipMemcpy(kf.data(), b.kfull, entries, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[hot dump ctx %d] cache entries %u (hits %u misses %u) hot %u %u %u %u tick %u\n", c.device, cnt[0], cnt[1], cnt[2], hot[0], hot[1], hot[2], hot[3], b.hot_tick);
+        fprintf(stderr, "[hot dump ctx %d] cache entries %u (hits %u misses %u) hot %u %u %u %u tick %u\n", c.device, cnt[0], cnt[1], cnt[2], hot[0], hot[1], hot[2], hot[3], hp.hot_tick);
         std::unordered_map<std::string, u32> seen;
         for (u32 sl = 0; sl < entries; ++sl) {
             const std::string k((const char*)&keys[(size_t)sl * 16], 64);
@@ -3656,19 +3531,19 @@ extern "C" int sbv_debug_hot_check(int device, uint32_t out[8]) {
     const size_t stride = sbv::gcomb_entries(SBV_HOT_BITS), per = (size_t)1 << (SBV_HOT_BITS - 1);
     const size_t W = stride / per;
     std::vector<sbv::apt> want(stride), got(stride);
-    std::vector<u32> users(b.wide_cap, 0);
+    std::vector<u32> users(hp.wide_cap, 0);
     unsigned hw = std::thread::hardware_concurrency();
     for (size_t slot = 0; slot < kw.size(); ++slot) {
         const u32 w = kw[slot];
         if (w == 0xFFFFFFFFu) continue;
         ++out[0];
-        if (w >= b.wide_cap) { ++out[5]; continue; }
+        if (w >= hp.wide_cap) { ++out[5]; continue; }
         if (wo[w] != slot) ++out[5];
         if (users[w]++) ++out[6];
         uint8_t key[64];
         HIP_TRY(SBV_EDEVICE, hipMemcpy(key, b.kc.keys + slot * 16, 64, hipMemcpyDeviceToHost));
         if (!sbv::host_build_wide_key_table(key, SBV_HOT_BITS, want.data(), (int)(hw > 32 ? 32 : (hw ? hw : 1)))) continue;
-        HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), b.wtab + (size_t)w * stride, stride * sizeof(sbv::apt), hipMemcpyDeviceToHost));
+        HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), static_cast<const sbv::apt*>(hp.wtab) + (size_t)w * stride, stride * sizeof(sbv::apt), hipMemcpyDeviceToHost));
         size_t bad = 0, first = 0;
         const size_t lim = (W - 1) * per + (((size_t)1 << (SBV_HOT_BITS / 2)) - 1);
         for (size_t e = 0; e < lim; ++e)
@@ -3761,7 +3636,7 @@ extern "C" int sbv_p256_pool_stats(uint32_t out[6]) {
     out[1] = c.grp.ktab ? c.grp.max_groups : 0;
     out[2] = c.pools_shrunk ? 1u : 0u;
     out[3] = c.group_nomem_events;
-    out[4] = c.grp.wide_cap;
+    out[4] = c.grp.hp.wide_cap;
     out[5] = (u32)c.mem_share;
     return SBV_OK;
 }
@@ -3770,23 +3645,13 @@ extern "C" int sbv_p256_pool_stats(uint32_t out[6]) {
 // window (the carry of the signed recoding) the babies, of which entry 1 is the only one ever read.  1 = equal, 0 = different.
 extern "C" int sbv_p256_hot_selfcheck(uint32_t index) {
     SBV_ENTER(c);
-    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
-    sbv::GroupBuffers& b = c.grp;
-    if (!b.wtab || !b.kwide) { g_err = "no hot-key pool"; return SBV_EINVAL; }
-    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    std::vector<u32> kw(b.kc.cap);
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(kw.data(), b.kwide, kw.size() * sizeof(u32), hipMemcpyDeviceToHost));
-    size_t slot = kw.size();
-    for (size_t i = 0; i < kw.size(); ++i) if (kw[i] == index) slot = i;
-    if (slot == kw.size()) { g_err = "sbv_p256_hot_selfcheck: no promoted key has this index"; return SBV_EINVAL; }
     uint8_t key[64];
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(key, b.kc.keys + slot * 16, 64, hipMemcpyDeviceToHost));
+    if (const int rc = hot_comb_key(c, SBV_SCHEME_P256, "sbv_p256_hot_selfcheck", index, key, sizeof key)) return rc;
     const size_t stride = sbv::gcomb_entries(SBV_HOT_BITS), per = (size_t)1 << (SBV_HOT_BITS - 1);
     std::vector<sbv::apt> want(stride), got(stride);
     unsigned hw = std::thread::hardware_concurrency();
     if (!sbv::host_build_wide_key_table(key, SBV_HOT_BITS, want.data(), (int)(hw > 32 ? 32 : (hw ? hw : 1)))) return 0;
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), b.wtab + (size_t)index * stride, stride * sizeof(sbv::apt), hipMemcpyDeviceToHost));
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), static_cast<const sbv::apt*>(c.grp.hp.wtab) + (size_t)index * stride, stride * sizeof(sbv::apt), hipMemcpyDeviceToHost));
     const size_t W = stride / per;                                            // 17
     if (memcmp(got.data(), want.data(), (W - 1) * per * sizeof(sbv::apt)) != 0) return 0;
     return memcmp(got.data() + (W - 1) * per, want.data() + (W - 1) * per, (((size_t)1 << (SBV_HOT_BITS / 2)) - 1) * sizeof(sbv::apt)) == 0 ? 1 : 0;

@@ -378,6 +378,79 @@ def test_small_device_gets_smaller_pools_not_enomem(oracle):
         sbv.shutdown()
 
 
+_SETTERS_DROP = r"""
+import ctypes, os, sys
+sys.path.insert(0, os.getcwd())
+import consensus_amd as sbv
+oracle = ctypes.CDLL(os.path.join("oracle", "libsbv_oracle.so"))
+P256, K256, ED = sbv.SCHEME_P256, sbv.SCHEME_SECP256K1, sbv.SCHEME_ED25519
+n = 4 * 512
+batch = {}
+for scheme, gen, size, seed in ((P256, oracle.sbvo_gen_batch, 160, 0x5E71), (K256, oracle.sbvo_k256_gen_batch, 160, 0x5E72),
+                                (ED, oracle.sbvo_ed25519_gen_batch, 128, 0x5E73)):
+    gen.argtypes = [ctypes.c_uint32, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    tup = ctypes.create_string_buffer(size * n); exp = ctypes.create_string_buffer(n // 8)
+    gen(seed, n, 4, 0, tup, exp, 8)                      # 4 signers x 512 tuples, all valid
+    assert exp.raw == b"\xff" * (n // 8)
+    batch[scheme] = (tup.raw, exp.raw)
+verify = {P256: sbv.verify_batch, K256: sbv.secp256k1_verify_batch, ED: sbv.ed25519_verify_batch}
+setter = {P256: sbv.hot_keys, K256: sbv.k256_hot_keys, ED: sbv.ed_hot_keys}
+stats = {P256: sbv.hot_key_stats, K256: sbv.k256_hot_key_stats, ED: sbv.ed_hot_key_stats}
+
+def run(scheme, times=1):
+    for _ in range(times):
+        assert verify[scheme](batch[scheme][0], n) == batch[scheme][1], scheme
+
+def state(scheme):                                       # (promoted combs, pool capacity, cached keys)
+    return stats[scheme]()[:2] + sbv.key_cache_stats(scheme)[:1]
+
+sbv.init(0)
+try:
+    sbv.set_grouping(True, 1, 8, 64)
+    for s in (P256, K256, ED):
+        setter[s](8, 64)
+    for s in (P256, K256, ED):
+        run(s, 2)                                        # the combs are promoted behind the first batch
+    if any(stats[s]()[1] == 0 for s in (P256, K256, ED)):
+        print("no room for the pool")
+        sys.exit(0)
+    for s in (P256, K256, ED):
+        assert state(s) == (4, 8, 4), (s, state(s))
+    sbv.ed_hot_keys(16, 64)                              # 1: Ed25519's pool and cache only
+    assert state(ED) == (0, 0, 0) and state(P256) == (4, 8, 4) and state(K256) == (4, 8, 4), [state(s) for s in (P256, K256, ED)]
+    run(ED, 2)
+    assert state(ED) == (4, 16, 4), state(ED)
+    sbv.k256_hot_keys(16, 64)                            # 2: secp256k1's pool and cache only
+    assert state(K256) == (0, 0, 0) and state(P256) == (4, 8, 4) and state(ED) == (4, 16, 4), [state(s) for s in (P256, K256, ED)]
+    run(K256, 2)
+    assert state(K256) == (4, 16, 4), state(K256)
+    sbv.hot_keys(16, 64)                                 # 3: the P-256 setter drops every scheme's pool and cache
+    assert [state(s) for s in (P256, K256, ED)] == [(0, 0, 0)] * 3, [state(s) for s in (P256, K256, ED)]
+    for s in (P256, K256, ED):                           # 4: the verdicts are still the generator's
+        run(s)
+    print("setters ok")
+finally:
+    sbv.hot_keys(1024, 4096); sbv.ed_hot_keys(1024, 4096); sbv.k256_hot_keys(0, 4096)
+    sbv.set_grouping(True, sbv.GROUP_MIN_BATCH_DEFAULT, 0, 0)
+"""
+
+
+def test_hot_key_setters_drop_only_what_they_own():
+    """A hot-key setter called with a new pool size frees pools that the next grouped batch rebuilds.  sbv_ed25519_hot_keys and
+    sbv_secp256k1_hot_keys drop their own scheme's comb pool and key-table cache; sbv_p256_hot_keys drops all three schemes', because
+    the P-256 pools are freed together with the grouping arrays the other two share.  In a fresh process: per scheme one batch of
+    4 signers x 512 valid tuples (2 048 tuples), verified twice with pools of 8 combs from 64 hits on, so that every scheme holds 4
+    promoted combs and 4 cached keys; then each setter in turn, reading (promoted, capacity, cached keys) of all three schemes."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if "HOT_KEYS" not in k and "HOT_MIN_HITS" not in k}
+    out = subprocess.run([sys.executable, "-c", _SETTERS_DROP], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    if out.returncode == 0 and "no room for the pool" in out.stdout:
+        pytest.skip("no room for the pool")
+    assert out.returncode == 0 and "setters ok" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
+
+
 def test_config3_registered_key_sharded_entry_550000(oracle, openssl_check):
     """configs[3] as BASELINE.json words it, on the consenters' resident combs: sbv_p256_verify_batch_keyed_sharded over
     550 000 = 50 000 x 11 records r | s | hash + key slots, 16 registered consenter keys with their wide combs.  Accept bitmap ==
