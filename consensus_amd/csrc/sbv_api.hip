@@ -31,6 +31,7 @@
 
 #include "../../include/sbv.h"
 #include "call_buffers.h"
+#include "shard_pieces.h"
 #include "ed25519_keyed.h"
 #include "ed25519_kernels.h"
 #include "p256_kernels.h"
@@ -1129,6 +1130,17 @@ std::mutex g_sharded_mu;
 // staging of the key-affine partition (part_enqueue below), per device, under that device's context lock
 struct PartBuffers { uint8_t* d_dense = nullptr; u32* d_idx = nullptr; u32* d_count = nullptr; uint8_t* d_bits = nullptr; u32* h_count = nullptr; size_t cap = 0; };
 PartBuffers g_part[kMaxDevices];
+void shard_buffers_free(ShardBuffers& sb) {
+    for (uint8_t* p : {sb.d_gather, sb.d_q, sb.d_on, sb.d_onq, sb.d_full, sb.d_stage2, sb.d_slots2, sb.d_msgs2, sb.d_sigs2, sb.d_moff2, sb.d_soff2})
+        if (p) (void)hipFree(p);
+    sb = ShardBuffers();
+}
+void part_buffers_free(PartBuffers& pb) {
+    void* dev[] = {pb.d_dense, pb.d_idx, pb.d_count, pb.d_bits};
+    for (void* p : dev) if (p) (void)hipFree(p);
+    if (pb.h_count) (void)hipHostFree(pb.h_count);
+    pb = PartBuffers();
+}
 
 int shutdown_context(Context& c) {
     if (!c.ready) return SBV_OK;
@@ -1137,23 +1149,8 @@ int shutdown_context(Context& c) {
     free_buffers(c);
     free_group_buffers(c);
     if (c.device >= 0 && c.device < kMaxDevices) {
-        ShardBuffers& sb = g_shard[c.device];
-        if (sb.d_gather) (void)hipFree(sb.d_gather);
-        if (sb.d_q) (void)hipFree(sb.d_q);
-        if (sb.d_on) (void)hipFree(sb.d_on);
-        if (sb.d_onq) (void)hipFree(sb.d_onq);
-        if (sb.d_full) (void)hipFree(sb.d_full);
-        if (sb.d_stage2) (void)hipFree(sb.d_stage2);
-        if (sb.d_slots2) (void)hipFree(sb.d_slots2);
-        for (uint8_t* p : {sb.d_msgs2, sb.d_sigs2, sb.d_moff2, sb.d_soff2}) if (p) (void)hipFree(p);
-        sb = ShardBuffers();
-        PartBuffers& pb = g_part[c.device];
-        if (pb.d_dense) (void)hipFree(pb.d_dense);
-        if (pb.d_idx) (void)hipFree(pb.d_idx);
-        if (pb.d_bits) (void)hipFree(pb.d_bits);
-        if (pb.d_count) (void)hipFree(pb.d_count);
-        if (pb.h_count) (void)hipHostFree(pb.h_count);
-        pb = PartBuffers();
+        shard_buffers_free(g_shard[c.device]);
+        part_buffers_free(g_part[c.device]);
     }
     if (c.d_gtab) (void)hipFree(c.d_gtab);
     c.d_gtab = nullptr;
@@ -3777,10 +3774,18 @@ bool rccl_setup() {
     return true;
 }
 
-size_t gcd_sz(size_t a, size_t b) { while (b) { const size_t t = a % b; a = b; b = t; } return a; }
-size_t shard_granule(size_t group) {
-    const size_t g8 = 8 * (group ? group : 1);
-    return 512 / gcd_sz(512, g8) * g8;            // lcm(512, 8 * group)
+using sbv::shard_granule;                         // shard_pieces.h
+
+// The tail of the two quorum kernels, reached by every lane: lane pidx's bit goes into an LSB-first bitmap of nbits bits, lanes 0-7
+// writing the wavefront's 8 bytes.
+__device__ __forceinline__ void write_wave_bits(bool bit, size_t pidx, size_t nbits, uint8_t* __restrict__ bitmap) {
+    const unsigned long long m = __ballot(bit);
+    const int lane = threadIdx.x & 63;
+    const size_t wave_first = pidx - (size_t)lane;
+    if (lane < 8) {
+        const size_t byte = (wave_first >> 3) + (size_t)lane;
+        if (byte < ((nbits + 7) >> 3)) bitmap[byte] = (uint8_t)(m >> (8 * lane));
+    }
 }
 
 // per proposal: at least `quorum` accepted signatures by DISTINCT public keys (>= Q distinct signers:
@@ -3812,13 +3817,7 @@ __global__ __launch_bounds__(256) void k_quorum_bits(const uint8_t* __restrict__
         }
         decided = count >= quorum;
     }
-    const unsigned long long m = __ballot(decided);
-    const int lane = threadIdx.x & 63;
-    const size_t wave_first = pidx - (size_t)lane;
-    if (lane < 8) {
-        const size_t byte = (wave_first >> 3) + (size_t)lane;
-        if (byte < ((nprops + 7) >> 3)) qbitmap[byte] = (uint8_t)(m >> (8 * lane));
-    }
+    write_wave_bits(decided, pidx, nprops, qbitmap);
 }
 
 // ---- key-affine partition ---------------------------------------------------------------------------------
@@ -3930,83 +3929,6 @@ int grow_bytes(uint8_t*& ptr, size_t& cap, size_t want) {
     return SBV_OK;
 }
 
-// One device's share of a sharded call; c.mu held.  Two upload slots and the copy stream: while the kernels of piece i run
-// on c.stream, the tuples of piece i + 1 are on their way over PCIe (168 MB per 2^20 tuples: 3.3 ms at 50 GB/s, as long as
-// the kernels themselves).  Pieces are 2^18 tuples (a multiple of the granule) when the key-table cache is on — the first
-// piece builds the signers' combs, the others find them (0.87 ms per piece, 1.7 ms for the first; one cold 2^20 step is
-// 3.45 ms) — and whole launches of up to kMaxChunk tuples when it is off (every cold piece would rebuild every table).
-// The bitmap is written straight into this device's slot of the gather buffer, the quorum bits of each piece behind it;
-// nothing waits on the host until the last piece is enqueued.  h2d_us: the copies' own durations, summed; kern_us: from the
-// end of the first copy to the end of the last kernel (waits for later copies included).
-int verify_shard(Context& c, const uint8_t* h_tuples, size_t m, size_t group, u32 quorum, uint8_t* d_slot, uint8_t* d_qslot,
-                 double* h2d_us, double* kern_us) {
-    if (!c.ready) { g_err = "device not initialised"; return SBV_ENOTINIT; }
-    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
-    const size_t gran = shard_granule(group);
-    const size_t want_piece = c.kc_on[0] && c.group_enabled ? g_shard_piece : kMaxChunk;
-    size_t chunk = (want_piece < kMaxChunk ? want_piece : kMaxChunk) / gran * gran;
-    if (chunk == 0) chunk = kMaxChunk / gran * gran;
-    if (chunk == 0) { g_err = "group too large"; return SBV_EINVAL; }
-    size_t pieces = (m + chunk - 1) / chunk;
-    if (pieces > 1) {
-        // EQUAL pieces (round 6): 550 000 signatures in pieces of 2^18 used to end with a piece of 32 000 that paid the step's fixed
-        // chain (grouping, sort, classes: ~0.4 ms) for a tenth of the work, behind the last upload
-        const size_t even = ((m + pieces - 1) / pieces + gran - 1) / gran * gran;
-        if (even && even <= chunk) { chunk = even; pieces = (m + chunk - 1) / chunk; }
-    }
-    int rc = ensure_capacity(c, m < chunk ? m : chunk);
-    if (rc != SBV_OK) return rc;
-    ShardBuffers& sbuf = g_shard[c.device];
-    if (pieces > 1) {
-        rc = grow_bytes(sbuf.d_stage2, sbuf.stage2_cap, chunk * SBV_TUPLE_BYTES);
-        if (rc != SBV_OK) return rc;
-        if (!c.copy_stream && hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking) != hipSuccess) { g_err = "hipStreamCreate failed"; return SBV_EDEVICE; }
-    }
-    hipStream_t up = pieces > 1 ? c.copy_stream : c.stream;
-    uint8_t* stage[2] = {c.d_tuples, pieces > 1 ? sbuf.d_stage2 : c.d_tuples};
-    // events: per piece copy start / copy end / kernels end (timing), destroyed before returning
-    std::vector<hipEvent_t> ev(3 * pieces, nullptr);
-    auto drop_events = [&] { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
-    for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) { drop_events(); g_err = "hipEventCreate failed"; return SBV_EDEVICE; }
-    hipError_t he = hipSuccess;
-    auto step = [&](hipError_t r) { if (he == hipSuccess) he = r; };
-    if (c.busy_valid) {                        // kernels of an earlier call (pipelined host entry, a key-affine part) may still be using the scratch and group buffers
-        step(hipStreamWaitEvent(c.stream, c.busy, 0));
-        if (pieces > 1) step(hipStreamWaitEvent(up, c.busy, 0));
-    }
-    size_t i = 0;
-    for (size_t off = 0; off < m && rc == SBV_OK && he == hipSuccess; off += chunk, ++i) {
-        const size_t k = m - off < chunk ? m - off : chunk;
-        uint8_t* d_in = stage[i & 1];
-        if (i >= 2) step(hipStreamWaitEvent(up, ev[3 * (i - 2) + 2], 0));       // the slot's previous kernels are done with it
-        step(hipEventRecord(ev[3 * i], up));
-        step(hipMemcpyAsync(d_in, h_tuples + off * SBV_TUPLE_BYTES, k * SBV_TUPLE_BYTES, hipMemcpyHostToDevice, up));
-        step(hipEventRecord(ev[3 * i + 1], up));
-        if (pieces > 1) step(hipStreamWaitEvent(c.stream, ev[3 * i + 1], 0));
-        if (he != hipSuccess) break;
-        rc = enqueue(c, d_in, k, d_slot + off / 8, c.stream, nullptr);
-        if (rc != SBV_OK) break;
-        if (d_qslot && group > 0 && quorum > 0) {
-            const size_t props = k / group;                 // k is a multiple of group except for a ragged tail, which gets no bit
-            if (props)
-                hipLaunchKernelGGL(k_quorum_bits, dim3((unsigned)((props + 255) / 256)), dim3(256), 0, c.stream, d_in, d_slot + off / 8,
-                                   props, (u32)group, quorum, d_qslot + (off / group) / 8);
-        }
-        step(hipEventRecord(ev[3 * i + 2], c.stream));
-    }
-    // drain in every case: the slots and the caller's host buffer must not be in use when this returns
-    if (pieces > 1) step(hipStreamSynchronize(up));
-    step(hipStreamSynchronize(c.stream));
-    if (rc == SBV_OK && he != hipSuccess) rc = fail(SBV_EDEVICE, "verify_shard", he);
-    if (rc == SBV_OK) {
-        if (h2d_us) for (size_t j = 0; j < pieces; ++j) *h2d_us += 1e3 * ms_between(ev[3 * j], ev[3 * j + 1]);
-        if (kern_us) *kern_us += 1e3 * ms_between(ev[1], ev[3 * (pieces - 1) + 2]);
-    }
-    drop_events();
-    c.busy_valid = false;
-    return rc;
-}
-
 // The registered-key form of k_quorum_bits: signature t of a proposal carries a key SLOT (equal keys share a slot: sbv_p256_register_keys),
 // so ">= quorum accepted signatures by distinct signers" (internal/bft/viewchanger.go:681-727) counts distinct accepted slots.
 __global__ __launch_bounds__(256) void k_quorum_bits_slots(const u32* __restrict__ slots, const uint8_t* __restrict__ bitmap,
@@ -4029,32 +3951,76 @@ __global__ __launch_bounds__(256) void k_quorum_bits_slots(const u32* __restrict
         }
         decided = count >= quorum;
     }
-    const unsigned long long m = __ballot(decided);
-    const int lane = threadIdx.x & 63;
-    const size_t wave_first = pidx - (size_t)lane;
-    if (lane < 8) {
-        const size_t byte = (wave_first >> 3) + (size_t)lane;
-        if (byte < ((nprops + 7) >> 3)) qbitmap[byte] = (uint8_t)(m >> (8 * lane));
-    }
+    write_wave_bits(decided, pidx, nprops, qbitmap);
+}
+
+// The quorum bits of tuples [off, off + k) of a share on `stream`, if the call asked for any: by distinct key of `tuples` (k tuples of
+// 160 bytes) or, with `slots` given, by distinct slot.  d_bits / d_q are the share's bitmaps; off is a multiple of 8 * group, and k a
+// multiple of group except for a ragged tail, which gets no bit.
+void launch_quorum(const uint8_t* tuples, const u32* slots, uint8_t* d_bits, uint8_t* d_q, size_t off, size_t k, size_t group, u32 quorum,
+                   hipStream_t stream) {
+    if (!d_q || group == 0 || quorum == 0) return;
+    const size_t props = k / group;
+    if (!props) return;
+    const dim3 grid((unsigned)((props + 255) / 256));
+    uint8_t* q = d_q + (off / group) / 8;
+    if (slots) hipLaunchKernelGGL(k_quorum_bits_slots, grid, dim3(256), 0, stream, slots, d_bits + off / 8, props, (u32)group, quorum, q);
+    else hipLaunchKernelGGL(k_quorum_bits, grid, dim3(256), 0, stream, tuples, d_bits + off / 8, props, (u32)group, quorum, q);
 }
 
 // Tuples per upload piece of a registered-key shard (SBV_SHARD_PIECE_KEYED).  No table is built per batch, so a piece only has to
 // fill the device: 2^17 signatures = two wavefronts on every SIMD, above the 8-lanes-per-signature latency form's range.
 size_t g_shard_piece_keyed = (size_t)1 << 17;
 
-// One device's share of a sharded registered-key call; c.mu and g_reg_mu (shared) held.  The same two upload slots as verify_shard:
-// 96-byte records r | s | hash and their 4-byte slots — 100 B per signature over PCIe instead of 160 — of piece i + 1 travel on
-// the copy stream beside stage A + B of piece i; quorum bits by distinct slot.
-// pieces of a registered-key shard: as many as the configured piece size asks for, then EQUAL sizes (a multiple of the granule) —
-// a short last piece would fall into the 8-lanes-per-signature latency kernel and every piece fills the device for about one round
-size_t keyed_piece(size_t m, size_t gran) {
-    size_t chunk = (g_shard_piece_keyed < kMaxChunk / 2 ? g_shard_piece_keyed : kMaxChunk / 2) / gran * gran;
-    if (chunk == 0) chunk = gran;
-    const size_t pieces = (m + chunk - 1) / chunk;
-    size_t per = ((m + pieces - 1) / pieces + gran - 1) / gran * gran;
-    return per < chunk ? per : chunk;
+// a share of more than one piece uploads through the copy stream, created on first use
+int ensure_copy_stream(Context& c) {
+    if (!c.copy_stream && hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking) != hipSuccess) { g_err = "hipStreamCreate failed"; return SBV_EDEVICE; }
+    return SBV_OK;
 }
 
+// ---- one device's share of a sharded call -------------------------------------------------------------------------------------
+// The three functions below run their share through the piece pipeline of shard_pieces.h (sbv::run_pieces): pieces of a planned size go
+// up through two staging sets — the context's own buffers and their twins in ShardBuffers — on the copy stream while the kernels of the
+// piece before run; the order of the waits, the first failure, the drain of every stream and the timing sums live there (h2d_us: the
+// copies' own durations, summed; kern_us: from the end of the first copy to the end of the last kernel).  Each function checks its
+// preconditions, sizes the staging for the plan and says what a piece uploads and what it enqueues.  The bitmap is written straight into
+// this device's slot of the gather buffer, the quorum bits of each piece behind it; nothing waits on the host until the last piece is
+// enqueued.
+//
+// The tuple form; c.mu held.  168 MB per 2^20 tuples over PCIe: 3.3 ms at 50 GB/s, as long as the kernels themselves.  Pieces are 2^18
+// tuples when the key-table cache is on (0.87 ms per piece, 1.7 ms for the first, which builds the signers' combs; one cold 2^20 step is
+// 3.45 ms) and whole launches when it is off (sbv::plan_tuple_pieces); every piece's kernels run on c.stream.
+int verify_shard(Context& c, const uint8_t* h_tuples, size_t m, size_t group, u32 quorum, uint8_t* d_slot, uint8_t* d_qslot,
+                 double* h2d_us, double* kern_us) {
+    if (!c.ready) { g_err = "device not initialised"; return SBV_ENOTINIT; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    sbv::PiecePlan p;
+    int rc = sbv::plan_tuple_pieces(m, shard_granule(group), c.kc_on[0] && c.group_enabled, g_shard_piece, kMaxChunk, &p, &g_err);
+    if (rc == SBV_OK) rc = ensure_capacity(c, m < p.chunk ? m : p.chunk);
+    ShardBuffers& sbuf = g_shard[c.device];
+    if (rc == SBV_OK && p.pieces > 1) {
+        rc = grow_bytes(sbuf.d_stage2, sbuf.stage2_cap, p.chunk * SBV_TUPLE_BYTES);
+        if (rc == SBV_OK) rc = ensure_copy_stream(c);
+    }
+    if (rc != SBV_OK) return rc;
+    uint8_t* const stage[2] = {c.d_tuples, sbuf.d_stage2};
+    return sbv::run_pieces({c.stream, c.copy_stream, nullptr}, c.busy, &c.busy_valid, m, p.chunk, "verify_shard", h2d_us, kern_us, &g_err,
+        [&](size_t, size_t off, size_t k, int w, hipStream_t up) {
+            return hipMemcpyAsync(stage[w], h_tuples + off * SBV_TUPLE_BYTES, k * SBV_TUPLE_BYTES, hipMemcpyHostToDevice, up);
+        },
+        [&](size_t, size_t off, size_t k, int w, hipStream_t stream) {
+            const int st = enqueue(c, stage[w], k, d_slot + off / 8, stream, nullptr);
+            if (st == SBV_OK) launch_quorum(stage[w], nullptr, d_slot, d_qslot, off, k, group, quorum, stream);
+            return st;
+        });
+}
+
+// The registered-key form; c.mu and g_reg_mu (shared) held.  96-byte records r | s | hash and their 4-byte slots — 100 B per signature
+// over PCIe instead of 160; quorum bits by distinct slot.  Two pieces are in flight (sbv::plan_keyed_pieces): piece i + 1 is uploaded and
+// runs its stage A on the grouped step's side stream — idle on this path; a process gets four hardware queues — in its own half of the
+// scratch planes while stage B of piece i still fills the device.  Stage A is a short latency-bound chain that would otherwise stand
+// between two stage-B launches on one stream (measured: 5 pieces of 2^17 on one stream 1.57 ms of kernels for 550 000 signatures
+// against 1.05 ms in one launch; profiles/r05/).
 int verify_shard_keyed(Context& c, const uint8_t* h_rsh, const u32* h_slots, size_t m, size_t group, u32 quorum, uint8_t* d_slot, uint8_t* d_qslot,
                        double* h2d_us, double* kern_us) {
     if (!c.ready) { g_err = "device not initialised"; return SBV_ENOTINIT; }
@@ -4062,76 +4028,36 @@ int verify_shard_keyed(Context& c, const uint8_t* h_rsh, const u32* h_slots, siz
     int rc = sync_registry(c);                 // this device's replica of the key registry (a no-op when it is current)
     if (rc != SBV_OK) return rc;
     if (c.nkeys == 0) { g_err = "no keys registered"; return SBV_EINVAL; }
-    const size_t gran = shard_granule(group);
-    if (gran > kMaxChunk / 2) { g_err = "group too large"; return SBV_EINVAL; }
-    const size_t chunk = keyed_piece(m, gran);
-    const size_t pieces = (m + chunk - 1) / chunk;
-    const bool two = pieces > 1;
-    // Two pieces are in flight: piece i + 1 is uploaded (copy stream) and runs its stage A (second kernel stream, its own half of
-    // the scratch planes) while stage B of piece i still fills the device — stage A is a short latency-bound chain that would
-    // otherwise stand between two stage-B launches on one stream (measured: 5 pieces of 2^17 on one stream 1.57 ms of kernels for
-    // 550 000 signatures against 1.05 ms in one launch; profiles/r05/).
-    rc = ensure_capacity(c, two ? 2 * chunk : m);
-    if (rc != SBV_OK) return rc;
+    sbv::PiecePlan p;
+    rc = sbv::plan_keyed_pieces(m, shard_granule(group), g_shard_piece_keyed, kMaxChunk, &p, &g_err);
+    const bool two = p.pieces > 1;
+    if (rc == SBV_OK) rc = ensure_capacity(c, two ? 2 * p.chunk : m);
     ShardBuffers& sbuf = g_shard[c.device];
-    if (two) {
-        rc = grow_bytes(sbuf.d_stage2, sbuf.stage2_cap, chunk * SBV_TUPLE_BYTES);
-        if (rc == SBV_OK) rc = grow_bytes(sbuf.d_slots2, sbuf.slots2_cap, chunk * sizeof(u32));
-        if (rc != SBV_OK) return rc;
-        if (!c.copy_stream && hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking) != hipSuccess) { g_err = "hipStreamCreate failed"; return SBV_EDEVICE; }
+    if (rc == SBV_OK && two) {
+        rc = grow_bytes(sbuf.d_stage2, sbuf.stage2_cap, p.chunk * SBV_TUPLE_BYTES);
+        if (rc == SBV_OK) rc = grow_bytes(sbuf.d_slots2, sbuf.slots2_cap, p.chunk * sizeof(u32));
+        if (rc == SBV_OK) rc = ensure_copy_stream(c);
     }
-    hipStream_t up = two ? c.copy_stream : c.stream;
-    hipStream_t ks[2] = {c.stream, two ? c.gsync.side_a : c.stream};      // the grouped step's side stream is idle on this path (a process gets four hardware queues)
-    uint8_t* stage[2] = {c.d_tuples, two ? sbuf.d_stage2 : c.d_tuples};
-    u32* sstage[2] = {c.d_slots, two ? reinterpret_cast<u32*>(sbuf.d_slots2) : c.d_slots};
-    std::vector<hipEvent_t> ev(3 * pieces, nullptr);
-    auto drop_events = [&] { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
-    for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) { drop_events(); g_err = "hipEventCreate failed"; return SBV_EDEVICE; }
-    hipError_t he = hipSuccess;
-    auto step = [&](hipError_t r) { if (he == hipSuccess) he = r; };
-    if (c.busy_valid) {
-        step(hipStreamWaitEvent(ks[0], c.busy, 0));
-        if (two) { step(hipStreamWaitEvent(ks[1], c.busy, 0)); step(hipStreamWaitEvent(up, c.busy, 0)); }
-    }
-    size_t i = 0;
-    for (size_t off = 0; off < m && rc == SBV_OK && he == hipSuccess; off += chunk, ++i) {
-        const size_t k = m - off < chunk ? m - off : chunk;
-        const int w = (int)(i & 1);
-        if (i >= 2) step(hipStreamWaitEvent(up, ev[3 * (i - 2) + 2], 0));       // the staging set's previous kernels are done with it
-        step(hipEventRecord(ev[3 * i], up));
-        step(hipMemcpyAsync(stage[w], h_rsh + off * 96, k * 96, hipMemcpyHostToDevice, up));
-        step(hipMemcpyAsync(sstage[w], h_slots + off, k * sizeof(u32), hipMemcpyHostToDevice, up));
-        step(hipEventRecord(ev[3 * i + 1], up));
-        if (two) step(hipStreamWaitEvent(ks[w], ev[3 * i + 1], 0));
-        if (he != hipSuccess) break;
-        rc = enqueue_keyed(c, stage[w], sstage[w], k, d_slot + off / 8, ks[w], nullptr, w ? chunk : 0);
-        if (rc != SBV_OK) break;
-        if (d_qslot && group > 0 && quorum > 0) {
-            const size_t props = k / group;
-            if (props)
-                hipLaunchKernelGGL(k_quorum_bits_slots, dim3((unsigned)((props + 255) / 256)), dim3(256), 0, ks[w], sstage[w], d_slot + off / 8,
-                                   props, (u32)group, quorum, d_qslot + (off / group) / 8);
-        }
-        step(hipEventRecord(ev[3 * i + 2], ks[w]));
-    }
-    // drain in every case: the staging sets and the caller's host buffers must not be in use when this returns
-    if (two) { step(hipStreamSynchronize(up)); step(hipStreamSynchronize(ks[1])); }
-    step(hipStreamSynchronize(ks[0]));
-    if (rc == SBV_OK && he != hipSuccess) rc = fail(SBV_EDEVICE, "verify_shard_keyed", he);
-    if (rc == SBV_OK) {
-        if (h2d_us) for (size_t j = 0; j < pieces; ++j) *h2d_us += 1e3 * ms_between(ev[3 * j], ev[3 * j + 1]);
-        if (kern_us) *kern_us += 1e3 * ms_between(ev[1], ev[3 * (pieces - 1) + 2]);
-    }
-    drop_events();
-    c.busy_valid = false;
-    return rc;
+    if (rc != SBV_OK) return rc;
+    uint8_t* const stage[2] = {c.d_tuples, sbuf.d_stage2};
+    u32* const sstage[2] = {c.d_slots, reinterpret_cast<u32*>(sbuf.d_slots2)};
+    return sbv::run_pieces({c.stream, c.copy_stream, c.gsync.side_a}, c.busy, &c.busy_valid, m, p.chunk, "verify_shard_keyed", h2d_us, kern_us, &g_err,
+        [&](size_t, size_t off, size_t k, int w, hipStream_t up) {
+            const hipError_t e = hipMemcpyAsync(stage[w], h_rsh + off * 96, k * 96, hipMemcpyHostToDevice, up);
+            return e != hipSuccess ? e : hipMemcpyAsync(sstage[w], h_slots + off, k * sizeof(u32), hipMemcpyHostToDevice, up);
+        },
+        [&](size_t, size_t off, size_t k, int w, hipStream_t stream) {
+            const int st = enqueue_keyed(c, stage[w], sstage[w], k, d_slot + off / 8, stream, nullptr, w ? p.chunk : 0);
+            if (st == SBV_OK) launch_quorum(nullptr, sstage[w], d_slot, d_qslot, off, k, group, quorum, stream);
+            return st;
+        });
 }
 
-// One device's share of a sharded raw-messages call (SURVEY.md section 8f row 1 across the node); c.mu and g_reg_mu (shared) held.
-// Piece i = signatures [first + i * chunk, ...): its message bytes, DER signatures, the slices of the caller's two offset tables as
-// they are (the kernel subtracts the slice's base) and its key slots go up on the copy stream into one of two staging sets while
-// SHA-256 + DER (k_msg_frontend), stage A and stage B of the previous piece run on c.stream.  The front end's records land in
-// Context::d_tuples: kernels of all pieces are ordered on one stream, so one record buffer serves.
+// The raw-messages form (SURVEY.md section 8f row 1 across the node); c.mu and g_reg_mu (shared) held.  Piece i = signatures
+// [first + i * chunk, ...): its message bytes, DER signatures, the slices of the caller's two offset tables as they are (the kernel
+// subtracts the slice's base) and its key slots go up into one of two staging sets; SHA-256 + DER (k_msg_frontend) and stage A of piece
+// i + 1 run beside stage B of piece i as in verify_shard_keyed.  The front end's 96-byte records land in the piece's half of
+// Context::d_tuples (160 bytes per scratch slot).
 int verify_shard_msgs(Context& c, const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const u32* h_slots,
                       size_t first, size_t m, size_t group, u32 quorum, uint8_t* d_slot, uint8_t* d_qslot, double* h2d_us, double* kern_us) {
     if (!c.ready) { g_err = "device not initialised"; return SBV_ENOTINIT; }
@@ -4139,10 +4065,11 @@ int verify_shard_msgs(Context& c, const uint8_t* msgs, const uint64_t* moff, con
     int rc = sync_registry(c);
     if (rc != SBV_OK) return rc;
     if (c.nkeys == 0) { g_err = "no keys registered"; return SBV_EINVAL; }
-    const size_t gran = shard_granule(group);
-    if (gran > kMaxChunk / 2) { g_err = "group too large"; return SBV_EINVAL; }
-    const size_t chunk = keyed_piece(m, gran);
-    const size_t pieces = (m + chunk - 1) / chunk;
+    sbv::PiecePlan p;
+    rc = sbv::plan_keyed_pieces(m, shard_granule(group), g_shard_piece_keyed, kMaxChunk, &p, &g_err);
+    if (rc != SBV_OK) return rc;
+    const size_t chunk = p.chunk;
+    const bool two = p.pieces > 1;
     size_t max_mb = 0, max_sb = 0;                 // staging for the largest piece, grown before anything is enqueued
     for (size_t off = 0; off < m; off += chunk) {
         const size_t k = m - off < chunk ? m - off : chunk;
@@ -4159,78 +4086,47 @@ int verify_shard_msgs(Context& c, const uint8_t* msgs, const uint64_t* moff, con
         if (sb > max_sb) max_sb = sb;
     }
     const size_t kmax = m < chunk ? m : chunk;
-    rc = ensure_capacity(c, pieces > 1 ? 2 * chunk : kmax);        // two pieces in flight, each in its half of the scratch planes and of the record buffer
+    rc = ensure_capacity(c, two ? 2 * chunk : kmax);        // two pieces in flight, each in its half of the scratch planes and of the record buffer
     if (rc == SBV_OK) rc = grow(c.d_msgs, c.msgs_cap, max_mb + 16);
     if (rc == SBV_OK) rc = grow(c.d_sigs, c.sigs_cap, max_sb + 16);
     if (rc == SBV_OK) rc = grow(c.d_moff, c.moff_cap, kmax + 1);
     if (rc == SBV_OK) rc = grow(c.d_soff, c.soff_cap, kmax + 1);
     ShardBuffers& sbuf = g_shard[c.device];
-    if (rc == SBV_OK && pieces > 1) {
+    if (rc == SBV_OK && two) {
         rc = grow_bytes(sbuf.d_msgs2, sbuf.msgs2_cap, max_mb + 16);
         if (rc == SBV_OK) rc = grow_bytes(sbuf.d_sigs2, sbuf.sigs2_cap, max_sb + 16);
         if (rc == SBV_OK) rc = grow_bytes(sbuf.d_moff2, sbuf.moff2_cap, (kmax + 1) * sizeof(uint64_t));
         if (rc == SBV_OK) rc = grow_bytes(sbuf.d_soff2, sbuf.soff2_cap, (kmax + 1) * sizeof(uint64_t));
         if (rc == SBV_OK) rc = grow_bytes(sbuf.d_slots2, sbuf.slots2_cap, kmax * sizeof(u32));
-        if (rc == SBV_OK && !c.copy_stream && hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking) != hipSuccess) { g_err = "hipStreamCreate failed"; rc = SBV_EDEVICE; }
+        if (rc == SBV_OK) rc = ensure_copy_stream(c);
     }
     if (rc != SBV_OK) return rc;
-    hipStream_t up = pieces > 1 ? c.copy_stream : c.stream;
-    const bool two = pieces > 1;
-    hipStream_t ks[2] = {c.stream, two ? c.gsync.side_a : c.stream};      // as verify_shard_keyed: front end + stage A of piece i + 1 beside stage B of piece i
-    uint8_t* recs[2] = {c.d_tuples, two ? c.d_tuples + chunk * 96 : c.d_tuples};      // the front end's 96-byte records (Context::d_tuples holds 160 bytes per scratch slot)
-    uint8_t* st_msgs[2] = {c.d_msgs, two ? sbuf.d_msgs2 : c.d_msgs};
-    uint8_t* st_sigs[2] = {c.d_sigs, two ? sbuf.d_sigs2 : c.d_sigs};
-    uint64_t* st_moff[2] = {c.d_moff, two ? reinterpret_cast<uint64_t*>(sbuf.d_moff2) : c.d_moff};
-    uint64_t* st_soff[2] = {c.d_soff, two ? reinterpret_cast<uint64_t*>(sbuf.d_soff2) : c.d_soff};
-    u32* st_slots[2] = {c.d_slots, two ? reinterpret_cast<u32*>(sbuf.d_slots2) : c.d_slots};
-    std::vector<hipEvent_t> ev(3 * pieces, nullptr);
-    auto drop_events = [&] { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
-    for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) { drop_events(); g_err = "hipEventCreate failed"; return SBV_EDEVICE; }
-    hipError_t he = hipSuccess;
-    auto step = [&](hipError_t r) { if (he == hipSuccess) he = r; };
-    if (c.busy_valid) {
-        step(hipStreamWaitEvent(ks[0], c.busy, 0));
-        if (two) { step(hipStreamWaitEvent(ks[1], c.busy, 0)); step(hipStreamWaitEvent(up, c.busy, 0)); }
-    }
-    size_t i = 0;
-    for (size_t off = 0; off < m && rc == SBV_OK && he == hipSuccess; off += chunk, ++i) {
-        const size_t k = m - off < chunk ? m - off : chunk;
-        const size_t a = first + off;
-        const uint64_t mbase = moff[a], sbase = soff[a];
-        const size_t mb = (size_t)(moff[a + k] - mbase), sb = (size_t)(soff[a + k] - sbase);
-        const int w = (int)(i & 1);
-        if (i >= 2) step(hipStreamWaitEvent(up, ev[3 * (i - 2) + 2], 0));       // the staging set's previous kernels are done with it
-        step(hipEventRecord(ev[3 * i], up));
-        if (mb) step(hipMemcpyAsync(st_msgs[w], msgs + mbase, mb, hipMemcpyHostToDevice, up));
-        if (sb) step(hipMemcpyAsync(st_sigs[w], sigs + sbase, sb, hipMemcpyHostToDevice, up));
-        step(hipMemcpyAsync(st_moff[w], moff + a, (k + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up));
-        step(hipMemcpyAsync(st_soff[w], soff + a, (k + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up));
-        step(hipMemcpyAsync(st_slots[w], h_slots + a, k * sizeof(u32), hipMemcpyHostToDevice, up));
-        step(hipEventRecord(ev[3 * i + 1], up));
-        if (two) step(hipStreamWaitEvent(ks[w], ev[3 * i + 1], 0));
-        if (he != hipSuccess) break;
-        step(sbv::launch_msg_frontend(st_msgs[w], st_moff[w], st_sigs[w], st_soff[w], k, reinterpret_cast<u32*>(recs[w]), ks[w], mbase, sbase, mb, sb));
-        if (he != hipSuccess) break;
-        rc = enqueue_keyed(c, recs[w], st_slots[w], k, d_slot + off / 8, ks[w], nullptr, w ? chunk : 0);
-        if (rc != SBV_OK) break;
-        if (d_qslot && group > 0 && quorum > 0) {
-            const size_t props = k / group;
-            if (props)
-                hipLaunchKernelGGL(k_quorum_bits_slots, dim3((unsigned)((props + 255) / 256)), dim3(256), 0, ks[w], st_slots[w], d_slot + off / 8,
-                                   props, (u32)group, quorum, d_qslot + (off / group) / 8);
-        }
-        step(hipEventRecord(ev[3 * i + 2], ks[w]));
-    }
-    if (two) { step(hipStreamSynchronize(up)); step(hipStreamSynchronize(ks[1])); }
-    step(hipStreamSynchronize(ks[0]));
-    if (rc == SBV_OK && he != hipSuccess) rc = fail(SBV_EDEVICE, "verify_shard_msgs", he);
-    if (rc == SBV_OK) {
-        if (h2d_us) for (size_t j = 0; j < pieces; ++j) *h2d_us += 1e3 * ms_between(ev[3 * j], ev[3 * j + 1]);
-        if (kern_us) *kern_us += 1e3 * ms_between(ev[1], ev[3 * (pieces - 1) + 2]);
-    }
-    drop_events();
-    c.busy_valid = false;
-    return rc;
+    struct Set { uint8_t *msgs, *sigs; uint64_t *moff, *soff; u32* slots; uint8_t* recs; };
+    const Set set[2] = {{c.d_msgs, c.d_sigs, c.d_moff, c.d_soff, c.d_slots, c.d_tuples},
+                        {sbuf.d_msgs2, sbuf.d_sigs2, reinterpret_cast<uint64_t*>(sbuf.d_moff2), reinterpret_cast<uint64_t*>(sbuf.d_soff2),
+                         reinterpret_cast<u32*>(sbuf.d_slots2), c.d_tuples + chunk * 96}};
+    return sbv::run_pieces({c.stream, c.copy_stream, c.gsync.side_a}, c.busy, &c.busy_valid, m, chunk, "verify_shard_msgs", h2d_us, kern_us, &g_err,
+        [&](size_t, size_t off, size_t k, int w, hipStream_t up) {
+            const size_t a = first + off;
+            const size_t mb = (size_t)(moff[a + k] - moff[a]), sb = (size_t)(soff[a + k] - soff[a]);
+            const Set& s = set[w];
+            hipError_t e = mb ? hipMemcpyAsync(s.msgs, msgs + moff[a], mb, hipMemcpyHostToDevice, up) : hipSuccess;
+            if (e == hipSuccess && sb) e = hipMemcpyAsync(s.sigs, sigs + soff[a], sb, hipMemcpyHostToDevice, up);
+            if (e == hipSuccess) e = hipMemcpyAsync(s.moff, moff + a, (k + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up);
+            if (e == hipSuccess) e = hipMemcpyAsync(s.soff, soff + a, (k + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up);
+            if (e == hipSuccess) e = hipMemcpyAsync(s.slots, h_slots + a, k * sizeof(u32), hipMemcpyHostToDevice, up);
+            return e;
+        },
+        [&](size_t, size_t off, size_t k, int w, hipStream_t stream) {
+            const size_t a = first + off;
+            const Set& s = set[w];
+            const hipError_t e = sbv::launch_msg_frontend(s.msgs, s.moff, s.sigs, s.soff, k, reinterpret_cast<u32*>(s.recs), stream, moff[a], soff[a],
+                                                          (size_t)(moff[a + k] - moff[a]), (size_t)(soff[a + k] - soff[a]));
+            if (e != hipSuccess) return fail(SBV_EDEVICE, "verify_shard_msgs", e);
+            const int st = enqueue_keyed(c, s.recs, s.slots, k, d_slot + off / 8, stream, nullptr, w ? chunk : 0);
+            if (st == SBV_OK) launch_quorum(nullptr, s.slots, d_slot, d_qslot, off, k, group, quorum, stream);
+            return st;
+        });
 }
 
 }  // namespace
@@ -4423,7 +4319,7 @@ int sharded_by_key(const uint8_t* tuples, size_t n, size_t group, u32 quorum, ui
         int rc = grow_bytes(sbuf.d_q, sbuf.q_cap, (props + 7) / 8 + 64);
         if (rc != SBV_OK) return rc;
         if (!use_rccl) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(sbuf.d_gather, accept_bitmap, bytes, hipMemcpyHostToDevice, c0->stream));
-        hipLaunchKernelGGL(k_quorum_bits, dim3((unsigned)((props + 255) / 256)), dim3(256), 0, c0->stream, sbuf.d_full, sbuf.d_gather, props, (u32)group, quorum, sbuf.d_q);
+        launch_quorum(sbuf.d_full, nullptr, sbuf.d_gather, sbuf.d_q, 0, n, group, quorum, c0->stream);
         HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(quorum_bitmap, sbuf.d_q, (props + 7) / 8, hipMemcpyDeviceToHost, c0->stream));
         HIP_TRY(SBV_EDEVICE, hipStreamSynchronize(c0->stream));
     }
@@ -4541,90 +4437,81 @@ int sharded_contiguous(size_t n, size_t group, u32 quorum, uint8_t* accept_bitma
     }
     return SBV_OK;
 }
+
+// The start of the three sharded entries: info cleared, the arguments checked (`args`: the entry's own pointers; `bases`: the message
+// entry's second look at them, behind the quorum check), the clock started, g_reg_mu taken (shared) into *reg where the entry reads the
+// registry, and the devices and the collective snapshotted under g_mu.  SBV_OK with n == 0 means there is nothing to do.
+struct ShardedCall { std::vector<int> devs; bool use_rccl = false; std::chrono::steady_clock::time_point t0; };
+int sharded_begin(ShardedCall& sc, sbv_shard_info* info, size_t n, bool args, size_t group, u32 quorum, const uint8_t* quorum_bitmap,
+                  std::shared_lock<std::shared_mutex>* reg = nullptr, bool bases = true) {
+    if (info) memset(info, 0, sizeof *info);
+    if (n == 0) return SBV_OK;
+    if (!args) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (quorum_bitmap && (group == 0 || quorum == 0 || quorum > group || group > 64)) { g_err = "quorum bits need 0 < quorum <= group <= 64"; return SBV_EINVAL; }
+    if (!bases) { g_err = "null pointer"; return SBV_EINVAL; }
+    sc.t0 = std::chrono::steady_clock::now();
+    if (reg) *reg = std::shared_lock<std::shared_mutex>(g_reg_mu);     // the registry does not change under a call that replicates / reads it
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        sc.devs = g_devs;
+        if (sc.devs.empty() && g_def) sc.devs.push_back(g_def->device);        // sbv_init only: one device
+        sc.use_rccl = g_rccl.ready && g_rccl.comms.size() == sc.devs.size();   // the communicator spans exactly these devices
+    }
+    if (sc.devs.empty()) { g_err = "sbv_init_all / sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    return SBV_OK;
+}
 }  // namespace
 
 extern "C" int sbv_p256_verify_batch_sharded(const uint8_t* tuples, size_t n, size_t group, uint32_t quorum, uint8_t* accept_bitmap,
                                              uint8_t* quorum_bitmap, sbv_shard_info* info) {
-    if (info) memset(info, 0, sizeof *info);
-    if (n == 0) return SBV_OK;
-    if (!tuples || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
-    if (quorum_bitmap && (group == 0 || quorum == 0 || quorum > group || group > 64)) { g_err = "quorum bits need 0 < quorum <= group <= 64"; return SBV_EINVAL; }
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<int> devs;
-    bool use_rccl;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        devs = g_devs;
-        if (devs.empty() && g_def) devs.push_back(g_def->device);     // sbv_init only: one device
-        use_rccl = g_rccl.ready && g_rccl.comms.size() == devs.size();   // the communicator spans exactly these devices
-    }
-    if (devs.empty()) { g_err = "sbv_init_all / sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    ShardedCall sc;
+    const int rc = sharded_begin(sc, info, n, tuples && accept_bitmap, group, quorum, quorum_bitmap);
+    if (rc != SBV_OK || n == 0) return rc;
     if (g_shard_mode.load() == 1) {
         unsigned parts = g_shard_parts.load();
-        if (parts == 0) parts = (unsigned)devs.size();
-        if (parts > 1 && n >= parts) return sharded_by_key(tuples, n, group, quorum, accept_bitmap, quorum_bitmap, info, devs, parts, use_rccl);
+        if (parts == 0) parts = (unsigned)sc.devs.size();
+        if (parts > 1 && n >= parts) return sharded_by_key(tuples, n, group, quorum, accept_bitmap, quorum_bitmap, info, sc.devs, parts, sc.use_rccl);
     }
-    return sharded_contiguous(n, group, quorum, accept_bitmap, quorum_bitmap, info, devs, use_rccl, sbv_shard_min_for(tuples, n, group),
+    return sharded_contiguous(n, group, quorum, accept_bitmap, quorum_bitmap, info, sc.devs, sc.use_rccl, sbv_shard_min_for(tuples, n, group),
                               [&](Context& c, size_t first, size_t count, uint8_t* d_bits, uint8_t* d_q, double* h2d_us, double* kern_us) {
                                   return verify_shard(c, tuples + first * SBV_TUPLE_BYTES, count, group, quorum, d_bits, d_q, h2d_us, kern_us);
-                              }, t0);
+                              }, sc.t0);
 }
 
 // The registered-key form of the sharded entry (round 5; include/sbv.h): the same plan, pieces, quorum bits and collective over
 // 96-byte records + key slots, every device holding a replica of the registry and of the consenters' wide combs.
 extern "C" int sbv_p256_verify_batch_keyed_sharded(const uint8_t* rsh, const uint32_t* slots, size_t n, size_t group, uint32_t quorum,
                                                    uint8_t* accept_bitmap, uint8_t* quorum_bitmap, sbv_shard_info* info) {
-    if (info) memset(info, 0, sizeof *info);
-    if (n == 0) return SBV_OK;
-    if (!rsh || !slots || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
-    if (quorum_bitmap && (group == 0 || quorum == 0 || quorum > group || group > 64)) { g_err = "quorum bits need 0 < quorum <= group <= 64"; return SBV_EINVAL; }
-    const auto t0 = std::chrono::steady_clock::now();
-    std::shared_lock<std::shared_mutex> rl(g_reg_mu);        // the registry does not change under a call that replicates / reads it
-    std::vector<int> devs;
-    bool use_rccl;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        devs = g_devs;
-        if (devs.empty() && g_def) devs.push_back(g_def->device);
-        use_rccl = g_rccl.ready && g_rccl.comms.size() == devs.size();
-    }
-    if (devs.empty()) { g_err = "sbv_init_all / sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    ShardedCall sc;
+    std::shared_lock<std::shared_mutex> rl;
+    const int rc = sharded_begin(sc, info, n, rsh && slots && accept_bitmap, group, quorum, quorum_bitmap, &rl);
+    if (rc != SBV_OK || n == 0) return rc;
     if (g_reg.keys.empty()) { g_err = "no keys registered"; return SBV_EINVAL; }
     // nothing is built per batch on this path (the combs are resident), so the few-signers minimum applies whatever the registry holds
-    return sharded_contiguous(n, group, quorum, accept_bitmap, quorum_bitmap, info, devs, use_rccl, g_shard_min_env ? g_shard_min : g_shard_min_few,
+    return sharded_contiguous(n, group, quorum, accept_bitmap, quorum_bitmap, info, sc.devs, sc.use_rccl, g_shard_min_env ? g_shard_min : g_shard_min_few,
                               [&](Context& c, size_t first, size_t count, uint8_t* d_bits, uint8_t* d_q, double* h2d_us, double* kern_us) {
                                   return verify_shard_keyed(c, rsh + first * 96, slots + first, count, group, quorum, d_bits, d_q, h2d_us, kern_us);
-                              }, t0);
+                              }, sc.t0);
 }
 
 // Raw messages + DER signatures + key slots, sharded (SHA-256 and the DER parse on every device's share).
 extern "C" int sbv_p256_verify_msgs_keyed_sharded(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
                                                   const uint32_t* slots, size_t n, size_t group, uint32_t quorum, uint8_t* accept_bitmap,
                                                   uint8_t* quorum_bitmap, sbv_shard_info* info) {
-    if (info) memset(info, 0, sizeof *info);
-    if (n == 0) return SBV_OK;
-    if (!msg_offsets || !sig_offsets || !slots || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
-    if (quorum_bitmap && (group == 0 || quorum == 0 || quorum > group || group > 64)) { g_err = "quorum bits need 0 < quorum <= group <= 64"; return SBV_EINVAL; }
     // The offset tables must never decrease: the piece boundaries are checked on the host (verify_shard_msgs), every entry between them by
     // its lane on the device (k_msg_frontend: an entry out of order or outside the upload becomes an empty message + signature = reject).
     // They need NOT start at 0 here: msgs / sigs are the bases the offsets refer to (a slice of a larger batch's tables is a valid argument).
-    if ((msg_offsets[n] && !msgs) || (sig_offsets[n] && !sigs)) { g_err = "null pointer"; return SBV_EINVAL; }
-    const auto t0 = std::chrono::steady_clock::now();
-    std::shared_lock<std::shared_mutex> rl(g_reg_mu);
-    std::vector<int> devs;
-    bool use_rccl;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        devs = g_devs;
-        if (devs.empty() && g_def) devs.push_back(g_def->device);
-        use_rccl = g_rccl.ready && g_rccl.comms.size() == devs.size();
-    }
-    if (devs.empty()) { g_err = "sbv_init_all / sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    const bool tables = msg_offsets && sig_offsets && slots && accept_bitmap;
+    const bool bases = !tables || n == 0 || !((msg_offsets[n] && !msgs) || (sig_offsets[n] && !sigs));
+    ShardedCall sc;
+    std::shared_lock<std::shared_mutex> rl;
+    const int rc = sharded_begin(sc, info, n, tables, group, quorum, quorum_bitmap, &rl, bases);
+    if (rc != SBV_OK || n == 0) return rc;
     if (g_reg.keys.empty()) { g_err = "no keys registered"; return SBV_EINVAL; }
-    return sharded_contiguous(n, group, quorum, accept_bitmap, quorum_bitmap, info, devs, use_rccl, g_shard_min_env ? g_shard_min : g_shard_min_few,
+    return sharded_contiguous(n, group, quorum, accept_bitmap, quorum_bitmap, info, sc.devs, sc.use_rccl, g_shard_min_env ? g_shard_min : g_shard_min_few,
                               [&](Context& c, size_t first, size_t count, uint8_t* d_bits, uint8_t* d_q, double* h2d_us, double* kern_us) {
                                   return verify_shard_msgs(c, msgs, msg_offsets, sigs, sig_offsets, slots, first, count, group, quorum, d_bits, d_q, h2d_us, kern_us);
-                              }, t0);
+                              }, sc.t0);
 }
 
 extern "C" int sbv_p256_verify_batch_dev_part(const void* d_tuples, size_t n, uint32_t part, uint32_t parts, void* d_bitmap_words,
