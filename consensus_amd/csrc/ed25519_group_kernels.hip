@@ -39,12 +39,6 @@ static __device__ __forceinline__ void ed_chain_prio() {
 #endif
 }
 
-__global__ __launch_bounds__(256) void k_ed_group_insert(const uint8_t* __restrict__ tuples, size_t n, GroupState g) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    (void)i;
-    group_insert_block<128, 64, 8>(tuples, n, g);
-}
-
 // Same result as ed_group_split_lane (compaction: group_split_emit)
 __global__ __launch_bounds__(256) void k_ed_group_split(size_t n, GroupState g) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -194,16 +188,6 @@ __global__ __launch_bounds__(SBV_VERIFY_BLOCK, SBV_ED_GROUP_WAVES) void k_ed_qph
     const bool v = ed_qphase_wide_lane(tuples, t, kvalid[slot] != 0, wtab + (size_t)kwide[slot] * SBV_ED_HOT_COMB_BYTES, gacc, okb);
     acc[t] = v ? SBV_ED_PENDING : 0;
 }
-// Hot keys, per batch: the groups' tuple counts go to their cache slots' hit counters, and wide[k] = the slot owns a comb
-// (p256_group.h: group_hot_class_lane); counters[8] = how many such groups (0 = the wide pass has no wavefront)
-__global__ __launch_bounds__(256) void k_ed_hot_class(GroupState g, const u32* __restrict__ tslot, const uint8_t* __restrict__ cold, HotKeys hk,
-                                                      uint8_t* __restrict__ wide) {
-    const u32 groups = group_count(g);
-    for (u32 k = blockIdx.x * 256 + threadIdx.x; k < groups; k += gridDim.x * 256) {
-        group_hot_class_lane(k, g, tslot, cold, hk.cache_cap, hk.kwide, hk.khits, wide);
-        if (wide[k]) atomicAdd(&g.counters[8], 1u);
-    }
-}
 // The builder of this batch's promotions: lane (promotion i, window j, part) writes 32 entries of comb plist[2 i + 1] from the base point
 // the slot's 8-bit comb holds (ed25519_group.h: ed_widetab_lane).  A bounded grid walks the promotions' 16 x 1024 lanes each; scratch
 // is per resident lane.
@@ -254,47 +238,23 @@ hipError_t launch_ed25519_verify_grouped(const uint8_t* d_tuples, size_t n, cons
     // step, 3.33-3.35 / 3.38-3.42 against 3.20-3.23 warm (profiles/r04/ab_ed_chunks_r04o.jsonl)
     const int chunks = y.chunks < 1 ? 1 : (y.chunks > SBV_GROUP_MAX_CHUNKS ? SBV_GROUP_MAX_CHUNKS : y.chunks);
     const int parts = SBV_KEYTAB_PARTS_DEFAULT;     // lanes per (key, window) of the table kernel (2 / 4 / 8 / 16 measured in round 2)
-    hipError_t e;
-#define SBV_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
-    // ev_fork was recorded by the caller on `stream` before anything of this batch (see the P-256 launcher)
-    SBV_TRY(hipStreamWaitEvent(y.side_a, y.ev_fork, 0));
-    // the P-256 step's tail (table marks, promotion select: p256_group_kernels.hip) reads tslot / cold, which this scheme's grouping shares
-    SBV_TRY(hipStreamWaitEvent(y.side_a, y.ev_promoted, 0));
-    SBV_TRY(hipMemsetAsync(b.ht, 0, ((size_t)b.ht_mask + 1) * sizeof(u32), y.side_a));
-    SBV_TRY(hipMemsetAsync(b.cnt, 0, n * sizeof(u32), y.side_a));
-    SBV_TRY(hipMemsetAsync(b.counters, 0, SBV_GROUP_COUNTERS * sizeof(u32), y.side_a));
-    if (g.sorted) SBV_TRY(hipMemsetAsync(b.gcount, 0, (size_t)b.max_groups * sizeof(u32), y.side_a));
-    SBV_TRY(hipMemsetAsync(b.acc, 0, n, y.side_a));      // no stale "pending" marker can survive a batch that was cut short
+    // this scheme's comb pool: slots of aniels combs of -A; hot keys (ed25519_group.h) only with the class bytes that exist with the pool
+    const KeyPool& kp = eb.kp;
+    aniels* const ktab = static_cast<aniels*>(kp.ktab);
+    const u32 table_slots = kp.kc.cap + b.max_groups;
+    const HotPool& hp = kp.hp;
+    uint8_t* const wtab = static_cast<uint8_t*>(hp.wtab);
+    const GroupHot hot = group_hot_of(hp, kp.kc, g, kp.wide != nullptr, kp.wide);
+    const bool hot_on = hot.on;
+    const uint8_t* wide = hot.wide;
     const unsigned gn = (unsigned)((n + 255) / 256);
     const unsigned gv = (unsigned)((n + SBV_VERIFY_BLOCK - 1) / SBV_VERIFY_BLOCK);
-    hipLaunchKernelGGL(k_ed_group_insert, dim3(gn), dim3(256), 0, y.side_a, d_tuples, n, g);
-    hipLaunchKernelGGL((k_group_assign_t<128, 64, 8>), dim3(gn), dim3(256), 0, y.side_a, d_tuples, n, g, eb.kc);
-    SBV_TRY(hipEventRecord(y.ev_assign, y.side_a));
-    hipLaunchKernelGGL((k_key_cache_lookup_t<128, 64, 8>), dim3((b.max_groups + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, eb.kc, b.tslot, b.cold);
-    hipLaunchKernelGGL((k_key_cache_insert_t<128, 64, 8>), dim3((b.max_groups + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, eb.kc, b.tslot);
-    const u32 table_slots = eb.kc.cap + b.max_groups;
-    // hot keys (ed25519_group.h): only with the cache on, a pool to promote into and the key-sorted list
-    const HotPool& hp = eb.hp;
-    uint8_t* const wtab = static_cast<uint8_t*>(hp.wtab);
-    const bool hot_on = hp.wtab && hp.kwide && eb.wide && eb.kc.enabled && g.sorted;
-    const HotKeys hk = hot_view(hp, eb.kc, hot_on);
-    const uint8_t* wide = hot_on ? eb.wide : nullptr;
-    if (hot_on) SBV_TRY(hipEventRecord(y.ev_cache, y.side_a));         // table slots assigned: the class kernel (side_b) reads them
-    SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_assign, 0));
-    if (hot_on) SBV_TRY(hipMemsetAsync(hp.hot + 1, 0, 3 * sizeof(u32), y.side_b));       // behind the previous batch's builder, which reads hot[1]
-    if (g.sorted) {
-        const unsigned tiles = (unsigned)((n + SBV_SORT_TILE - 1) / SBV_SORT_TILE);
-        hipLaunchKernelGGL(k_group_classify, dim3(gn), dim3(256), 0, y.side_b, n, g, b.ung_cand, b.counters + 4);
-        hipLaunchKernelGGL(k_group_sort_count, dim3(tiles), dim3(1024), sort_lds, y.side_b, n, g);
-        hipLaunchKernelGGL(k_group_sort_scan, dim3(1), dim3(1024), 0, y.side_b, g);
-        hipLaunchKernelGGL(k_group_sort_scatter, dim3(tiles), dim3(1024), sort_lds, y.side_b, n, g);
-    } else {
-        hipLaunchKernelGGL(k_ed_group_split, dim3(gn), dim3(256), 0, y.side_b, n, g);
-    }
-    if (hot_on) {
-        SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_cache, 0));
-        hipLaunchKernelGGL(k_ed_hot_class, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, b.cold, hk, eb.wide);
-    }
+    // side_a: the head; acc is cleared too: no stale "pending" marker can survive a batch that was cut short
+    SBV_TRY((group_launch_head<128, 64, 8>(d_tuples, n, g, b, kp.kc, y, hot_on, b.acc)));
+    // side_b: no key check in front of the sort (it sits on side_a, below)
+    SBV_TRY(group_launch_split(n, g, b, hot, sort_lds, y, [] {}));
+    if (!g.sorted) hipLaunchKernelGGL(k_ed_group_split, dim3(gn), dim3(256), 0, y.side_b, n, g);
+    SBV_TRY(group_launch_hot_class(g, b, hot, y));
     SBV_TRY(hipEventRecord(y.ev_split, y.side_b));
     // stream: the G phase needs nothing but the tuples.  (Holding it back until the grouping's first kernels are through, so that the head
     // of the table pipeline does not share the CUs with it, was measured in round 6 and changes nothing: 3.84 against 3.81 ms cold.)
@@ -304,7 +264,7 @@ hipError_t launch_ed25519_verify_grouped(const uint8_t* d_tuples, size_t n, cons
     // side_a: the doubling chains of every chunk, then the ungrouped list
     for (int c = 0; c < chunks; ++c) {
         const int j_first = SBV_ED_KEY_WINDOWS * c / chunks, j_end = SBV_ED_KEY_WINDOWS * (c + 1) / chunks;
-        hipLaunchKernelGGL(k_ed_keytab_bases, dim3((b.max_groups * 4u + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, b.jbases, eb.kvalid,
+        hipLaunchKernelGGL(k_ed_keytab_bases, dim3((b.max_groups * 4u + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, b.jbases, kp.kvalid,
                            b.tslot, b.cold, j_first, j_end - 1);
         SBV_TRY(hipEventRecord(y.ev_bases[c], y.side_a));
     }
@@ -336,16 +296,16 @@ hipError_t launch_ed25519_verify_grouped(const uint8_t* d_tuples, size_t n, cons
         hipStream_t tb = y.side_b;      // one table stream: the windows of the odd chunks on a second stream measured slower (round 4: 4.55 -> 4.67 ms)
         SBV_TRY(hipStreamWaitEvent(tb, y.ev_bases[c], 0));
         const size_t wl = (size_t)b.max_groups * j_count * parts;
-        hipLaunchKernelGGL(k_ed_keytab_window, dim3((unsigned)((wl + 63) / 64)), dim3(64), 0, tb, g, b.jbases, b.tmp, eb.ktab,
+        hipLaunchKernelGGL(k_ed_keytab_window, dim3((unsigned)((wl + 63) / 64)), dim3(64), 0, tb, g, b.jbases, b.tmp, ktab,
                            b.tslot, b.cold, j_first, j_count, parts);
         SBV_TRY(hipEventRecord(y.ev_tables[c], tb));
         SBV_TRY(hipStreamWaitEvent(stream, y.ev_tables[c], 0));
         if (prof) SBV_TRY(hipEventRecord(prof[2 * c], stream));
-        if (!g.sorted) hipLaunchKernelGGL(k_ed_qphase_list, dim3(gv), dim3(SBV_VERIFY_BLOCK), 0, stream, d_tuples, g, eb.ktab, eb.kvalid, b.tslot, table_slots, b.gacc, b.gacc_cap,
+        if (!g.sorted) hipLaunchKernelGGL(k_ed_qphase_list, dim3(gv), dim3(SBV_VERIFY_BLOCK), 0, stream, d_tuples, g, ktab, kp.kvalid, b.tslot, table_slots, b.gacc, b.gacc_cap,
                                           eb.okb, b.acc, j_first, j_end, c + 1 == chunks ? 1 : 0);
-        else if (c + 1 == chunks) hipLaunchKernelGGL(k_ed_qphase<true>, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, d_tuples, g, eb.ktab, eb.kvalid, b.tslot, table_slots,
+        else if (c + 1 == chunks) hipLaunchKernelGGL(k_ed_qphase<true>, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, d_tuples, g, ktab, kp.kvalid, b.tslot, table_slots,
                                                      b.gacc, b.gacc_cap, eb.okb, b.acc, j_first, j_end, wide);
-        else hipLaunchKernelGGL(k_ed_qphase<false>, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, d_tuples, g, eb.ktab, eb.kvalid, b.tslot, table_slots,
+        else hipLaunchKernelGGL(k_ed_qphase<false>, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, stream, d_tuples, g, ktab, kp.kvalid, b.tslot, table_slots,
                                 b.gacc, b.gacc_cap, eb.okb, b.acc, j_first, j_end, wide);
         if (prof) SBV_TRY(hipEventRecord(prof[2 * c + 1], stream));
     }
@@ -356,7 +316,7 @@ hipError_t launch_ed25519_verify_grouped(const uint8_t* d_tuples, size_t n, cons
         // Like the first Q launch it lets the ungrouped list's key check go first.
         SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_class, 0));
         if (g.sorted && keycheck_first) SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_narrow, 0));
-        hipLaunchKernelGGL(k_ed_qphase_wide, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, y.side_b, d_tuples, g, eb.kvalid, b.tslot, wide, hp.kwide, wtab,
+        hipLaunchKernelGGL(k_ed_qphase_wide, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, y.side_b, d_tuples, g, kp.kvalid, b.tslot, wide, hp.kwide, wtab,
                            hp.hot + 2, b.gacc, eb.okb, b.acc);
         SBV_TRY(hipEventRecord(y.ev_wide, y.side_b));
         SBV_TRY(hipStreamWaitEvent(stream, y.ev_wide, 0));
@@ -365,21 +325,14 @@ hipError_t launch_ed25519_verify_grouped(const uint8_t* d_tuples, size_t n, cons
         const size_t fl = (n + SBV_ED_FINISH_T - 1) / SBV_ED_FINISH_T;
         hipLaunchKernelGGL(k_ed_finish, dim3((unsigned)((fl + 255) / 256)), dim3(256), 0, stream, d_tuples, n, b.gacc, b.gacc_cap, b.acc, (int)g.sorted);
     }
+    // the tail on side_b: in stream order behind this batch's table windows and its wide pass
+    SBV_TRY(group_launch_promote_select(g, b, kp.kvalid, hp, hot, y, false, [] {}));
     if (hot_on) {
-        // The tail on side_b, behind this batch's last table windows (the builder reads a promoted slot's 8-bit comb, which this very batch
-        // may have built) and behind the wide pass (an evicted comb is rewritten) — stream order: the clock sweep, which slots get a comb, the
-        // evictions; then — the next batch's side_a may rewrite tslot from here on — the combs themselves and their publication.
-        // The next batch's class kernel queues up behind all of it on this stream: a comb is used only once it is complete.
-        if (hp.hot_tick % SBV_HOT_DECAY_EVERY == SBV_HOT_DECAY_EVERY - 1) hipLaunchKernelGGL(k_hot_decay, dim3((eb.kc.cap + 255) / 256), dim3(256), 0, y.side_b, hk);
-        hipLaunchKernelGGL(k_promote_select, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, eb.kvalid, hk);
-        hipLaunchKernelGGL(k_promote_evict, dim3(1), dim3(1024), 0, y.side_b, hk);
-        SBV_TRY(hipEventRecord(y.ev_promoted, y.side_b));
-        hipLaunchKernelGGL(k_ed_promote_window, dim3(SBV_ED_HOT_BUILD_BLOCKS), dim3(64), 0, y.side_b, hp.plist, hp.hot, eb.ktab, hp.ptmp, wtab);
-        hipLaunchKernelGGL(k_promote_publish, dim3(1), dim3(64), 0, y.side_b, hp.plist, hp.hot, hp.kwide, hp.wowner);
+        hipLaunchKernelGGL(k_ed_promote_window, dim3(SBV_ED_HOT_BUILD_BLOCKS), dim3(64), 0, y.side_b, hp.plist, hp.hot, ktab, hp.ptmp, wtab);
+        group_launch_promote_publish(hp, y);
     }
     SBV_TRY(hipStreamWaitEvent(stream, y.ev_generic, 0));
     hipLaunchKernelGGL(k_pack_bitmap, dim3((unsigned)(((n + 7) / 8 + 255) / 256)), dim3(256), 0, stream, b.acc, n, d_bitmap);
-#undef SBV_TRY
     if (prof && prof_pairs) *prof_pairs = chunks;
     return hipGetLastError();
 }

@@ -9,20 +9,15 @@ hipError_t launch_ed25519_verify(const uint8_t* d_tuples, size_t n, u32* d_qtab,
                                  hipStream_t stream);
 // device buffers of the Ed25519 grouped step that the P-256 GroupBuffers do not already provide
 struct EdGroupBuffers {
-    aniels* ktab = nullptr;       // [kc.cap + max_groups][32 x 128] combs of -A: slots [0, kc.cap) = this scheme's persistent key-table
-                                  // cache (round 4), [kc.cap, kc.cap + max_groups) = per batch
+    // This scheme's comb pool.  ktab: aniels [kc.cap + max_groups][32 x 128] combs of -A; kc is keyed by the 32 key bytes (padded to the
+    // cache's 16 words).  kvalid (1 = the slot's key decompressed) is NOT GroupBuffers::kvalid: bytes [0, kc.cap) of that array belong to
+    // the P-256 key-table cache and outlive the batch — an Ed25519 batch writing its own group verdicts there invalidated cached P-256
+    // keys (found in round 3 by test order).  Hot keys (ed25519_group.h, round 6): combs of -A, SBV_ED_HOT_COMB_BYTES each (16 x 32 768
+    // entries at a 128-byte pitch); ptmp = SBV_ED_HOT_TMP_WORDS per resident lane of the builder.
+    KeyPool kp;
     uint8_t* okb = nullptr;       // [cap] S < L && k < L
     u32* ungxy = nullptr;         // [cap][20] X | Y of the ungrouped list's keys, left by the key check for the quad form of the one-lane kernel
-    uint8_t* kvalid = nullptr;    // [kc.cap + max_groups] 1 = the slot's key decompressed.  NOT GroupBuffers::kvalid: bytes [0, kc.cap) of
-                                  // that array belong to the P-256 key-table cache and outlive the batch — an Ed25519 batch writing
-                                  // its own group verdicts there invalidated cached P-256 keys (found in round 3 by test order)
-    KeyCache kc = {};             // keyed by the 32 key bytes (padded to the cache's 16 words)
     size_t cap = 0;
-    u32 max_groups = 0;
-    // hot keys of this scheme (ed25519_group.h, round 6): combs of -A, SBV_ED_HOT_COMB_BYTES each (16 x 32 768 entries at a 128-byte
-    // pitch); ptmp = SBV_ED_HOT_TMP_WORDS per resident lane of the builder
-    HotPool hp;
-    uint8_t* wide = nullptr;      // [max_groups] this batch's groups whose slot owns a comb.  Here, not in HotPool: per batch; it exists only with the pool
 };
 // Grouped step (ed25519_group.h).  `b` supplies the grouping arrays, jbases, tmp, acc and gacc (32 words per
 // tuple, stride b.gacc_cap); ev_fork of `y` must have been recorded on `stream` before the call.

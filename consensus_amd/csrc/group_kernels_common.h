@@ -1,9 +1,13 @@
-// group_kernels_common.h — the curve-independent kernels of the in-step key grouping, shared by the P-256 and
-// the Ed25519 pipelines (each translation unit gets its own static copy; no relocatable device code needed).
+// group_kernels_common.h — what the grouped steps of the three schemes (P-256, Ed25519, secp256k1) share: the curve-independent
+// kernels of the in-step key grouping (each translation unit gets its own static copy; no relocatable device code needed) and, at
+// the end of the file, the pieces of the three-stream schedule that every launcher runs — the head on side_a, the split and sort
+// on side_b, the hot-key class launch and the promotion tail.  A launcher holds its curve's kernels and its own schedule between
+// those pieces.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "p256_group.h"
+#include "p256_kernels.h"
 
 namespace sbv {
 
@@ -19,6 +23,7 @@ __device__ __forceinline__ u32 group_count(const GroupState& g) {
 // stage A 1.43 ms of a 3.2 ms call (profiles/r06/kernel_stats_replay_r06l.csv).  Now: the lanes of a wavefront that share a
 // representative elect a leader (ballot / readlane loop, one round per distinct representative), the leaders meet in a 512-entry
 // LDS table keyed by the representative, and the workgroup flushes one atomic per distinct representative.
+// STRIDE / OFF / WORDS = the tuple format's key location (p256_group.h: group_insert_lane_t): <160, 96, 16> P-256 and secp256k1, <128, 64, 8> Ed25519
 template <int STRIDE, int OFF, int WORDS>
 static __device__ __forceinline__ void group_insert_block(const uint8_t* __restrict__ tuples, size_t n, const GroupState& g) {
     __shared__ u32 skey[512], scnt[512];
@@ -64,17 +69,17 @@ static __device__ __forceinline__ void group_insert_block(const uint8_t* __restr
     for (unsigned t = tid; t < 512; t += blockDim.x)
         if (skey[t] != 0xFFFFFFFFu) atomicAdd(&g.cnt[skey[t]], scnt[t]);
 }
+template <int STRIDE, int OFF, int WORDS>
+static __global__ __launch_bounds__(256) void k_group_insert_t(const uint8_t* __restrict__ tuples, size_t n, GroupState g) {
+    group_insert_block<STRIDE, OFF, WORDS>(tuples, n, g);
+}
 
 // kc: the scheme's persistent key-table cache (kc.enabled = 0 when it is off): cached keys are grouped whatever their count
-// in this batch.  STRIDE / OFF / WORDS = the tuple format's key location (p256_group.h: group_insert_lane_t)
+// in this batch
 template <int STRIDE, int OFF, int WORDS>
 static __global__ __launch_bounds__(256) void k_group_assign_t(const uint8_t* __restrict__ tuples, size_t n, GroupState g, KeyCache kc) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) group_assign_lane_t<STRIDE, OFF, WORDS>(tuples, i, g, kc);
-}
-static __global__ __launch_bounds__(256) void k_group_assign(const uint8_t* __restrict__ tuples, size_t n, GroupState g, KeyCache kc) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) group_assign_lane(tuples, i, g, kc);
 }
 
 // Every group of the batch finds its table slot (p256_group.h: persistent key-table cache), in two small launches of
@@ -104,6 +109,17 @@ struct HotKeys { const void* wtab; u32* kwide; u32* khits; u32* hot; u32* plist;
 // the kernels' view of a scheme's pool `p` over the slots of its cache `kc`; hot_on = this batch uses it (each launcher's own conditions)
 inline HotKeys hot_view(const HotPool& p, const KeyCache& kc, bool hot_on) {
     return {p.wtab, hot_on ? p.kwide : nullptr, p.khits, p.hot, p.plist, kc.cap, p.wide_cap, p.promote_min, p.wowner, p.elist};
+}
+// Per batch (Ed25519, secp256k1; the P-256 step's k_group_table_class does this among its other classes): the groups' tuple counts go
+// to their cache slots' hit counters, and wide[k] = the slot owns a comb and is not being built in this batch (p256_group.h:
+// group_hot_class_lane); counters[8] = how many such groups (0 = the wide pass has no wavefront)
+static __global__ __launch_bounds__(256) void k_group_hot_class(GroupState g, const u32* __restrict__ tslot, const uint8_t* __restrict__ cold, HotKeys hk,
+                                                                uint8_t* __restrict__ wide) {
+    const u32 groups = group_count(g);
+    for (u32 k = blockIdx.x * 256 + threadIdx.x; k < groups; k += gridDim.x * 256) {
+        group_hot_class_lane(k, g, tslot, cold, hk.cache_cap, hk.kwide, hk.khits, wide);
+        if (wide[k]) atomicAdd(&g.counters[8], 1u);
+    }
 }
 static __device__ __forceinline__ u32 promote_live(const u32* hot) { const u32 c = hot[1]; return c < SBV_PROMOTE_MAX ? c : SBV_PROMOTE_MAX; }
 // Life cycle of the hot keys (p256_group.h, round 6): the clock sweep and the evictions.
@@ -344,6 +360,100 @@ static __global__ __launch_bounds__(1024) void k_group_sort_scatter(size_t n, Gr
         g.grp_idx[L] = (u32)(base + (size_t)q * 1024 + threadIdx.x);
         g.grp_of[L] = grp[q];
     }
+}
+
+// ---- the launchers' shared pieces -----------------------------------------------------------------------------------------------------
+// A grouped launcher (launch_p256_verify_grouped, launch_ed25519_verify_grouped, launch_k256_verify_grouped) is a three-stream schedule:
+// the caller's `stream` and GroupSync's side_a and side_b.  The pieces below are the parts of it that do not depend on the curve; each
+// enqueues on the stream its name says and returns the first error, like SBV_TRY in the launchers.  The grouping arrays (GroupBuffers)
+// are shared by the three schemes and by consecutive batches, so the order is the same for all of them:
+//   * ev_fork (recorded by the caller on `stream` in front of the batch) keeps the side streams off the group buffers until everything
+//     already enqueued on `stream` — the previous batch's readers — has run;
+//   * ev_promoted keeps side_a, which rewrites tslot / cold / the class bytes, behind the previous batch's tail on side_b — whichever
+//     scheme's it was (an event never recorded yet waits for nothing);
+//   * hot[1..3] (promotions, wide-pass lanes and eviction candidates of THIS batch) are reset on side_b: in stream order behind the
+//     previous batch's builder, which reads hot[1];
+//   * the tail runs on side_b behind the batch's last table windows (the builder reads a promoted slot's 8-bit comb, which this very
+//     batch may have built) and behind its wide pass (an evicted comb is rewritten): the clock sweep, which slots get a comb, the
+//     evictions — the last readers of tslot, hence ev_promoted HERE, from where the next batch's side_a may rewrite it — then the combs
+//     themselves and their publication.  The next batch's class kernel queues up behind all of it on side_b: a comb is used only once
+//     it is complete.
+#define SBV_TRY(x) do { const hipError_t sbv_try_e = (x); if (sbv_try_e != hipSuccess) return sbv_try_e; } while (0)
+
+// Hot keys of one batch: on = the batch uses the scheme's pool — only with a pool to promote into, the cache on, the key-sorted list
+// and the scheme's own conditions (`extra`); hk = the kernels' view; wide = the batch's class bytes, null when off
+struct GroupHot { bool on; HotKeys hk; uint8_t* wide; };
+static inline GroupHot group_hot_of(const HotPool& hp, const KeyCache& kc, const GroupState& g, bool extra = true, uint8_t* wide = nullptr) {
+    const bool on = hp.wtab && hp.kwide && extra && kc.enabled && g.sorted;
+    return {on, hot_view(hp, kc, on), on ? wide : nullptr};
+}
+
+// The head on side_a: the grouping (insert, assign -> ev_assign) and the table slots of the batch's groups (cache lookup and insert ->
+// ev_cache if record_cache: somebody on side_b reads tslot / cold).  also_clear (n bytes, may be null): a per-tuple array of the scheme
+// that has to be zero before the batch.
+template <int STRIDE, int OFF, int WORDS>
+static inline hipError_t group_launch_head(const uint8_t* d_tuples, size_t n, const GroupState& g, const GroupBuffers& b, const KeyCache& kc, const GroupSync& y,
+                                    bool record_cache, uint8_t* also_clear = nullptr) {
+    SBV_TRY(hipStreamWaitEvent(y.side_a, y.ev_fork, 0));
+    SBV_TRY(hipStreamWaitEvent(y.side_a, y.ev_promoted, 0));
+    SBV_TRY(hipMemsetAsync(b.ht, 0, ((size_t)b.ht_mask + 1) * sizeof(u32), y.side_a));
+    SBV_TRY(hipMemsetAsync(b.cnt, 0, n * sizeof(u32), y.side_a));
+    SBV_TRY(hipMemsetAsync(b.counters, 0, SBV_GROUP_COUNTERS * sizeof(u32), y.side_a));
+    if (g.sorted) SBV_TRY(hipMemsetAsync(b.gcount, 0, (size_t)b.max_groups * sizeof(u32), y.side_a));
+    if (also_clear) SBV_TRY(hipMemsetAsync(also_clear, 0, n, y.side_a));
+    const unsigned gn = (unsigned)((n + 255) / 256), gk = (b.max_groups + 63) / 64;
+    hipLaunchKernelGGL((k_group_insert_t<STRIDE, OFF, WORDS>), dim3(gn), dim3(256), 0, y.side_a, d_tuples, n, g);
+    hipLaunchKernelGGL((k_group_assign_t<STRIDE, OFF, WORDS>), dim3(gn), dim3(256), 0, y.side_a, d_tuples, n, g, kc);
+    SBV_TRY(hipEventRecord(y.ev_assign, y.side_a));
+    hipLaunchKernelGGL((k_key_cache_lookup_t<STRIDE, OFF, WORDS>), dim3(gk), dim3(64), 0, y.side_a, d_tuples, g, kc, b.tslot, b.cold);
+    hipLaunchKernelGGL((k_key_cache_insert_t<STRIDE, OFF, WORDS>), dim3(gk), dim3(64), 0, y.side_a, d_tuples, g, kc, b.tslot);
+    if (record_cache) SBV_TRY(hipEventRecord(y.ev_cache, y.side_a));
+    return hipSuccess;
+}
+
+// side_b behind the assignment: the reset of hot[1..3] and, for the key-sorted list, classify, the scheme's key check where it has one
+// here (`keycheck` launches it on side_b: P-256, secp256k1), and the counting sort by key.  Without the sorted list the launcher's own
+// split kernel follows.  sort_lds: one LDS word per group the histogram may hold.
+template <class KeyCheck>
+static inline hipError_t group_launch_split(size_t n, const GroupState& g, const GroupBuffers& b, const GroupHot& hot, size_t sort_lds, const GroupSync& y, KeyCheck keycheck) {
+    SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_assign, 0));
+    if (hot.on) SBV_TRY(hipMemsetAsync(hot.hk.hot + 1, 0, 3 * sizeof(u32), y.side_b));
+    if (!g.sorted) return hipSuccess;
+    const unsigned gn = (unsigned)((n + 255) / 256), tiles = (unsigned)((n + SBV_SORT_TILE - 1) / SBV_SORT_TILE);
+    hipLaunchKernelGGL(k_group_classify, dim3(gn), dim3(256), 0, y.side_b, n, g, b.ung_cand, b.counters + 4);
+    keycheck();
+    hipLaunchKernelGGL(k_group_sort_count, dim3(tiles), dim3(1024), sort_lds, y.side_b, n, g);
+    hipLaunchKernelGGL(k_group_sort_scan, dim3(1), dim3(1024), 0, y.side_b, g);
+    hipLaunchKernelGGL(k_group_sort_scatter, dim3(tiles), dim3(1024), sort_lds, y.side_b, n, g);
+    return hipSuccess;
+}
+
+// side_b, Ed25519 and secp256k1: the hot-key classes of the batch's groups, once the cache has assigned their slots
+static inline hipError_t group_launch_hot_class(const GroupState& g, const GroupBuffers& b, const GroupHot& hot, const GroupSync& y) {
+    if (!hot.on) return hipSuccess;
+    SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_cache, 0));
+    hipLaunchKernelGGL(k_group_hot_class, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, b.cold, hot.hk, hot.wide);
+    return hipSuccess;
+}
+
+// The tail on side_b, first half: the clock sweep every SBV_HOT_DECAY_EVERY-th batch, which slots get a comb, the evictions when the pool
+// is full, whatever else of the scheme still reads tslot or the per-batch tables (`before_record`: the P-256 builder's base points), and
+// ev_promoted — also without hot keys where the scheme's tail reads tslot regardless (always_record: the P-256 table marks).
+template <class BeforeRecord>
+static inline hipError_t group_launch_promote_select(const GroupState& g, const GroupBuffers& b, const uint8_t* kvalid, const HotPool& hp, const GroupHot& hot,
+                                              const GroupSync& y, bool always_record, BeforeRecord before_record) {
+    if (hot.on) {
+        if (hp.hot_tick % SBV_HOT_DECAY_EVERY == SBV_HOT_DECAY_EVERY - 1) hipLaunchKernelGGL(k_hot_decay, dim3((hot.hk.cache_cap + 255) / 256), dim3(256), 0, y.side_b, hot.hk);
+        hipLaunchKernelGGL(k_promote_select, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, kvalid, hot.hk);
+        hipLaunchKernelGGL(k_promote_evict, dim3(1), dim3(1024), 0, y.side_b, hot.hk);
+        before_record();
+    }
+    if (hot.on || always_record) SBV_TRY(hipEventRecord(y.ev_promoted, y.side_b));
+    return hipSuccess;
+}
+// ... second half, behind the scheme's builder: later batches find the new combs
+static inline void group_launch_promote_publish(const HotPool& hp, const GroupSync& y) {
+    hipLaunchKernelGGL(k_promote_publish, dim3(1), dim3(64), 0, y.side_b, hp.plist, hp.hot, hp.kwide, hp.wowner);
 }
 
 }  // namespace sbv

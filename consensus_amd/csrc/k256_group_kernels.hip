@@ -36,9 +36,6 @@ __global__ __launch_bounds__(64) void k_k256_prep_chunk(const uint8_t* __restric
     auto words = [&](size_t idx) { return KGlobalTupleG{reinterpret_cast<const u32*>(tuples + idx * 160)}; };
     k256_prep_chunk(words, n, s, first, (size_t)64, T);
 }
-__global__ __launch_bounds__(256) void k_k256_group_insert(const uint8_t* __restrict__ tuples, size_t n, GroupState g) {
-    group_insert_block<160, 96, 16>(tuples, n, g);
-}
 __global__ __launch_bounds__(256) void k_k256_keycheck(const uint8_t* __restrict__ tuples, GroupState g, uint8_t* __restrict__ acc) {
     const u32 L = blockIdx.x * 256 + threadIdx.x;
     const u32 cands = g.counters[4];
@@ -165,16 +162,6 @@ __global__ __launch_bounds__(SBV_VERIFY_BLOCK, 2) void k_k256_qphase_wide(Scratc
     const kgcomb wc = {wtab + (size_t)w * SBV_K256_WIDE_ENTRIES, SBV_K256_WIDE_BITS, SBV_K256_WIDE_WINDOWS};
     acc[t] = k256_qphase_wide_lane(s, t, L, live, wc, gacc) ? 1 : 0;
 }
-// Hot keys, per batch: the groups' tuple counts go to their cache slots' hit counters, and wide[k] = the slot owns a comb and is not
-// being built in this batch (p256_group.h: group_hot_class_lane); counters[8] = how many such groups (0 = the wide pass has no wavefront)
-__global__ __launch_bounds__(256) void k_k256_hot_class(GroupState g, const u32* __restrict__ tslot, const uint8_t* __restrict__ cold, HotKeys hk,
-                                                        uint8_t* __restrict__ wide) {
-    const u32 groups = group_count(g);
-    for (u32 k = blockIdx.x * 256 + threadIdx.x; k < groups; k += gridDim.x * 256) {
-        group_hot_class_lane(k, g, tslot, cold, hk.cache_cap, hk.kwide, hk.khits, wide);
-        if (wide[k]) atomicAdd(&g.counters[8], 1u);
-    }
-}
 // The builder of this batch's promotions: lane (promotion i, builder lane) writes one run of comb plist[2 i + 1] from the promoted cache
 // slot's 8-bit comb (k256_keyed.h: k256_widetab_lane).  A bounded grid walks promote_live x SBV_K256_WIDE_LANES items; scratch is per
 // lane of the grid.
@@ -205,46 +192,22 @@ hipError_t launch_k256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
     kapt* ktab = reinterpret_cast<kapt*>(kp.ktab);
     uint8_t* kvalid = kp.kvalid;
     const u32 table_slots = kp.kc.cap + b.max_groups;
-    hipError_t e;
-#define SBV_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
-    SBV_TRY(hipStreamWaitEvent(y.side_a, y.ev_fork, 0));
-    // the P-256 step's tail (table marks, promotion select: p256_group_kernels.hip) reads tslot / cold, which this scheme's grouping shares
-    SBV_TRY(hipStreamWaitEvent(y.side_a, y.ev_promoted, 0));
-    SBV_TRY(hipMemsetAsync(b.ht, 0, ((size_t)b.ht_mask + 1) * sizeof(u32), y.side_a));
-    SBV_TRY(hipMemsetAsync(b.cnt, 0, n * sizeof(u32), y.side_a));
-    SBV_TRY(hipMemsetAsync(b.counters, 0, SBV_GROUP_COUNTERS * sizeof(u32), y.side_a));
-    SBV_TRY(hipMemsetAsync(b.gcount, 0, (size_t)b.max_groups * sizeof(u32), y.side_a));
-    const unsigned gn = (unsigned)((n + 255) / 256);
-    const unsigned gv = (unsigned)((n + SBV_VERIFY_BLOCK - 1) / SBV_VERIFY_BLOCK);
-    hipLaunchKernelGGL(k_k256_group_insert, dim3(gn), dim3(256), 0, y.side_a, d_tuples, n, g);
-    hipLaunchKernelGGL(k_group_assign, dim3(gn), dim3(256), 0, y.side_a, d_tuples, n, g, kp.kc);
-    SBV_TRY(hipEventRecord(y.ev_assign, y.side_a));
-    hipLaunchKernelGGL((k_key_cache_lookup_t<160, 96, 16>), dim3((b.max_groups + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, kp.kc, b.tslot, b.cold);
-    hipLaunchKernelGGL((k_key_cache_insert_t<160, 96, 16>), dim3((b.max_groups + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, kp.kc, b.tslot);
-    // hot keys (k256_group.h): only with a pool to promote into, the cache on and the key-sorted list — the Ed25519 launcher's conditions
+    // hot keys (k256_group.h): only with the class bytes and the builder's grid, which exist with the pool
     const HotPool& hp = kp.hp;
     kapt* const wtab = static_cast<kapt*>(hp.wtab);
-    const bool hot_on = hp.wtab && hp.kwide && kp.wide && kp.build_blocks && kp.kc.enabled && g.sorted;
-    const HotKeys hk = hot_view(hp, kp.kc, hot_on);
-    const uint8_t* wide = hot_on ? kp.wide : nullptr;
-    if (hot_on) SBV_TRY(hipEventRecord(y.ev_cache, y.side_a));         // table slots assigned: the class kernel (side_b) reads them
+    const GroupHot hot = group_hot_of(hp, kp.kc, g, kp.wide && kp.build_blocks, kp.wide);
+    const bool hot_on = hot.on;
+    const uint8_t* wide = hot.wide;
+    const unsigned gn = (unsigned)((n + 255) / 256);
+    const unsigned gv = (unsigned)((n + SBV_VERIFY_BLOCK - 1) / SBV_VERIFY_BLOCK);
+    SBV_TRY((group_launch_head<160, 96, 16>(d_tuples, n, g, b, kp.kc, y, hot_on)));
     {   // stage A: SBV_K256_PREP_T tuples per lane share one inversion (Montgomery's trick).  Measured in round 4
         // (profiles/r04/ab_k256_prep_t_r04a.jsonl): 1 / 4 / 8 tuples per inversion 4.97 / 4.79 / 4.68 ms per 2^20 step.
         const size_t per_block = (size_t)64 * SBV_K256_PREP_T;
         hipLaunchKernelGGL(k_k256_prep_chunk, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(64), 0, stream, d_tuples, n, s, SBV_K256_PREP_T);
     }
-    SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_assign, 0));
-    if (hot_on) SBV_TRY(hipMemsetAsync(hp.hot + 1, 0, 3 * sizeof(u32), y.side_b));       // behind the previous batch's builder, which reads hot[1]
-    hipLaunchKernelGGL(k_group_classify, dim3(gn), dim3(256), 0, y.side_b, n, g, b.ung_cand, b.counters + 4);
-    hipLaunchKernelGGL(k_k256_keycheck, dim3(gn), dim3(256), 0, y.side_b, d_tuples, g, b.acc);
-    const unsigned tiles = (unsigned)((n + SBV_SORT_TILE - 1) / SBV_SORT_TILE);
-    hipLaunchKernelGGL(k_group_sort_count, dim3(tiles), dim3(1024), sort_lds, y.side_b, n, g);
-    hipLaunchKernelGGL(k_group_sort_scan, dim3(1), dim3(1024), 0, y.side_b, g);
-    hipLaunchKernelGGL(k_group_sort_scatter, dim3(tiles), dim3(1024), sort_lds, y.side_b, n, g);
-    if (hot_on) {
-        SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_cache, 0));
-        hipLaunchKernelGGL(k_k256_hot_class, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, b.cold, hk, kp.wide);
-    }
+    SBV_TRY(group_launch_split(n, g, b, hot, sort_lds, y, [&] { hipLaunchKernelGGL(k_k256_keycheck, dim3(gn), dim3(256), 0, y.side_b, d_tuples, g, b.acc); }));
+    SBV_TRY(group_launch_hot_class(g, b, hot, y));
     SBV_TRY(hipEventRecord(y.ev_split, y.side_b));
     SBV_TRY(hipStreamWaitEvent(stream, y.ev_split, 0));
     hipLaunchKernelGGL(k_k256_gphase_generic, dim3(2 * gv), dim3(SBV_VERIFY_BLOCK), 0, stream, s, g, d_qtab, d_gtab, kgcomb_make(d_gcomb, gcomb_bits), b.gacc, b.acc, gv);
@@ -267,29 +230,23 @@ hipError_t launch_k256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
         if (prof) SBV_TRY(hipEventRecord(prof[2 * c + 1], stream));
     }
     if (hot_on) {
-        // The wide pass, on side_b behind the G phase and the class kernel and beside the chunks' launches: it needs no table (ed25519_group_kernels.hip
-        // says why not on `stream` in front of them).  Then the tail, still on side_b: behind this batch's last table windows — those built on
-        // side_t too: the builder reads a promoted slot's 8-bit comb, which this very batch may have built — and behind the wide pass (an
-        // evicted comb is rewritten).  Stream order: the clock sweep, which slots get a comb, the evictions; then — the next batch's side_a may
-        // rewrite tslot from here on — the combs themselves and their publication.  The next batch's class kernel queues up behind all of it
-        // on this stream: a comb is used only once it is complete.  (The wave rule reads the valid byte of every lane's slot, a cold group's
-        // included: chunk 0's chain writes those, and side_b has waited for it in front of chunk 0's rows — both Q kernels see them final.)
+        // The wide pass, on side_b behind the G phase and the class kernel and beside the chunks' launches: it needs no table (on `stream` in
+        // front of them a batch with SOME hot signers runs three launches in a row, each over a part of the lanes: measured on the Ed25519
+        // step).  (The wave rule reads the valid byte of every lane's slot, a cold group's included: chunk 0's chain writes those, and side_b
+        // has waited for it in front of chunk 0's rows — both Q kernels see them final.)
         SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_class, 0));
         hipLaunchKernelGGL(k_k256_qphase_wide, dim3((gv + 7u) & ~7u), dim3(SBV_VERIFY_BLOCK), 0, y.side_b, s, g, kvalid, b.tslot, table_slots, wide, hp.kwide,
                            wtab, hp.wide_cap, hp.hot + 2, b.gacc, b.acc);
         SBV_TRY(hipEventRecord(y.ev_wide, y.side_b));
         SBV_TRY(hipStreamWaitEvent(stream, y.ev_wide, 0));
+        // the tail: side_b must also wait for the table windows that were built on side_t
         for (int c = 0; c < chunks; ++c) SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_tables[c], 0));
-        if (hp.hot_tick % SBV_HOT_DECAY_EVERY == SBV_HOT_DECAY_EVERY - 1) hipLaunchKernelGGL(k_hot_decay, dim3((kp.kc.cap + 255) / 256), dim3(256), 0, y.side_b, hk);
-        hipLaunchKernelGGL(k_promote_select, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, kvalid, hk);
-        hipLaunchKernelGGL(k_promote_evict, dim3(1), dim3(1024), 0, y.side_b, hk);
-        SBV_TRY(hipEventRecord(y.ev_promoted, y.side_b));
+        SBV_TRY(group_launch_promote_select(g, b, kvalid, hp, hot, y, false, [] {}));
         hipLaunchKernelGGL(k_k256_promote_build, dim3(kp.build_blocks), dim3(64), 0, y.side_b, hp.plist, hp.hot, ktab, kp.kc.cap, hp.ptmp,
                            wtab, hp.wide_cap);
-        hipLaunchKernelGGL(k_promote_publish, dim3(1), dim3(64), 0, y.side_b, hp.plist, hp.hot, hp.kwide, hp.wowner);
+        group_launch_promote_publish(hp, y);
     }
     hipLaunchKernelGGL(k_pack_bitmap, dim3((unsigned)(((n + 7) / 8 + 255) / 256)), dim3(256), 0, stream, b.acc, n, d_bitmap);
-#undef SBV_TRY
     if (prof && prof_pairs) *prof_pairs = chunks;
     return hipGetLastError();
 }

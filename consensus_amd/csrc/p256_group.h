@@ -147,7 +147,7 @@ SBV_HD bool tuple_key_ok(const uint8_t* tuples, size_t idx) {
 // P-256: 160 / 96 / 16 (Qx|Qy); Ed25519: 128 / 64 / 8 (A_enc).
 // group_find_rep_t: the representative of tuple i's key (claims the hash-table entry when the key is new) -> g.rep[i]; the caller
 // counts the tuple: group_insert_lane_t one atomic per tuple (the emulator; any caller without a workgroup), the kernels through
-// group_count_block (group_kernels_common.h: aggregated per workgroup — a consenter batch puts 34 000 tuples on each of 16 counters).
+// k_group_insert_t (group_kernels_common.h: aggregated per workgroup — a consenter batch puts 34 000 tuples on each of 16 counters).
 template <int STRIDE, int OFF, int WORDS>
 SBV_HD u32 group_find_rep_t(const uint8_t* tuples, size_t i, const GroupState& g) {
     const u32* k = reinterpret_cast<const u32*>(tuples + i * STRIDE + OFF);

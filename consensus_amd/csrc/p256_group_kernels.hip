@@ -1,7 +1,7 @@
 // p256_group_kernels.hip — kernels for grouping a generic batch by public key inside the step
 // (p256_group.h) and for running stage B over the two compacted index lists.
 //
-//   k_group_insert / k_group_assign / k_group_split : one lane per tuple; global atomics only
+//   k_group_insert_t / k_group_assign_t (group_kernels_common.h) / k_group_split : one lane per tuple; global atomics only
 //   k_keytab_bases   : one lane per grouped key  (256 doublings: the latency floor of a fresh key), in chunks of windows
 //   k_keytab_window  : a few lanes per (key, window): additions + Montgomery-trick normalisation each,
 //                      Jacobian intermediates parked in a private strip of HBM
@@ -40,9 +40,6 @@
 
 namespace sbv {
 
-__global__ __launch_bounds__(256) void k_group_insert(const uint8_t* __restrict__ tuples, size_t n, GroupState g) {
-    group_insert_block<160, 96, 16>(tuples, n, g);
-}
 // Same result as group_split_lane (compaction: group_split_emit)
 __global__ __launch_bounds__(256) void k_group_split(const uint8_t* __restrict__ tuples, size_t n, GroupState g, uint8_t* __restrict__ acc) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -591,50 +588,23 @@ hipError_t launch_p256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
     // hot keys (p256_group.h): only with the cache on, a pool to promote into and the key-sorted list
     const HotPool& hp = b.hp;
     apt* const wtab = static_cast<apt*>(hp.wtab);
-    const bool hot_on = hp.wtab && hp.kwide && b.kc.enabled && g.sorted;
-    const HotKeys hk = hot_view(hp, b.kc, hot_on);
+    const GroupHot hot = group_hot_of(hp, b.kc, g);
+    const bool hot_on = hot.on;
+    const HotKeys& hk = hot.hk;
     const widekeys wk = hot_on ? widekeys_make(wtab, hp.kwide, SBV_HOT_BITS) : widekeys_none();
     static const bool q_lds = [] { const char* v = getenv("SBV_QPHASE_LDS"); return v && v[0] == '1'; }();      // the LDS-staged form of the chunks' launches (opt-in)
-    hipError_t e;
-#define SBV_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
-    // The side streams may not touch the group buffers before everything already enqueued on `stream` (the
-    // previous batch's readers of those buffers) has run; ev_fork was recorded by the caller BEFORE stage A.
-    SBV_TRY(hipStreamWaitEvent(y.side_a, y.ev_fork, 0));
-    // ... nor before the previous batch's tail on side_b (table marks, promotion select: the readers of tslot and of the class bytes) is
-    // through (an event never recorded yet waits for nothing)
-    SBV_TRY(hipStreamWaitEvent(y.side_a, y.ev_promoted, 0));
-    SBV_TRY(hipMemsetAsync(b.ht, 0, ((size_t)b.ht_mask + 1) * sizeof(u32), y.side_a));
-    SBV_TRY(hipMemsetAsync(b.cnt, 0, n * sizeof(u32), y.side_a));
-    SBV_TRY(hipMemsetAsync(b.counters, 0, SBV_GROUP_COUNTERS * sizeof(u32), y.side_a));
-    if (g.sorted) SBV_TRY(hipMemsetAsync(b.gcount, 0, (size_t)b.max_groups * sizeof(u32), y.side_a));
     const unsigned gn = (unsigned)((n + 255) / 256);
     const unsigned gv = (unsigned)((n + SBV_VERIFY_BLOCK - 1) / SBV_VERIFY_BLOCK);
-    hipLaunchKernelGGL(k_group_insert, dim3(gn), dim3(256), 0, y.side_a, d_tuples, n, g);
-    hipLaunchKernelGGL(k_group_assign, dim3(gn), dim3(256), 0, y.side_a, d_tuples, n, g, b.kc);
-    SBV_TRY(hipEventRecord(y.ev_assign, y.side_a));
-    hipLaunchKernelGGL((k_key_cache_lookup_t<160, 96, 16>), dim3((b.max_groups + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, b.kc, b.tslot, b.cold);
-    hipLaunchKernelGGL((k_key_cache_insert_t<160, 96, 16>), dim3((b.max_groups + 63) / 64), dim3(64), 0, y.side_a, d_tuples, g, b.kc, b.tslot);
-    SBV_TRY(hipEventRecord(y.ev_cache, y.side_a));        // tslot / cold are final: the table classes (side_b) need them
+    // side_a: the head; ev_cache always: the table classes (side_b) need tslot / cold with or without hot keys
+    SBV_TRY((group_launch_head<160, 96, 16>(d_tuples, n, g, b, b.kc, y, true)));
     // stage A
     const size_t pbt = prep_block_tuples(n);
     const unsigned pblocks = (unsigned)((n + pbt - 1) / pbt);
     SBV_TRY(launch_p256_prep_blocks(d_tuples, n, s, stream, 0, pblocks));
-    // side_b: split
-    SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_assign, 0));
-    if (hot_on) SBV_TRY(hipMemsetAsync(hp.hot + 1, 0, 3 * sizeof(u32), y.side_b));        // promotions and wide-pass lanes of THIS batch: behind the previous batch's builder, which reads hot[1]
+    // side_b: classify, check the ungrouped candidates' keys, counting sort of the grouped tuples by key (ev_split then also stands for
+    // "the sorted list is final"), or the split in compaction order
+    SBV_TRY(group_launch_split(n, g, b, hot, sort_lds, y, [&] { hipLaunchKernelGGL(k_group_keycheck, dim3(gn), dim3(256), 0, y.side_b, d_tuples, g, b.acc); }));
     if (!g.sorted) hipLaunchKernelGGL(k_group_split, dim3(gn), dim3(256), 0, y.side_b, d_tuples, n, g, b.acc);
-    if (g.sorted) {             // classify, check the ungrouped candidates' keys, counting sort of the grouped tuples by key;
-                                // ev_split then also stands for "the sorted list is final"
-        hipLaunchKernelGGL(k_group_classify, dim3(gn), dim3(256), 0, y.side_b, n, g, b.ung_cand, b.counters + 4);
-        hipLaunchKernelGGL(k_group_keycheck, dim3(gn), dim3(256), 0, y.side_b, d_tuples, g, b.acc);
-        const unsigned tiles = (unsigned)((n + SBV_SORT_TILE - 1) / SBV_SORT_TILE);
-        hipLaunchKernelGGL(k_group_sort_count, dim3(tiles), dim3(1024), sort_lds, y.side_b, n, g);
-        hipLaunchKernelGGL(k_group_sort_scan, dim3(1), dim3(1024), 0, y.side_b, g);
-    }
-    if (g.sorted) {
-        const unsigned tiles = (unsigned)((n + SBV_SORT_TILE - 1) / SBV_SORT_TILE);
-        hipLaunchKernelGGL(k_group_sort_scatter, dim3(tiles), dim3(1024), sort_lds, y.side_b, n, g);
-    }
     SBV_TRY(hipEventRecord(y.ev_split, y.side_b));
     // table classes: after the exact counts (gcount survives the scan; the scatter moves gcursor only) and after the cache assigned the
     // slots; behind the scatter, so that the G phase (which waits for the sorted list, not for the classes) starts a launch earlier
@@ -730,29 +700,21 @@ hipError_t launch_p256_verify_grouped(const uint8_t* d_tuples, const Scratch& s_
     hipLaunchKernelGGL(k_pack_bitmap, dim3((unsigned)(((n + 7) / 8 + 255) / 256)), dim3(256), 0, stream, b.acc, n, d_bitmap);
     SBV_TRY(hipStreamWaitEvent(y.side_b, y.ev_promote, 0));
     hipLaunchKernelGGL(k_group_table_mark, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, b.cold, b.full, b.needfill, table_slots, b.kfull);
-    if (hot_on) {
-        // the life cycle (round 6): the clock sweep every SBV_HOT_DECAY_EVERY-th batch
-        if (hp.hot_tick % SBV_HOT_DECAY_EVERY == SBV_HOT_DECAY_EVERY - 1) hipLaunchKernelGGL(k_hot_decay, dim3((b.kc.cap + 255) / 256), dim3(256), 0, y.side_b, hk);
-        // promotions (p256_group.h: hot keys): which slots (the evictions when the pool is full), and their base points (tiny launches
-        // that read tslot and the tables)
-        hipLaunchKernelGGL(k_promote_select, dim3(64), dim3(256), 0, y.side_b, g, b.tslot, b.kvalid, hk);
-        hipLaunchKernelGGL(k_promote_evict, dim3(1), dim3(1024), 0, y.side_b, hk);
-        const widebuild wb = widebuild_make(SBV_HOT_BITS);
+    // The promotions: the table marks above read tslot and the class bytes whether or not hot keys are on, so ev_promoted is recorded
+    // for every batch; the builder's base points (a tiny launch that reads tslot's tables) sit in front of it, its chains and fill behind
+    // it — in front of the next batch's own side_b work (its table classes read kwide) and of its wide pass (behind the G phase, which
+    // waits for that side_b work)
+    const widebuild wb = widebuild_make(SBV_HOT_BITS);
+    SBV_TRY(group_launch_promote_select(g, b, b.kvalid, hp, hot, y, true, [&] {
         hipLaunchKernelGGL(k_promote_bases, dim3((SBV_PROMOTE_MAX * 2 * (u32)wb.windows + 63) / 64), dim3(64), 0, y.side_b, hp.plist, hp.hot, b.ktab, b.pbases);
-    }
-    // ev_promoted: the tail no longer reads tslot, the class bytes or the per-batch tables — the next batch's side_a (which rewrites them)
-    // waits for it; the builder and the publication follow on side_b, in front of the next batch's own side_b work (its table classes
-    // read kwide, its hot[] reset sits there too) and of its wide pass (behind the G phase, which waits for that side_b work)
-    SBV_TRY(hipEventRecord(y.ev_promoted, y.side_b));
+    }));
     if (hot_on) {
-        const widebuild wb = widebuild_make(SBV_HOT_BITS);
         const size_t stride = gcomb_entries(SBV_HOT_BITS);
         hipLaunchKernelGGL(k_promote_chains, dim3((SBV_PROMOTE_MAX * (u32)wb.windows * 2u + 63) / 64), dim3(64), 0, y.side_b, b.pbases, hp.plist, hp.hot, wb, stride, hp.ptmp, wtab);
         const size_t fill_lanes = (size_t)SBV_PROMOTE_MAX * wb.windows * (wb.giants - 1) * widebuild_fill_chunks(wb);
         hipLaunchKernelGGL(k_promote_fill, dim3((unsigned)((fill_lanes + 255) / 256)), dim3(256), 0, y.side_b, hp.plist, hp.hot, wb, stride, wtab);
-        hipLaunchKernelGGL(k_promote_publish, dim3(1), dim3(64), 0, y.side_b, hp.plist, hp.hot, hp.kwide, hp.wowner);
+        group_launch_promote_publish(hp, y);
     }
-#undef SBV_TRY
     if (prof && prof_pairs) *prof_pairs = coop ? 1 : chunks;
     return hipGetLastError();
 }

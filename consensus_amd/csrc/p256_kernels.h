@@ -80,19 +80,21 @@ struct GroupBuffers {
     size_t cap = 0;
     size_t gacc_cap = 0;        // the scratch capacity gacc was sized for
 };
-// A scheme's comb pool with its persistent key-table cache (secp256k1; the Ed25519 step keeps the same three things in its
-// EdGroupBuffers, the P-256 step in GroupBuffers): table slots [0, kc.cap) are kept between batches, [kc.cap, kc.cap + max_groups)
-// are rebuilt per batch.  One pool per scheme: a slot is found by the key BYTES, and the same bytes can be a point of two curves.
+// A variant's comb pool with its persistent key-table cache and hot keys (secp256k1: the context's own; Ed25519: EdGroupBuffers::kp):
+// table slots [0, kc.cap) are kept between batches, [kc.cap, kc.cap + max_groups) are rebuilt per batch.  One pool per scheme: a slot
+// is found by the key BYTES, and the same bytes can be a point of two curves.  (The P-256 step keeps its pool in GroupBuffers: another
+// entry type with the compact rows, the class bytes and the builder's base points beside it — ntab, kfull, pbases — and the one pool
+// that free_group_buffers' keep_pools hands over while the per-tuple arrays regrow.)
 struct KeyPool {
-    void* ktab = nullptr;       // (kc.cap + max_groups) x SBV_KEYTAB_ENTRIES 64-byte affine entries
+    void* ktab = nullptr;       // (kc.cap + max_groups) combs of the scheme's own entry type: cast where it is used (secp256k1: SBV_KEYTAB_ENTRIES 64-byte affine entries)
     uint8_t* kvalid = nullptr;  // (kc.cap + max_groups)
     KeyCache kc = {};
     u32 max_groups = 0;
-    // hot keys of this scheme (k256_group.h; sbv_secp256k1_hot_keys), off by default: combs of 17 x 32 768 64-byte affine entries
-    // (k256_keyed.h: SBV_K256_WIDE_*); ptmp = SBV_K256_WIDE_TMP_WORDS per lane of the builder's grid
+    // hot keys of the scheme (secp256k1: k256_group.h; sbv_secp256k1_hot_keys, off by default: combs of 17 x 32 768 64-byte affine entries,
+    // k256_keyed.h: SBV_K256_WIDE_*; ptmp = SBV_K256_WIDE_TMP_WORDS per lane of the builder's grid)
     HotPool hp;
     uint8_t* wide = nullptr;    // [max_groups] this batch's groups whose slot owns a comb.  Here, not in HotPool: per batch; it exists only with the pool
-    u32 build_blocks = 0;       // workgroups of the builder's grid (k256_keyed.h: k256_hot_build_blocks).  Here, not in HotPool: only this scheme's builder sizes its grid, and so ptmp, by the pool
+    u32 build_blocks = 0;       // secp256k1: workgroups of the builder's grid (k256_keyed.h: k256_hot_build_blocks).  Here, not in HotPool: only this scheme's builder sizes its grid, and so ptmp, by the pool
 };
 // streams and events of the grouped step; owned by the context.  `chunks` (1..SBV_GROUP_MAX_CHUNKS) = how
 // many pieces the 33 key-comb windows are built and consumed in.
@@ -103,11 +105,12 @@ struct GroupSync {
     hipStream_t side_t = nullptr;   // P-256, secp256k1: not owned — rows + fill of the odd chunks when tstreams = 2 (the context's own stream while the caller's runs the step)
     int tstreams = 2;               // SBV_GROUP_TSTREAMS (1, 2): 1 = every chunk's rows + fill queue up on side_b.  2: rows of chunk 1 start when ITS chain ends, not when fill of chunk 0 does — cold 2^18 2.04 -> 1.70 ms, 2^17 2.54 -> 2.23, 2^20 unchanged (profiles/r03/ab_sched_r03m.jsonl).  The Ed25519 step keeps one table stream (measured in round 4: 4.55 -> 4.67 ms with two, profiles/r04/ab_ed_tstreams_r04a.jsonl)
     hipEvent_t ev_fork = nullptr, ev_assign = nullptr, ev_split = nullptr, ev_generic = nullptr;
-    hipEvent_t ev_cache = nullptr, ev_class = nullptr;       // P-256: table slots assigned (side_a) / table classes decided (side_b)
-    hipEvent_t ev_narrow = nullptr;                          // P-256: the rows-only pass (side_a) is done
-    hipEvent_t ev_promote = nullptr;                         // P-256: this batch's promotions are selected (stream): side_b builds them
-    hipEvent_t ev_wide = nullptr;                            // P-256: the wide pass (side_a) is done
-    hipEvent_t ev_promoted = nullptr;                        // P-256: ... and published (side_b): the next batch's side_a waits for it
+    hipEvent_t ev_cache = nullptr;                           // every scheme: table slots assigned (side_a); the class kernel (side_b) waits for it
+    hipEvent_t ev_class = nullptr;                           // P-256: table classes decided (side_b).  Ed25519, secp256k1: the G phase is enqueued (stream), the wide pass may add to its sums
+    hipEvent_t ev_narrow = nullptr;                          // P-256: the rows-only pass (side_b) is done.  Ed25519: the key check of the ungrouped list (side_a) is enqueued
+    hipEvent_t ev_promote = nullptr;                         // P-256: the verdict bytes are final (stream): side_b runs the batch's tail behind it
+    hipEvent_t ev_wide = nullptr;                            // every scheme: the wide pass is done (P-256: side_a; Ed25519, secp256k1: side_b)
+    hipEvent_t ev_promoted = nullptr;                        // every scheme: the batch's tail (side_b) no longer reads tslot, the class bytes or the per-batch tables: the next batch's side_a waits for it
     hipEvent_t ev_bases[SBV_GROUP_MAX_CHUNKS] = {}, ev_tables[SBV_GROUP_MAX_CHUNKS] = {};
     int chunks = 1;
     int sorted = 1;                 // key-sorted grouped list + XCD-aware Q phase (SBV_GROUP_SORT=0: the split's compaction order; the form the step falls back to when a batch has more groups than one LDS histogram holds)

@@ -447,20 +447,20 @@ bool hot_pool_alloc(const Context& c, sbv::HotPool& p, const sbv::KeyCache& kc, 
     return false;
 }
 
-// a scheme's comb pool with its key-table cache and hot keys (the P-256 step's go with its other buffers: free_group_buffers)
-void ed_pool_free(sbv::EdGroupBuffers& e) {
-    void* part[] = {e.ktab, e.okb, e.ungxy, e.kvalid, e.wide};
-    for (void* q : part) if (q) (void)hipFree(q);
-    key_cache_free(e.kc);
-    hot_pool_free(e.hp);
-    e = sbv::EdGroupBuffers();
-}
-void k256_pool_free(sbv::KeyPool& kp) {
+// a variant's comb pool with its key-table cache and hot keys (the P-256 step's go with its other buffers: free_group_buffers)
+void key_pool_free(sbv::KeyPool& kp) {
     void* part[] = {kp.ktab, kp.kvalid, kp.wide};
     for (void* q : part) if (q) (void)hipFree(q);
     key_cache_free(kp.kc);
     hot_pool_free(kp.hp);
     kp = sbv::KeyPool();
+}
+// ... and the Ed25519 step's per-tuple arrays beside its pool
+void ed_buffers_free(sbv::EdGroupBuffers& e) {
+    if (e.okb) (void)hipFree(e.okb);
+    if (e.ungxy) (void)hipFree(e.ungxy);
+    key_pool_free(e.kp);
+    e = sbv::EdGroupBuffers();
 }
 
 // keep_pools: the comb pools and key-table caches of the three schemes depend on (cache capacity, max_groups) only — a batch larger
@@ -482,8 +482,8 @@ void free_group_buffers(Context& c, bool keep_pools = false) {
     key_cache_free(b.kc);
     hot_pool_free(b.hp);
     b = sbv::GroupBuffers();
-    ed_pool_free(c.edgrp);
-    k256_pool_free(c.k256pool);
+    ed_buffers_free(c.edgrp);
+    key_pool_free(c.k256pool);
 }
 
 // HBM that everything sized by (cache capacity K, groups per batch G) takes: the comb pool (270 KiB per slot), the compact rows
@@ -625,84 +625,75 @@ void note_grouped_launch(Context& c, int scheme, size_t n, const sbv::GroupBuffe
     ++l.serial;
 }
 
+// the optional hot-key pool of a variant goes, with the class bytes that exist only with it: the feature is off, the batch goes on
+void key_pool_drop_hot(sbv::KeyPool& kp) {
+    (void)hipGetLastError();
+    if (kp.wide) (void)hipFree(kp.wide);
+    kp.wide = nullptr; kp.build_blocks = 0;
+    hot_pool_free(kp.hp);
+}
+// A variant's pool for (K = the scheme's cache capacity, variant_groups): the comb pool of slot_bytes per table slot — [0, K) = the
+// persistent key-table cache, [K, K + groups) per batch —, the valid bytes, the key cache, the optional hot pool (hot_pool_alloc's
+// arguments) and the class bytes that exist only with it.  The pool depends on (K, groups) only: a batch larger than any before must
+// not empty the cache (found on the GPU in round 4: the warm batch of the cache test was 384 tuples longer than the cold one and
+// missed every key).  *fresh: the pool was rebuilt, behind a device-wide synchronisation.
+int ensure_key_pool(Context& c, sbv::KeyPool& kp, int scheme, size_t slot_bytes, size_t comb_bytes, size_t (*scratch_of)(size_t combs), unsigned percent,
+                    bool fit_scratch, bool* fresh) {
+    const size_t K = c.kc_caps[scheme];
+    const u32 vg = variant_groups(c);
+    *fresh = !(kp.ktab && kp.max_groups == vg && kp.kc.ht && kp.kc.cap == K);
+    if (*fresh) {
+        HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+        key_pool_free(kp);
+        HIP_TRY(SBV_ENOMEM, hipMalloc(&kp.ktab, (K + vg) * slot_bytes));
+        HIP_TRY(SBV_ENOMEM, hipMalloc(&kp.kvalid, K + vg));
+        const int rc = key_cache_alloc(kp.kc, K, c.kc_on[scheme]);
+        if (rc != SBV_OK) return rc;
+        kp.max_groups = vg;
+        if (hot_pool_alloc(c, kp.hp, kp.kc, c.hot_keys[scheme], comb_bytes, scratch_of, percent, fit_scratch) &&
+            (hipMalloc(&kp.wide, vg) != hipSuccess || memset_now(kp.wide, 0, vg) != hipSuccess)) key_pool_drop_hot(kp);
+    }
+    kp.hp.promote_min = c.hot_min_hits[scheme];
+    kp.kc.enabled = c.kc_on[scheme] ? 1u : 0u;
+    return SBV_OK;
+}
+
+// Ed25519: the grouping arrays of the P-256 step + this scheme's own pool and its per-tuple arrays
 int ensure_ed_group_buffers(Context& c, size_t n) {
     int rc = ensure_group_buffers(c, n);
     if (rc != SBV_OK) return rc;
     sbv::EdGroupBuffers& e = c.edgrp;
-    const size_t K = c.kc_caps[2];
-    // The comb pool and its cache depend on (K, max_groups) only: a batch larger than any before must not empty the cache
-    // (found on the GPU in round 4: the warm batch of the cache test was 384 tuples longer than the cold one and missed every key).
-    const u32 vg = variant_groups(c);
-    const bool pool_ok = e.ktab && e.max_groups == vg && e.kc.ht && e.kc.cap == K;
-    e.hp.promote_min = c.hot_min_hits[SBV_SCHEME_ED25519];
-    if (pool_ok && e.okb && e.cap >= c.grp.cap) {
-        e.kc.enabled = c.kc_on[2] ? 1u : 0u;
-        return SBV_OK;
-    }
-    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
+    // hot keys of this scheme: 64 MiB combs — 1024 of them are 64 GiB of the 288, hence a quarter of the device at most
+    bool fresh;
+    rc = ensure_key_pool(c, e.kp, SBV_SCHEME_ED25519, (size_t)SBV_ED_KEYTAB_ENTRIES_PER_KEY * sizeof(sbv::aniels), SBV_ED_HOT_COMB_BYTES,
+                         [](size_t) { return (size_t)SBV_ED_HOT_BUILD_BLOCKS * 64 * SBV_ED_HOT_TMP_WORDS * sizeof(u32); }, 25, true, &fresh);
+    if (rc != SBV_OK) return rc;
+    if (e.okb && e.cap >= c.grp.cap) return SBV_OK;
+    if (!fresh) HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
     if (e.okb) (void)hipFree(e.okb);
     if (e.ungxy) (void)hipFree(e.ungxy);
     e.okb = nullptr; e.ungxy = nullptr; e.cap = 0;
-    if (!pool_ok) {
-        ed_pool_free(e);
-        // comb pool of this scheme: slots [0, K) = its persistent key-table cache, [K, K + max_groups) per batch
-        HIP_TRY(SBV_ENOMEM, hipMalloc(&e.ktab, (K + vg) * (size_t)SBV_ED_KEYTAB_ENTRIES_PER_KEY * sizeof(sbv::aniels)));
-        HIP_TRY(SBV_ENOMEM, hipMalloc(&e.kvalid, K + vg));
-        rc = key_cache_alloc(e.kc, K, c.kc_on[2]);
-        if (rc != SBV_OK) return rc;
-        e.max_groups = vg;
-        // hot keys of this scheme: the optional pool (hot_pool_alloc) of 64 MiB combs — 1024 of them are 64 GiB of the 288, hence a quarter
-        // of the device at most — and the class bytes that exist only with it
-        if (hot_pool_alloc(c, e.hp, e.kc, c.hot_keys[SBV_SCHEME_ED25519], SBV_ED_HOT_COMB_BYTES,
-                           [](size_t) { return (size_t)SBV_ED_HOT_BUILD_BLOCKS * 64 * SBV_ED_HOT_TMP_WORDS * sizeof(u32); }, 25, true) &&
-            (hipMalloc(&e.wide, vg) != hipSuccess || memset_now(e.wide, 0, vg) != hipSuccess)) {
-            (void)hipGetLastError();
-            if (e.wide) (void)hipFree(e.wide);
-            e.wide = nullptr;
-            hot_pool_free(e.hp);
-        }
-    }
     HIP_TRY(SBV_ENOMEM, hipMalloc(&e.okb, c.grp.cap));
     HIP_TRY(SBV_ENOMEM, hipMalloc(&e.ungxy, c.grp.cap * (size_t)SBV_ED_UNGXY_WORDS * sizeof(u32)));
-    e.hp.promote_min = c.hot_min_hits[SBV_SCHEME_ED25519];
     e.cap = c.grp.cap;
-    e.kc.enabled = c.kc_on[2] ? 1u : 0u;
     return SBV_OK;
 }
 
-// secp256k1: the grouping arrays of the P-256 step + this curve's own comb pool and key-table cache
+// secp256k1: the grouping arrays of the P-256 step + this curve's own pool
 int ensure_k256_group_buffers(Context& c, size_t n) {
     int rc = ensure_group_buffers(c, n);
     if (rc != SBV_OK) return rc;
     sbv::KeyPool& kp = c.k256pool;
-    const size_t K = c.kc_caps[1];
-    const u32 vg = variant_groups(c);
-    kp.hp.promote_min = c.hot_min_hits[SBV_SCHEME_SECP256K1];
-    if (kp.ktab && kp.max_groups == vg && kp.kc.cap == K) {
-        kp.kc.enabled = c.kc_on[1] ? 1u : 0u;
-        return SBV_OK;
-    }
-    HIP_TRY(SBV_EDEVICE, hipDeviceSynchronize());
-    k256_pool_free(kp);
-    HIP_TRY(SBV_ENOMEM, hipMalloc(&kp.ktab, (K + vg) * (size_t)SBV_KEYTAB_ENTRIES * sizeof(sbv::apt)));
-    HIP_TRY(SBV_ENOMEM, hipMalloc(&kp.kvalid, K + vg));
-    rc = key_cache_alloc(kp.kc, K, c.kc_on[1]);
+    // hot keys of this scheme: 35.7 MB combs, off unless asked for (sbv_secp256k1_hot_keys); the builder's grid and scratch follow the pool's
+    // final size.  The pool is zeroed once: a comb's top window holds one entry, the builder writes no other of it.
+    bool fresh;
+    rc = ensure_key_pool(c, kp, SBV_SCHEME_SECP256K1, (size_t)SBV_KEYTAB_ENTRIES * sizeof(sbv::apt), SBV_K256_WIDE_COMB_BYTES,
+                         [](size_t combs) { return (size_t)sbv::k256_hot_build_blocks((u32)combs) * 64 * SBV_K256_WIDE_TMP_WORDS * sizeof(u32); }, 15, true, &fresh);
     if (rc != SBV_OK) return rc;
-    kp.max_groups = vg;
-    // hot keys of this scheme: the optional pool (hot_pool_alloc) of 35.7 MB combs, off unless asked for (sbv_secp256k1_hot_keys); the builder's
-    // grid and scratch follow the pool's final size.  The pool is zeroed once: a comb's top window holds one entry, the builder writes no other of it.
-    if (hot_pool_alloc(c, kp.hp, kp.kc, c.hot_keys[SBV_SCHEME_SECP256K1], SBV_K256_WIDE_COMB_BYTES,
-                       [](size_t combs) { return (size_t)sbv::k256_hot_build_blocks((u32)combs) * 64 * SBV_K256_WIDE_TMP_WORDS * sizeof(u32); }, 15, true)) {
-        const size_t pool_bytes = (size_t)kp.hp.wide_cap * SBV_K256_WIDE_COMB_BYTES;
+    if (fresh && kp.hp.wtab) {
         kp.build_blocks = sbv::k256_hot_build_blocks(kp.hp.wide_cap);
-        if (hipMalloc(&kp.wide, vg) != hipSuccess || memset_now(kp.wide, 0, vg) != hipSuccess || memset_now(kp.hp.wtab, 0, pool_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            if (kp.wide) (void)hipFree(kp.wide);
-            kp.wide = nullptr; kp.build_blocks = 0;
-            hot_pool_free(kp.hp);
-        }
+        if (memset_now(kp.hp.wtab, 0, (size_t)kp.hp.wide_cap * SBV_K256_WIDE_COMB_BYTES) != hipSuccess) key_pool_drop_hot(kp);
     }
-    kp.hp.promote_min = c.hot_min_hits[SBV_SCHEME_SECP256K1];
     return SBV_OK;
 }
 
@@ -726,6 +717,28 @@ bool group_buffers_or_fallback(Context& c, size_t, F&& ensure, bool& grouped) {
     return true;
 }
 
+// ---- what the three enqueue functions below share -----------------------------------------------------------------------------------------
+// The step's streams and events with the second table stream (P-256, secp256k1).  That stream is NOT a stream of its own: a process gets
+// four hardware queues and the fifth stream shares one with the first — here the caller's, so rows + fill of chunk 1 queued behind the
+// first Q launch (2^20 cold 3.45 -> 3.75 ms, profiles/r03/timeline_r03o.txt).  When the caller brings its own stream (device-pointer
+// entries) the context's stream is idle and takes the job; the host-pointer entries run on it themselves and keep one table stream.
+sbv::GroupSync sync_lending_stream(const Context& c, hipStream_t stream) {
+    sbv::GroupSync y = c.gsync;
+    if (y.tstreams > 1 && stream != c.stream) y.side_t = c.stream;
+    else y.tstreams = 1;
+    return y;
+}
+// the clock of the hot keys' decay (p256_group.h): one tick per grouped batch that uses them
+void hot_tick(sbv::HotPool& hp, const sbv::KeyCache& kc) { if (hp.wtab && kc.enabled) ++hp.hot_tick; }
+// The grouped launch failed.  k_key_cache_insert_t publishes a slot before its tables are built: a step that failed half-way may leave
+// slots whose combs never were.  Forget the whole cache and its hot keys (best effort, after draining what did get enqueued).
+int grouped_launch_failed(sbv::KeyCache& kc, sbv::HotPool& hp, const char* launcher, hipError_t ge) {
+    (void)hipDeviceSynchronize();
+    (void)key_cache_forget(kc);
+    (void)hot_pool_forget(hp, kc);
+    return fail(SBV_EDEVICE, launcher, ge);
+}
+
 int ensure_ed_bcomb(Context& c);
 // one chunk (n <= cap) of Ed25519 tuples on `stream`: grouped step or the one-lane kernel
 int enqueue_ed25519(Context& c, const uint8_t* d_tuples, size_t n, uint8_t* d_bitmap, hipStream_t stream, hipEvent_t* dom = nullptr, int* dom_pairs = nullptr) {
@@ -735,17 +748,11 @@ int enqueue_ed25519(Context& c, const uint8_t* d_tuples, size_t n, uint8_t* d_bi
     if (grouped && !group_buffers_or_fallback(c, n, [&] { const int r = ensure_ed_group_buffers(c, n); return r != SBV_OK ? r : ensure_ed_bcomb(c); }, grouped)) return g_last_rc;
     if (grouped) {
         HIP_TRY(SBV_EDEVICE, hipEventRecord(c.gsync.ev_fork, stream));
-        if (c.edgrp.hp.wtab && c.edgrp.kc.enabled) ++c.edgrp.hp.hot_tick;     // the clock of the hot keys' decay
+        hot_tick(c.edgrp.kp.hp, c.edgrp.kp.kc);
         const sbv::GroupBuffers bv = variant_view(c, n);
         note_grouped_launch(c, SBV_SCHEME_ED25519, n, bv, sbv::ed25519_group_step_sorted(c.gsync, bv));
         const hipError_t ge = sbv::launch_ed25519_verify_grouped(d_tuples, n, bv, c.edgrp, c.d_qtab, c.d_btab, sbv::edcomb_make(c.d_ed_bcomb, c.ed_bbits, c.ed_bpitch), d_bitmap, stream, c.gsync, dom, dom_pairs);
-        if (ge != hipSuccess) {          // a slot is published before its tables are built (see enqueue()): forget the cache
-            (void)hipDeviceSynchronize();
-            (void)key_cache_forget(c.edgrp.kc);
-            (void)hot_pool_forget(c.edgrp.hp, c.edgrp.kc);
-            return fail(SBV_EDEVICE, "launch_ed25519_verify_grouped", ge);
-        }
-        return SBV_OK;
+        return ge == hipSuccess ? SBV_OK : grouped_launch_failed(c.edgrp.kp.kc, c.edgrp.kp.hp, "launch_ed25519_verify_grouped", ge);
     }
     HIP_TRY(SBV_EDEVICE, sbv::launch_ed25519_verify(d_tuples, n, c.d_qtab, c.d_btab, d_bitmap, stream));
     return SBV_OK;
@@ -772,26 +779,12 @@ int enqueue(Context& c, const uint8_t* d_tuples, size_t n, uint8_t* d_bitmap, hi
     if (grouped) {           // stage A is enqueued by the grouped launcher
         sbv::Scratch sg = s;
         sg.rec = c.gsync.sorted ? c.grp.rec : nullptr;      // stage A also writes the per-tuple records the key-sorted list reads
-        // The second table stream is NOT a stream of its own: a process gets four hardware queues and the fifth stream shares
-        // one with the first — here the caller's, so rows + fill of chunk 1 queued behind the first Q launch (2^20 cold 3.45 ->
-        // 3.75 ms, profiles/r03/timeline_r03o.txt).  When the caller brings its own stream (device-pointer entries) the
-        // context's stream is idle and takes the job; the host-pointer entries run on it themselves and keep one table stream.
-        sbv::GroupSync y = c.gsync;
-        if (y.tstreams > 1 && stream != c.stream) y.side_t = c.stream;
-        else y.tstreams = 1;
-        if (c.grp.hp.wtab && c.grp.kc.enabled) ++c.grp.hp.hot_tick;           // the clock of the hot keys' decay (p256_group.h)
+        const sbv::GroupSync y = sync_lending_stream(c, stream);
+        hot_tick(c.grp.hp, c.grp.kc);
         note_grouped_launch(c, SBV_SCHEME_P256, n, c.grp, sbv::p256_group_step_sorted(y, sg, c.grp));
         const hipError_t ge = sbv::launch_p256_verify_grouped(d_tuples, sg, n, c.grp, c.d_qtab, c.d_gtab, sbv::gcomb_make(c.d_g16r, c.g_bits), d_bitmap, stream, y,
                                                               after_prep, dom, dom_pairs);
-        if (ge != hipSuccess) {
-            // k_key_cache_insert publishes a slot before its tables are built: a step that failed half-way may leave slots
-            // whose combs never were.  Forget the whole cache (best effort, after draining what did get enqueued).
-            (void)hipDeviceSynchronize();
-            (void)key_cache_forget(c.grp.kc);
-            (void)hot_pool_forget(c.grp.hp, c.grp.kc);
-            return fail(SBV_EDEVICE, "launch_p256_verify_grouped", ge);
-        }
-        return SBV_OK;
+        return ge == hipSuccess ? SBV_OK : grouped_launch_failed(c.grp.kc, c.grp.hp, "launch_p256_verify_grouped", ge);
     }
     HIP_TRY(SBV_EDEVICE, sbv::launch_p256_prep(d_tuples, n, s, stream));
     if (after_prep) HIP_TRY(SBV_EDEVICE, hipEventRecord(after_prep, stream));
@@ -1917,20 +1910,12 @@ int enqueue_k256(Context& c, const uint8_t* d_tuples, size_t m, uint8_t* d_bitma
     if (grouped && !group_buffers_or_fallback(c, m, [&] { const int r = ensure_k256_group_buffers(c, m); return r != SBV_OK ? r : ensure_k256_gcomb(c); }, grouped)) return g_last_rc;
     if (grouped) {
         HIP_TRY(SBV_EDEVICE, hipEventRecord(c.gsync.ev_fork, stream));
-        sbv::GroupSync y = c.gsync;                 // second table stream: the context's own, when the caller's runs the step (enqueue() says why)
-        if (y.tstreams > 1 && stream != c.stream) y.side_t = c.stream;
-        else y.tstreams = 1;
-        if (c.k256pool.hp.wtab && c.k256pool.kc.enabled) ++c.k256pool.hp.hot_tick;     // the clock of the hot keys' decay
+        const sbv::GroupSync y = sync_lending_stream(c, stream);
+        hot_tick(c.k256pool.hp, c.k256pool.kc);
         const sbv::GroupBuffers bv = variant_view(c, m);
         note_grouped_launch(c, SBV_SCHEME_SECP256K1, m, bv, sbv::k256_group_step_sorted(y, bv));
         const hipError_t ge = sbv::launch_k256_verify_grouped(d_tuples, s, m, bv, c.k256pool, c.d_qtab, c.d_k256_gtab, c.d_k256_gcomb, c.k256_gbits, d_bitmap, stream, y, dom, dom_pairs);
-        if (ge != hipSuccess) {
-            (void)hipDeviceSynchronize();
-            (void)key_cache_forget(c.k256pool.kc);
-            (void)hot_pool_forget(c.k256pool.hp, c.k256pool.kc);
-            return fail(SBV_EDEVICE, "launch_k256_verify_grouped", ge);
-        }
-        return SBV_OK;
+        return ge == hipSuccess ? SBV_OK : grouped_launch_failed(c.k256pool.kc, c.k256pool.hp, "launch_k256_verify_grouped", ge);
     }
     HIP_TRY(SBV_EDEVICE, sbv::launch_k256_verify(d_tuples, m, s, c.d_qtab, c.d_k256_gtab, d_bitmap, stream));
     return SBV_OK;
@@ -3272,10 +3257,10 @@ extern "C" int sbv_p256_set_grouping(int enabled, size_t min_batch, uint32_t min
 
 namespace {
 sbv::KeyCache* scheme_cache(Context& c, int scheme) {
-    return scheme == SBV_SCHEME_P256 ? &c.grp.kc : scheme == SBV_SCHEME_SECP256K1 ? &c.k256pool.kc : &c.edgrp.kc;
+    return scheme == SBV_SCHEME_P256 ? &c.grp.kc : scheme == SBV_SCHEME_SECP256K1 ? &c.k256pool.kc : &c.edgrp.kp.kc;
 }
 sbv::HotPool* scheme_hot_pool(Context& c, int scheme) {
-    return scheme == SBV_SCHEME_P256 ? &c.grp.hp : scheme == SBV_SCHEME_SECP256K1 ? &c.k256pool.hp : &c.edgrp.hp;
+    return scheme == SBV_SCHEME_P256 ? &c.grp.hp : scheme == SBV_SCHEME_SECP256K1 ? &c.k256pool.hp : &c.edgrp.kp.hp;
 }
 }  // namespace
 
@@ -3388,7 +3373,7 @@ int set_hot_keys(int scheme, const char* entry, uint32_t max_keys, uint32_t min_
         if (min_hits) c.hot_min_hits[scheme] = min_hits;
         if (c.hot_keys[scheme] == max_keys) continue;          // the size it has: nothing is freed, nobody waits for the device
         c.hot_keys[scheme] = max_keys;
-        const bool built = scheme == SBV_SCHEME_P256 ? c.grp.ktab != nullptr : scheme == SBV_SCHEME_SECP256K1 ? c.k256pool.ktab != nullptr : c.edgrp.ktab != nullptr;
+        const bool built = scheme == SBV_SCHEME_P256 ? c.grp.ktab != nullptr : scheme == SBV_SCHEME_SECP256K1 ? c.k256pool.ktab != nullptr : c.edgrp.kp.ktab != nullptr;
         if (!c.ready || !built) continue;
         hipError_t e = hipSetDevice(c.hip_dev);
         if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -3397,8 +3382,8 @@ int set_hot_keys(int scheme, const char* entry, uint32_t max_keys, uint32_t min_
         // pools are their own; the P-256 pool is freed with the grouping arrays that all three steps share, and with them go the other two
         // schemes' pools and caches as well (tests/test_gpu_configs.py: test_hot_key_setters_drop_only_what_they_own holds both).
         if (scheme == SBV_SCHEME_P256) free_group_buffers(c);
-        else if (scheme == SBV_SCHEME_SECP256K1) k256_pool_free(c.k256pool);
-        else ed_pool_free(c.edgrp);
+        else if (scheme == SBV_SCHEME_SECP256K1) key_pool_free(c.k256pool);
+        else ed_buffers_free(c.edgrp);
     }
     return rc;
 }
@@ -3465,7 +3450,7 @@ extern "C" int sbv_ed25519_hot_selfcheck(uint32_t index) {
         for (auto& t : th) t.join();
     }
     std::vector<uint8_t> got(SBV_ED_HOT_COMB_BYTES);
-    HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), static_cast<const uint8_t*>(c.edgrp.hp.wtab) + (size_t)index * SBV_ED_HOT_COMB_BYTES, got.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(SBV_EDEVICE, hipMemcpy(got.data(), static_cast<const uint8_t*>(c.edgrp.kp.hp.wtab) + (size_t)index * SBV_ED_HOT_COMB_BYTES, got.size(), hipMemcpyDeviceToHost));
     for (size_t e = 0; e < want.size(); ++e)
         if (memcmp(got.data() + e * SBV_ED_HOT_PITCH, &want[e], sizeof(sbv::aniels)) != 0) return 0;
     return 1;

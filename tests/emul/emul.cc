@@ -1055,7 +1055,7 @@ void sbve_ed25519_verify_batch_grouped(const uint8_t* tuples_in, size_t n, uint8
     auto table_of = [&](u32 k) -> aniels* { return tslot[k] < kc.cap ? (aniels*)g_kc_ed.pool + (size_t)tslot[k] * SBV_ED_KEYTAB_ENTRIES : ktab + (size_t)k * SBV_ED_KEYTAB_ENTRIES; };
     auto valid_of = [&](u32 k) -> uint8_t* { return tslot[k] < kc.cap ? &g_kc_ed.valid[tslot[k]] : &kvalid[k]; };
     memset(bitmap, 0, (n + 7) / 8);
-    // hot keys (k_ed_hot_class; the wavefronts of the wide pass: ed_wave_is_wide) — with the cache on, a pool and the key-sorted list
+    // hot keys (k_group_hot_class; the wavefronts of the wide pass: ed_wave_is_wide) — with the cache on, a pool and the key-sorted list
     const bool hot_on = g_ed_hot_cap && g_ed_hot_wtab && kc.enabled && g.sorted && g_ed_hot_kwide.size() >= kc.cap;
     std::vector<uint8_t> wide(ng1, 0), wave_wide((counters[1] + 63) / 64 + 1, 0);
     if (hot_on) {

@@ -22,7 +22,7 @@ def run():
 def show(path):
     rows = [r for r in csv.DictReader(open(path)) if "sbv::" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    inserts = [i for i, r in enumerate(rows) if "k_ed_group_insert" in r["Kernel_Name"]]
+    inserts = [i for i, r in enumerate(rows) if "k_group_insert_t<128, 64, 8>" in r["Kernel_Name"]]      # the insert kernel on this scheme's tuple format
     # the cold steps come first (the leg's warm part follows): take the third cold step
     start = inserts[2]
     end = inserts[3]
