@@ -436,6 +436,48 @@ def verify_msgs_keyed(msgs, sigs_der, slots) -> bytes:
     return out.raw[:(n + 7) // 8]
 
 
+_MSGS_ARGS = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p]
+
+
+def _msgs_tables(msgs, sigs_der, keys, offsets=None):
+    """(n, message offsets, signature offsets, key bytes) of a raw-message call; keys: n x 64 bytes Qx | Qy, as a list or one string"""
+    n = len(msgs)
+    mo = (ctypes.c_uint64 * (n + 1))()
+    so = (ctypes.c_uint64 * (n + 1))()
+    a = b = 0
+    for i in range(n):
+        mo[i], so[i] = a, b
+        a += len(msgs[i]); b += len(sigs_der[i])
+    mo[n], so[n] = a, b
+    if offsets is not None:
+        for i in range(n + 1):
+            mo[i], so[i] = offsets[0][i], offsets[1][i]
+    kb = bytes(keys) if isinstance(keys, (bytes, bytearray)) else b"".join(keys)
+    if len(kb) != 64 * n:
+        raise ValueError("keys must be n x 64 bytes Qx | Qy")
+    return n, mo, so, kb
+
+
+def _verify_msgs(symbol, msgs, sigs_der, keys) -> bytes:
+    n, mo, so, kb = _msgs_tables(msgs, sigs_der, keys)
+    out = ctypes.create_string_buffer(max(1, (n + 7) // 8))
+    fn = getattr(load(), symbol)
+    fn.argtypes = _MSGS_ARGS + [ctypes.c_size_t, ctypes.c_void_p]
+    _check(fn(b"".join(msgs), mo, b"".join(sigs_der), so, kb, n, out))
+    return out.raw[:(n + 7) // 8]
+
+
+def verify_msgs(msgs, sigs_der, keys) -> bytes:
+    """sbv_p256_verify_msgs: raw messages + DER signatures + the signers' 64-byte keys (no registry): SHA-256, the strict DER parse and
+    the tuple layout on the GPU, then the generic P-256 step -> accept bitmap (n <= 2^21)."""
+    return _verify_msgs("sbv_p256_verify_msgs", msgs, sigs_der, keys)
+
+
+def secp256k1_verify_msgs(msgs, sigs_der, keys) -> bytes:
+    """sbv_secp256k1_verify_msgs: the same front end in front of the generic secp256k1 step."""
+    return _verify_msgs("sbv_secp256k1_verify_msgs", msgs, sigs_der, keys)
+
+
 def set_grouping(enabled: bool, min_batch: int = 0, min_count: int = 0, max_groups: int = 0) -> None:
     """In-step grouping of generic batches by public key (0 keeps a value; min_batch = GROUP_MIN_BATCH_DEFAULT restores the
     built-in thresholds); see include/sbv.h."""
@@ -1015,6 +1057,22 @@ def verify_msgs_keyed_sharded(msgs, sigs_der, slots, group: int = 0, quorum: int
     qout = ctypes.create_string_buffer(max(1, (props + 7) // 8)) if group and quorum else None
     info = ShardInfo()
     _check(lib.sbv_p256_verify_msgs_keyed_sharded(b"".join(msgs), mo, b"".join(sigs_der), so, arr, n, group, quorum, out, qout, ctypes.byref(info)))
+    return out.raw[:(n + 7) // 8], (qout.raw[:(props + 7) // 8] if qout is not None else None), info
+
+
+def verify_msgs_sharded(msgs, sigs_der, keys, group: int = 0, quorum: int = 0, offsets=None):
+    """sbv_p256_verify_msgs_sharded: raw messages + DER signatures + the signers' keys over every initialised device (always the
+    contiguous split), SHA-256 and the DER parse on the devices, uploads in pieces.  Returns (accept bitmap, quorum bitmap or None,
+    ShardInfo).  offsets = (msg_offsets, sig_offsets): use these tables instead of the ones the byte strings imply."""
+    lib = load()
+    lib.sbv_p256_verify_msgs_sharded.argtypes = _MSGS_ARGS + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.POINTER(ShardInfo)]
+    n, mo, so, kb = _msgs_tables(msgs, sigs_der, keys, offsets)
+    out = ctypes.create_string_buffer(max(1, (n + 7) // 8))
+    props = n // group if group else 0
+    qout = ctypes.create_string_buffer(max(1, (props + 7) // 8)) if group and quorum else None
+    info = ShardInfo()
+    _check(lib.sbv_p256_verify_msgs_sharded(b"".join(msgs), mo, b"".join(sigs_der), so, kb, n, group, quorum, out, qout, ctypes.byref(info)))
     return out.raw[:(n + 7) // 8], (qout.raw[:(props + 7) // 8] if qout is not None else None), info
 
 

@@ -40,6 +40,7 @@
 #include "k256_sign_kernels.h"
 #include "k256_recover_kernels.h"
 #include "keccak_kernels.h"
+#include "msg_frontend_kernels.h"
 #include "k256_schnorr_kernels.h"
 #include "k256_schnorr_keyed_kernels.h"
 
@@ -2556,6 +2557,66 @@ extern "C" int sbv_secp256k1_verify_msgs_keyed(const uint8_t* msgs, const uint64
         });
 }
 
+// ---- raw messages for the GENERIC verifiers (include/sbv.h: sbv_p256_verify_msgs, sbv_secp256k1_verify_msgs) ---------------------------
+// Messages, DER signatures, both offset tables and the signers' keys go up; k_msg_frontend_tuples (msg_frontend_kernels.hip) writes the
+// 160-byte tuples r | s | SHA-256 | Qx | Qy into c.d_tuples, and the scheme's tuple step runs on them exactly as on uploaded tuples: the
+// grouped step, the key-table cache and the hot-key pools see no difference.  The keys are staged behind the signatures in d_sigs, at
+// the next multiple of 16 bytes (as sbv_ed25519_verify_msgs stages its keys).  prep_us: the front end (P-256: + stage A).
+namespace {
+// c.mu held.  tables(): the scheme's device tables; step(after_prep): its tuple step over c.d_tuples, which records after_prep.
+template <class Tables, class Step>
+int verify_msgs_tuples(Context& c, const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
+                       const uint8_t* keys, size_t n, uint8_t* accept_bitmap, Tables&& tables, Step&& step) {
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }         // before any array is read
+    if (!msg_offsets || !sig_offsets || !keys || !accept_bitmap) { g_err = "null pointer"; return SBV_EINVAL; }
+    size_t mbytes = 0, sbytes = 0;
+    int rc = check_offsets(msg_offsets, n, msgs, mbytes);
+    if (rc == SBV_OK) rc = check_offsets(sig_offsets, n, sigs, sbytes);
+    if (rc != SBV_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    if ((rc = tables()) != SBV_OK) return rc;
+    const size_t koff = (sbytes + 15) & ~(size_t)15;
+    if ((rc = grow(c.d_msgs, c.msgs_cap, mbytes + 16)) != SBV_OK) return rc;
+    if ((rc = grow(c.d_sigs, c.sigs_cap, koff + n * 64 + 16)) != SBV_OK) return rc;
+    if ((rc = grow(c.d_moff, c.moff_cap, n + 1)) != SBV_OK) return rc;
+    if ((rc = grow(c.d_soff, c.soff_cap, n + 1)) != SBV_OK) return rc;
+    return run_chunks_host(c, n, accept_bitmap, t0, true,
+        [&](size_t, size_t) {
+            if (mbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_msgs, msgs, mbytes, hipMemcpyHostToDevice, c.stream));
+            if (sbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs, sigs, sbytes, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs + koff, keys, n * 64, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_moff, msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_soff, sig_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+            return SBV_OK;
+        },
+        [&](size_t, size_t, hipEvent_t after_prep) {
+            HIP_TRY(SBV_EDEVICE, sbv::launch_msg_frontend_tuples(c.d_msgs, c.d_moff, c.d_sigs, c.d_soff, c.d_sigs + koff, n,
+                                                                 reinterpret_cast<u32*>(c.d_tuples), c.stream, 0, 0, mbytes, sbytes));
+            return step(after_prep);
+        });
+}
+}  // namespace
+
+extern "C" int sbv_p256_verify_msgs(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
+                                    const uint8_t* keys, size_t n, uint8_t* accept_bitmap) {
+    SBV_ENTER(c);
+    return verify_msgs_tuples(c, msgs, msg_offsets, sigs, sig_offsets, keys, n, accept_bitmap, [] { return SBV_OK; },
+                              [&](hipEvent_t after_prep) { return enqueue(c, c.d_tuples, n, c.d_bitmap, c.stream, after_prep); });
+}
+
+extern "C" int sbv_secp256k1_verify_msgs(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
+                                         const uint8_t* keys, size_t n, uint8_t* accept_bitmap) {
+    SBV_ENTER(c);
+    return verify_msgs_tuples(c, msgs, msg_offsets, sigs, sig_offsets, keys, n, accept_bitmap, [&] { return ensure_k256_table(c); },
+                              [&](hipEvent_t after_prep) {
+                                  HIP_TRY(SBV_EDEVICE, hipEventRecord(after_prep, c.stream));
+                                  return enqueue_k256(c, c.d_tuples, n, c.d_bitmap, c.stream);
+                              });
+}
+
 // ---- batch signing (p256_sign.h) ----------------------------------------------------------------------
 extern "C" int sbv_p256_sign_batch_dev(const void* d_keys, uint32_t n_keys, const void* d_key_index, const void* d_digests, size_t n,
                                        void* d_sigs, void* d_ok, void* hip_stream) {
@@ -4114,24 +4175,103 @@ int verify_shard_msgs(Context& c, const uint8_t* msgs, const uint64_t* moff, con
         });
 }
 
+// The raw-messages form of the TUPLE path (sbv_p256_verify_msgs_sharded); c.mu held.  The pieces are verify_shard's (plan_tuple_pieces:
+// the first piece builds the signers' combs, the later ones find them), the uploads verify_shard_msgs's with the signers' keys in place
+// of slots: piece i's message bytes, DER signatures, the slices of the caller's offset tables as they are and its keys (behind the
+// signatures, at a multiple of 16 bytes) go up into one of two staging sets; k_msg_frontend_tuples writes the piece's tuples into
+// stage[w] — c.d_tuples or its twin, which no copy writes on this path — and the generic step and the quorum kernel (distinct keys)
+// read them there, all on c.stream.
+int verify_shard_msgs_tuples(Context& c, const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* h_keys,
+                             size_t first, size_t m, size_t group, u32 quorum, uint8_t* d_slot, uint8_t* d_qslot, double* h2d_us, double* kern_us) {
+    if (!c.ready) { g_err = "device not initialised"; return SBV_ENOTINIT; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    sbv::PiecePlan p;
+    int rc = sbv::plan_tuple_pieces(m, shard_granule(group), c.kc_on[0] && c.group_enabled, g_shard_piece, kMaxChunk, &p, &g_err);
+    if (rc != SBV_OK) return rc;
+    const size_t chunk = p.chunk;
+    const bool two = p.pieces > 1;
+    size_t max_mb = 0, max_sb = 0;                 // staging for the largest piece, grown before anything is enqueued
+    for (size_t off = 0; off < m; off += chunk) {
+        const size_t k = m - off < chunk ? m - off : chunk;
+        // the plausibility bounds of verify_shard_msgs on the piece boundaries; every entry between them is checked by its lane
+        if (moff[first + off + k] < moff[first + off] || soff[first + off + k] < soff[first + off] ||
+            moff[first + off + k] - moff[first + off] > (uint64_t)k * 65536 || soff[first + off + k] - soff[first + off] > (uint64_t)k * 4096) {
+            g_err = "offset table is not monotone";
+            return SBV_EINVAL;
+        }
+        const size_t mb = (size_t)(moff[first + off + k] - moff[first + off]), sb = (size_t)(soff[first + off + k] - soff[first + off]);
+        if (mb > max_mb) max_mb = mb;
+        if (sb > max_sb) max_sb = sb;
+    }
+    const size_t kmax = m < chunk ? m : chunk;
+    const size_t koff = (max_sb + 15) & ~(size_t)15;        // the keys of a piece, behind its signatures
+    rc = ensure_capacity(c, kmax);
+    if (rc == SBV_OK) rc = grow(c.d_msgs, c.msgs_cap, max_mb + 16);
+    if (rc == SBV_OK) rc = grow(c.d_sigs, c.sigs_cap, koff + kmax * 64 + 16);
+    if (rc == SBV_OK) rc = grow(c.d_moff, c.moff_cap, kmax + 1);
+    if (rc == SBV_OK) rc = grow(c.d_soff, c.soff_cap, kmax + 1);
+    ShardBuffers& sbuf = g_shard[c.device];
+    if (rc == SBV_OK && two) {
+        rc = grow_bytes(sbuf.d_stage2, sbuf.stage2_cap, chunk * SBV_TUPLE_BYTES);
+        if (rc == SBV_OK) rc = grow_bytes(sbuf.d_msgs2, sbuf.msgs2_cap, max_mb + 16);
+        if (rc == SBV_OK) rc = grow_bytes(sbuf.d_sigs2, sbuf.sigs2_cap, koff + kmax * 64 + 16);
+        if (rc == SBV_OK) rc = grow_bytes(sbuf.d_moff2, sbuf.moff2_cap, (kmax + 1) * sizeof(uint64_t));
+        if (rc == SBV_OK) rc = grow_bytes(sbuf.d_soff2, sbuf.soff2_cap, (kmax + 1) * sizeof(uint64_t));
+        if (rc == SBV_OK) rc = ensure_copy_stream(c);
+    }
+    if (rc != SBV_OK) return rc;
+    struct Set { uint8_t *msgs, *sigs; uint64_t *moff, *soff; uint8_t* tuples; };
+    const Set set[2] = {{c.d_msgs, c.d_sigs, c.d_moff, c.d_soff, c.d_tuples},
+                        {sbuf.d_msgs2, sbuf.d_sigs2, reinterpret_cast<uint64_t*>(sbuf.d_moff2), reinterpret_cast<uint64_t*>(sbuf.d_soff2), sbuf.d_stage2}};
+    return sbv::run_pieces({c.stream, c.copy_stream, nullptr}, c.busy, &c.busy_valid, m, chunk, "verify_shard_msgs_tuples", h2d_us, kern_us, &g_err,
+        [&](size_t, size_t off, size_t k, int w, hipStream_t up) {
+            const size_t a = first + off;
+            const size_t mb = (size_t)(moff[a + k] - moff[a]), sb = (size_t)(soff[a + k] - soff[a]);
+            const Set& s = set[w];
+            hipError_t e = mb ? hipMemcpyAsync(s.msgs, msgs + moff[a], mb, hipMemcpyHostToDevice, up) : hipSuccess;
+            if (e == hipSuccess && sb) e = hipMemcpyAsync(s.sigs, sigs + soff[a], sb, hipMemcpyHostToDevice, up);
+            if (e == hipSuccess) e = hipMemcpyAsync(s.sigs + koff, h_keys + a * 64, k * 64, hipMemcpyHostToDevice, up);
+            if (e == hipSuccess) e = hipMemcpyAsync(s.moff, moff + a, (k + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up);
+            if (e == hipSuccess) e = hipMemcpyAsync(s.soff, soff + a, (k + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up);
+            return e;
+        },
+        [&](size_t, size_t off, size_t k, int w, hipStream_t stream) {
+            const size_t a = first + off;
+            const Set& s = set[w];
+            const hipError_t e = sbv::launch_msg_frontend_tuples(s.msgs, s.moff, s.sigs, s.soff, s.sigs + koff, k, reinterpret_cast<u32*>(s.tuples), stream,
+                                                                 moff[a], soff[a], (size_t)(moff[a + k] - moff[a]), (size_t)(soff[a + k] - soff[a]));
+            if (e != hipSuccess) return fail(SBV_EDEVICE, "verify_shard_msgs_tuples", e);
+            const int st = enqueue(c, s.tuples, k, d_slot + off / 8, stream, nullptr);
+            if (st == SBV_OK) launch_quorum(s.tuples, nullptr, d_slot, d_qslot, off, k, group, quorum, stream);
+            return st;
+        });
+}
+
 }  // namespace
 
 // The per-device minimum the sharded entry uses for THIS batch (host memory, no device): the keys of 256 evenly spaced tuples
 // are compared; at most 32 distinct ones among them = a consenter-style batch (a batch over K equally likely signers shows
 // about min(K, 256 (1 - e^(-256/K)) ...) distinct keys in such a sample: 16 for K = 16, 226 for K = 1024).
-extern "C" size_t sbv_shard_min_for(const uint8_t* tuples, size_t n, size_t group) {
-    (void)group;
-    if (g_shard_min_env || !tuples || n == 0) return g_shard_min;
+namespace {
+// keys: the first of n 64-byte keys `stride` bytes apart
+size_t shard_min_of_keys(const uint8_t* keys, size_t n, size_t stride) {
+    if (g_shard_min_env || !keys || n == 0) return g_shard_min;
     const size_t samples = n < 256 ? n : 256;
     const uint8_t* seen[33];
     size_t distinct = 0;
     for (size_t j = 0; j < samples && distinct <= 32; ++j) {
-        const uint8_t* k = tuples + (j * n / samples) * SBV_TUPLE_BYTES + 96;
+        const uint8_t* k = keys + (j * n / samples) * stride;
         bool dup = false;
         for (size_t d = 0; d < distinct && !dup; ++d) dup = memcmp(seen[d], k, 64) == 0;
         if (!dup) seen[distinct++] = k;
     }
     return distinct <= 32 ? g_shard_min_few : g_shard_min;
+}
+}  // namespace
+
+extern "C" size_t sbv_shard_min_for(const uint8_t* tuples, size_t n, size_t group) {
+    (void)group;
+    return shard_min_of_keys(tuples ? tuples + 96 : nullptr, n, SBV_TUPLE_BYTES);
 }
 
 extern "C" size_t sbv_shard_plan(size_t n, int devices, size_t group, size_t min_per_device, size_t* first) {
@@ -4496,6 +4636,23 @@ extern "C" int sbv_p256_verify_msgs_keyed_sharded(const uint8_t* msgs, const uin
     return sharded_contiguous(n, group, quorum, accept_bitmap, quorum_bitmap, info, sc.devs, sc.use_rccl, g_shard_min_env ? g_shard_min : g_shard_min_few,
                               [&](Context& c, size_t first, size_t count, uint8_t* d_bits, uint8_t* d_q, double* h2d_us, double* kern_us) {
                                   return verify_shard_msgs(c, msgs, msg_offsets, sigs, sig_offsets, slots, first, count, group, quorum, d_bits, d_q, h2d_us, kern_us);
+                              }, sc.t0);
+}
+
+// Raw messages + DER signatures + the signers' keys, sharded: the tuple path's plan and pieces with SHA-256 and the DER parse on every
+// device's share.  Always the contiguous split, whatever sbv_shard_mode says: a key-affine split would send every message to every device.
+extern "C" int sbv_p256_verify_msgs_sharded(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
+                                            const uint8_t* keys, size_t n, size_t group, uint32_t quorum, uint8_t* accept_bitmap,
+                                            uint8_t* quorum_bitmap, sbv_shard_info* info) {
+    // the offset tables as in sbv_p256_verify_msgs_keyed_sharded: never decreasing, and they need not start at 0
+    const bool tables = msg_offsets && sig_offsets && keys && accept_bitmap;
+    const bool bases = !tables || n == 0 || !((msg_offsets[n] && !msgs) || (sig_offsets[n] && !sigs));
+    ShardedCall sc;
+    const int rc = sharded_begin(sc, info, n, tables, group, quorum, quorum_bitmap, nullptr, bases);
+    if (rc != SBV_OK || n == 0) return rc;
+    return sharded_contiguous(n, group, quorum, accept_bitmap, quorum_bitmap, info, sc.devs, sc.use_rccl, shard_min_of_keys(keys, n, 64),
+                              [&](Context& c, size_t first, size_t count, uint8_t* d_bits, uint8_t* d_q, double* h2d_us, double* kern_us) {
+                                  return verify_shard_msgs_tuples(c, msgs, msg_offsets, sigs, sig_offsets, keys, first, count, group, quorum, d_bits, d_q, h2d_us, kern_us);
                               }, sc.t0);
 }
 

@@ -145,4 +145,13 @@ SBV_HD void msg_frontend_lane(const uint8_t* msg, size_t mlen, const uint8_t* de
     }
 }
 
+// The same lane for the generic verifiers: msg_frontend_lane plus the signer's 64 key bytes Qx | Qy (16 dwords, copied as they are:
+// the verifier judges them, as it does for uploaded tuples), written as the 160-byte tuple r | s | hash | Qx | Qy (40 dwords) that
+// k_p256_prep and k_k256_prep consume.  A DER failure leaves r = s = 0.  The lane knows nothing of the curve.
+SBV_HD void msg_frontend_tuple_lane(const uint8_t* msg, size_t mlen, const uint8_t* der, size_t dlen, const u32* key64, u32* tuple_out) {
+    msg_frontend_lane(msg, mlen, der, dlen, tuple_out);
+    SBV_UNROLL
+    for (int i = 0; i < 16; ++i) tuple_out[24 + i] = key64[i];
+}
+
 }  // namespace sbv

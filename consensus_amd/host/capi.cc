@@ -74,6 +74,12 @@ void* sbvh_verifier_new(int backend_kind, int device, backend_fn fn, void* user,
 }
 void sbvh_verifier_free(void* h) { delete (VHandle*)h; }
 uint64_t sbvh_backend_keyed_batches(void* h) { return ((VHandle*)h)->be->keyed_batches(); }
+uint64_t sbvh_backend_msgs_batches(void* h) { return ((VHandle*)h)->be->msgs_batches(); }
+// the host route's tuples for n ECDSA requests (verifier.h: make_tuples_ecdsa), for tools that time it against the device front end
+void sbvh_make_tuples_ecdsa(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n,
+                            uint8_t* tuples) {
+    make_tuples_ecdsa(msgs, moff, sigs, soff, keys, n, tuples);
+}
 uint64_t sbvh_backend_widened_keys(void* h) { return ((VHandle*)h)->be->widened_keys(); }
 // the backend's Ed25519 registry as the Verifier sees it: slot of a 32-byte encoding (-1 = no registry)
 long sbvh_backend_register_ed25519(void* h, const uint8_t* a32) { return ((VHandle*)h)->be->register_key_ed25519(a32); }

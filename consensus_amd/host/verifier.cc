@@ -114,6 +114,20 @@ void parallel_chunks(size_t n, F fn) {
 }
 }  // namespace
 
+// What the host workers do for a batch of ECDSA requests whose signers hold no slot, when the backend has no front end for them:
+// tuple i = strict DER parse of signature i (a failure leaves r = s = 0) | SHA-256 of message i | key i, over the worker pool.
+void make_tuples_ecdsa(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n,
+                       uint8_t* tuples) {
+    parallel_chunks(n, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) {
+            uint8_t* out = tuples + i * 160;
+            if (sbv_p256_parse_der(sigs + soff[i], (size_t)(soff[i + 1] - soff[i]), out) != SBV_OK) memset(out, 0, 64);
+            sha256(msgs + moff[i], (size_t)(moff[i + 1] - moff[i]), out + 64);
+            memcpy(out + 96, keys + i * 64, 64);
+        }
+    });
+}
+
 // ---- backends ------------------------------------------------------------------------------------
 // the defaults of the Schnorr entries: a loop over the host forms (k256_host.cc)
 int Backend::schnorr_verify_k256(const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint8_t* ok) {
@@ -258,9 +272,33 @@ class SbvBackend : public Backend {
         if (n > 32768) return sbv_p256_verify_msgs_keyed_sharded(msgs, moff, sigs, soff, slots, n, 0, 0, bitmap, nullptr, nullptr);
         return sbv_p256_verify_msgs_keyed(msgs, moff, sigs, soff, slots, n, bitmap);
     }
+    // unregistered signers: the keys travel with the call; one device call each
+    int verify_msgs(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n,
+                    uint8_t* bitmap) override {
+        if (rc_ != SBV_OK) return rc_;
+        ++msgs_batches_;
+        // a proposal of many thousands of requests: every GPU of the node, uploads in pieces beside SHA-256 + DER + verification
+        if (n > 32768) return sbv_p256_verify_msgs_sharded(msgs, moff, sigs, soff, keys, n, 0, 0, bitmap, nullptr, nullptr);
+        return sbv_p256_verify_msgs(msgs, moff, sigs, soff, keys, n, bitmap);
+    }
+    int verify_msgs_k256(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n,
+                         uint8_t* bitmap) override {
+        if (rc_ != SBV_OK) return rc_;
+        if (n > ((size_t)1 << 21)) return -2;          // beyond the entry's limit: the caller takes the tuple path
+        ++msgs_batches_;
+        return sbv_secp256k1_verify_msgs(msgs, moff, sigs, soff, keys, n, bitmap);
+    }
+    int verify_ed25519_msgs(const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* moff, size_t n, uint8_t* bitmap) override {
+        if (rc_ != SBV_OK) return rc_;
+        if (n > ((size_t)1 << 21)) return -2;          // beyond the entry's limit: the caller takes the tuple path
+        ++msgs_batches_;
+        return sbv_ed25519_verify_msgs(sigs, pks, msgs, moff, n, bitmap);
+    }
+    uint64_t msgs_batches() override { return msgs_batches_.load(); }
  private:
     bool all_;
     int rc_;
+    std::atomic<uint64_t> msgs_batches_{0};
 };
 class CallbackBackend : public Backend {
  public:
@@ -413,6 +451,32 @@ class CallbackBackend : public Backend {
         return verify_k256_keyed(rsh.data(), slots, n, bitmap);
     }
     std::vector<uint32_t> last_k256_slots() override { std::lock_guard<std::mutex> lk(mu_); return last_k256_slots_; }
+    // stand-ins for the generic front ends (sbv_p256_verify_msgs, sbv_secp256k1_verify_msgs, sbv_ed25519_verify_msgs): SHA-256 + strict
+    // DER (Ed25519: SHA-512 mod L) on the host, the keys as they came, then the callback
+    int verify_msgs(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n,
+                    uint8_t* bitmap) override {
+        std::vector<uint8_t> tuples(n * 160);
+        make_tuples_ecdsa(msgs, moff, sigs, soff, keys, n, tuples.data());
+        { std::lock_guard<std::mutex> lk(mu_); ++msgs_batches_; }
+        return fn_(tuples.data(), n, bitmap, user_);
+    }
+    int verify_msgs_k256(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n,
+                         uint8_t* bitmap) override {
+        return verify_msgs(msgs, moff, sigs, soff, keys, n, bitmap);          // the stand-in knows which scheme its test runs
+    }
+    int verify_ed25519_msgs(const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* moff, size_t n, uint8_t* bitmap) override {
+        std::vector<uint8_t> tuples(n * 128, 0);
+        parallel_chunks(n, [&](size_t lo, size_t hi) {
+            for (size_t i = lo; i < hi; ++i) {
+                memcpy(&tuples[i * 128], sigs + i * 64, 64);
+                memcpy(&tuples[i * 128 + 64], pks + i * 32, 32);
+                ed25519_hram(sigs + i * 64, pks + i * 32, (const char*)msgs + moff[i], (size_t)(moff[i + 1] - moff[i]), &tuples[i * 128 + 96]);
+            }
+        });
+        { std::lock_guard<std::mutex> lk(mu_); ++msgs_batches_; }
+        return fn_(tuples.data(), n, bitmap, user_);
+    }
+    uint64_t msgs_batches() override { std::lock_guard<std::mutex> lk(mu_); return msgs_batches_; }
     // the CPU form of sbv_secp256k1_schnorr_verify_keyed: a loop over the host verifier under the slot's Qx; a slot out of range or a
     // key that is no curve point is a reject
     int schnorr_verify_keyed_k256(const uint8_t* msgs, const uint8_t* sigs, const uint32_t* slots, size_t n, uint8_t* ok) override {
@@ -454,6 +518,7 @@ class CallbackBackend : public Backend {
     std::vector<std::string> ed_keys_;
     std::vector<long> ed_widened_;
     uint64_t keyed_batches_ = 0;
+    uint64_t msgs_batches_ = 0;
 };
 }  // namespace
 std::shared_ptr<Backend> make_sbv_backend(int device) { return std::make_shared<SbvBackend>(device); }
@@ -590,6 +655,38 @@ int Coalescer::submit_many_k256_msgs_keyed(const uint8_t* msgs, const uint64_t* 
 int Coalescer::submit_many_msgs_keyed(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint32_t* slots,
                                       size_t n, uint8_t* bitmap) {
     const int rc = be_->verify_msgs_keyed(msgs, moff, sigs, soff, slots, n, bitmap);
+    if (rc != -2) {
+        std::lock_guard<SpinLock> lk(mu_);
+        ++st_.batches;
+        if (n > st_.max_batch) st_.max_batch = n;
+    }
+    return rc;
+}
+
+int Coalescer::submit_many_msgs(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n,
+                                uint8_t* bitmap) {
+    const int rc = be_->verify_msgs(msgs, moff, sigs, soff, keys, n, bitmap);
+    if (rc != -2) {
+        std::lock_guard<SpinLock> lk(mu_);
+        ++st_.batches;
+        if (n > st_.max_batch) st_.max_batch = n;
+    }
+    return rc;
+}
+
+int Coalescer::submit_many_k256_msgs(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n,
+                                     uint8_t* bitmap) {
+    const int rc = be_->verify_msgs_k256(msgs, moff, sigs, soff, keys, n, bitmap);
+    if (rc != -2) {
+        std::lock_guard<SpinLock> lk(mu_);
+        ++st_.batches;
+        if (n > st_.max_batch) st_.max_batch = n;
+    }
+    return rc;
+}
+
+int Coalescer::submit_many_ed25519_msgs(const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* moff, size_t n, uint8_t* bitmap) {
+    const int rc = be_->verify_ed25519_msgs(sigs, pks, msgs, moff, n, bitmap);
     if (rc != -2) {
         std::lock_guard<SpinLock> lk(mu_);
         ++st_.batches;
@@ -1125,8 +1222,31 @@ Status Verifier::VerifyProposal(const Proposal& p, std::vector<RequestInfo>* req
             });
             rc = co_.submit_many_ed25519_msgs_keyed(sbuf.data(), mbuf.data(), moff.data(), slots.data(), n, bitmap.data());
         }
+        if (rc == -2 && unkeyed.load()) {
+            // some client has no slot: raw signed bytes + signatures + the clients' own keys to the backend's generic front end (ECDSA:
+            // SHA-256, the strict DER parse and the tuple layout on the device, sbv_p256_verify_msgs / sbv_secp256k1_verify_msgs;
+            // Ed25519: SHA-512 mod L on the device, sbv_ed25519_verify_msgs); the host only lays bytes out.  A signature that is not
+            // 64 bytes is the Ed25519 caller's reject: S = 2^256 - 1.
+            const size_t kb = ed() ? 32 : 64;
+            std::vector<uint64_t> moff(n + 1), soff(n + 1);
+            uint64_t a = 0, b = 0;
+            for (size_t i = 0; i < n; ++i) { moff[i] = a; soff[i] = b; a += views[i].signed_len; b += ed() ? 64 : views[i].sig_len; }
+            moff[n] = a; soff[n] = b;
+            std::vector<uint8_t> mbuf(a + 1), sbuf(b + 1), kbuf(n * kb);
+            parallel_chunks(n, [&](size_t lo, size_t hi) {
+                for (size_t i = lo; i < hi; ++i) {
+                    memcpy(&mbuf[moff[i]], pl.data() + views[i].signed_off, views[i].signed_len);
+                    if (!ed() || views[i].sig_len == 64) memcpy(&sbuf[soff[i]], pl.data() + views[i].sig_off, views[i].sig_len);
+                    else { memset(&sbuf[i * 64], 0, 32); memset(&sbuf[i * 64 + 32], 0xFF, 32); }
+                    memcpy(&kbuf[i * kb], keys[i]->data(), kb);
+                }
+            });
+            rc = ed()     ? co_.submit_many_ed25519_msgs(sbuf.data(), kbuf.data(), mbuf.data(), moff.data(), n, bitmap.data())
+                 : k256() ? co_.submit_many_k256_msgs(mbuf.data(), moff.data(), sbuf.data(), soff.data(), kbuf.data(), n, bitmap.data())
+                          : co_.submit_many_msgs(mbuf.data(), moff.data(), sbuf.data(), soff.data(), kbuf.data(), n, bitmap.data());
+        }
         if (rc == -2) {
-            // no front end, unregistered clients or another scheme: tuples built by the host workers (SHA-256, strict DER)
+            // no front end or another scheme: tuples built by the host workers (SHA-256, strict DER)
             std::vector<uint8_t> tuples(n * tb);
             parallel_chunks(n, [&](size_t lo, size_t hi) {
                 for (size_t i = lo; i < hi; ++i) {

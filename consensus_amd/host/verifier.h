@@ -122,7 +122,29 @@ class Backend {
                                   const uint32_t* slots, size_t n, uint8_t* bitmap) {
         (void)msgs; (void)moff; (void)sigs; (void)soff; (void)slots; (void)n; (void)bitmap; return -2;
     }
+    // Raw messages for signers WITHOUT a slot (include/sbv.h: sbv_p256_verify_msgs, sbv_secp256k1_verify_msgs): raw messages + DER
+    // signatures + the signers' keys, n x 64 bytes Qx | Qy; SHA-256, the DER parse and the tuple layout by the backend.  -2 when
+    // unsupported: the caller builds the tuples itself.  The callback backend loops over SHA-256, the strict parse and the callback; the
+    // GPU backend makes one device call (P-256 above 32 768 requests: the sharded entry, as verify_msgs_keyed).
+    virtual int verify_msgs(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n,
+                            uint8_t* bitmap) {
+        (void)msgs; (void)moff; (void)sigs; (void)soff; (void)keys; (void)n; (void)bitmap; return -2;
+    }
+    virtual int verify_msgs_k256(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n,
+                                 uint8_t* bitmap) {
+        (void)msgs; (void)moff; (void)sigs; (void)soff; (void)keys; (void)n; (void)bitmap; return -2;
+    }
+    // ... and the Ed25519 form (sbv_ed25519_verify_msgs): n signatures of 64 bytes + n keys of 32 bytes + raw messages, k hashed by the
+    // backend; -2 when unsupported
+    virtual int verify_ed25519_msgs(const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* moff, size_t n, uint8_t* bitmap) {
+        (void)sigs; (void)pks; (void)msgs; (void)moff; (void)n; (void)bitmap; return -2;
+    }
+    virtual uint64_t msgs_batches() { return 0; }       // test hook: how many batches the three forms above ran
 };
+// The host route of a batch of ECDSA requests (what VerifyProposal's workers build when no front end takes the batch): tuple i = strict
+// DER parse of signature i (zeros when refused) | SHA-256(message i) | keys[64 i ..), n x 160 bytes, over the worker pool.
+void make_tuples_ecdsa(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n,
+                       uint8_t* tuples);
 std::shared_ptr<Backend> make_sbv_backend(int device);     // device >= 0: sbv_init(device); device < 0: sbv_init_all() + the sharded entry
 typedef int (*backend_fn)(const uint8_t* tuples, size_t n, uint8_t* bitmap, void* user);
 std::shared_ptr<Backend> make_callback_backend(backend_fn fn, void* user, bool with_key_registry = false);
@@ -182,6 +204,11 @@ class Coalescer {
     // raw messages + DER signatures + slots through the backend's front end (-2 when it has none)
     int submit_many_msgs_keyed(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint32_t* slots, size_t n,
                                uint8_t* bitmap);
+    // raw messages + DER signatures + the signers' keys (no slots) through the backend's generic front ends (-2 when it has none)
+    int submit_many_msgs(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n, uint8_t* bitmap);
+    int submit_many_k256_msgs(const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys, size_t n,
+                              uint8_t* bitmap);
+    int submit_many_ed25519_msgs(const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* moff, size_t n, uint8_t* bitmap);
     Backend& backend() { return *be_; }
     CoalescerStats stats();
     // How many submissions a burst is expected to bring (N-1 commit votes: view.go:537-541); the dispatcher ships as soon as

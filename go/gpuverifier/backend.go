@@ -140,6 +140,16 @@ type K256SchnorrKeyed interface {
 	VerifyBatchSchnorrKeyed(msgs [][32]byte, sigs [][64]byte, slots []uint32) (ok []bool, err error)
 }
 
+// RawMessageVerifier is the raw-message form of Verify for signers that hold no slot (sbv_p256_verify_msgs, its sharded form and
+// sbv_secp256k1_verify_msgs): Msg, Sig (ASN.1 DER) and the 64-byte key Qx|Qy of every item go to the device as they are; SHA-256, the
+// strict DER parse and the tuple layout run there, so the host only lays bytes out.  ok[i] is what Verify reports for item i: a
+// signature that does not parse and a key the verifier refuses are rejects.  SchemeP256 and SchemeSecp256k1 only; Slot is ignored.
+// What VerifyProposal's K client requests take when the clients are not registered.  An optional interface beside Backend like the
+// key registries, so that existing backends need no change: callers type-assert for it.
+type RawMessageVerifier interface {
+	VerifyMsgs(scheme Scheme, items []Item) (ok []bool, err error)
+}
+
 // ErrNoBatchSigner: the backend has no batch signing entry (the pure-Go backend).
 var ErrNoBatchSigner = errors.New("gpuverifier: backend has no batch signer")
 

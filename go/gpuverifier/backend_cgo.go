@@ -39,6 +39,9 @@ const (
 //	SchemeEd25519, every item has a slot       sbv_ed25519_verify_msgs_keyed  signatures + raw messages + slots (SHA-512 on the device)
 //	SchemeSecp256k1, every item has a slot     sbv_secp256k1_verify_msgs_keyed (n >= frontEndFrom) / sbv_secp256k1_verify_batch_keyed
 //	SchemeEd25519 / SchemeSecp256k1            sbv_ed25519_verify_msgs / sbv_secp256k1_verify_batch
+//
+// and, beside Verify, VerifyMsgs (the optional RawMessageVerifier) for signers without a slot: sbv_p256_verify_msgs_sharded /
+// sbv_secp256k1_verify_msgs — raw messages + DER + keys, SHA-256, the DER parse and the tuple layout on the device.
 type gpuBackend struct {
 	jobs     chan *gpuJob
 	mu       sync.Mutex
@@ -361,6 +364,63 @@ func (b *gpuBackend) Verify(scheme Scheme, items []Item) (ok []bool, err error) 
 		default:
 			ok, err = b.verifyP256(items)
 		}
+	})
+	return ok, err
+}
+
+// keysOf lays the items' 64-byte keys back to back; an item without one gets the all-zero key, which is not on either curve.
+func keysOf(items []Item) []byte {
+	keys := make([]byte, 64*len(items))
+	for i := range items {
+		if len(items[i].Key) == 64 {
+			copy(keys[64*i:], items[i].Key)
+		}
+	}
+	return keys
+}
+
+// VerifyMsgs (RawMessageVerifier): raw messages + DER signatures + keys, hashed, parsed and laid out as tuples on the device.
+// SchemeP256: the whole batch in one call of the sharded entry (the library splits it by device and by piece; no 2^21 limit; a batch
+// that is not worth splitting goes whole to one device).  SchemeSecp256k1: chunks of at most 2^21 on the first device.
+func (b *gpuBackend) VerifyMsgs(scheme Scheme, items []Item) (ok []bool, err error) {
+	n := len(items)
+	if n == 0 {
+		return nil, nil
+	}
+	if scheme != SchemeP256 && scheme != SchemeSecp256k1 {
+		return nil, errors.New("gpuverifier: VerifyMsgs takes SchemeP256 or SchemeSecp256k1")
+	}
+	b.on(func() {
+		bitmap := make([]byte, (n+7)/8)
+		keys := keysOf(items)
+		if scheme == SchemeP256 {
+			msgs, moff := packMsgs(func(i int) []byte { return items[i].Msg }, n)
+			sigs, soff := packMsgs(func(i int) []byte { return items[i].Sig }, n)
+			rc := C.sbv_p256_verify_msgs_sharded(u8(msgs), (*C.uint64_t)(unsafe.Pointer(&moff[0])), u8(sigs),
+				(*C.uint64_t)(unsafe.Pointer(&soff[0])), u8(keys), C.size_t(n), 0, 0, u8(bitmap), nil, nil)
+			if rc != 0 {
+				err = lastError()
+				return
+			}
+			ok = bitmapToBools(bitmap, n)
+			return
+		}
+		for lo := 0; lo < n; lo += frontEndMax {
+			hi := lo + frontEndMax
+			if hi > n {
+				hi = n
+			}
+			m := hi - lo
+			msgs, moff := packMsgs(func(i int) []byte { return items[lo+i].Msg }, m)
+			sigs, soff := packMsgs(func(i int) []byte { return items[lo+i].Sig }, m)
+			rc := C.sbv_secp256k1_verify_msgs(u8(msgs), (*C.uint64_t)(unsafe.Pointer(&moff[0])), u8(sigs),
+				(*C.uint64_t)(unsafe.Pointer(&soff[0])), u8(keys[64*lo:]), C.size_t(m), u8(bitmap[lo/8:])) // lo is a multiple of 2^21: whole bitmap bytes
+			if rc != 0 {
+				err = lastError()
+				return
+			}
+		}
+		ok = bitmapToBools(bitmap, n)
 	})
 	return ok, err
 }

@@ -601,6 +601,30 @@ int sbv_secp256k1_verify_batch_keyed_dev(const void* d_rsh, const void* d_slots,
 int sbv_secp256k1_verify_msgs_keyed(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs,
                                     const uint64_t* sig_offsets, const uint32_t* slots, size_t n, uint8_t* accept_bitmap);
 
+/* Raw messages for the GENERIC verifiers (SURVEY.md §8(f) row 1 for signers that hold no slot: VerifyProposal's K client requests
+ * when the clients are not registered, internal/bft/view.go:553-559).  The inputs of sbv_p256_verify_msgs_keyed with the signers'
+ * keys in place of slots: message i = msgs[msg_offsets[i] .. msg_offsets[i+1]), DER signature i = sigs[sig_offsets[i] ..
+ * sig_offsets[i+1]), keys = n x 64 bytes Qx | Qy, big-endian.  One kernel (consensus_amd/csrc/msg_frontend_kernels.hip, the same for
+ * both curves) hashes the messages (SHA-256), parses the signatures (strict DER) and writes the 160-byte tuples on the device; the
+ * tuple step then runs on them as on uploaded ones (grouped step, key-table cache and hot-key pools included).  Bit i equals what
+ * sbv_p256_verify_batch / sbv_secp256k1_verify_batch return for the tuple sbv_p256_parse_der(sig i) | sbv_sha256_batch(msg i) |
+ * keys[i]; for P-256 that is crypto/ecdsa.VerifyASN1(key i, sha256(msg i), sig i).  A signature that does not parse is a reject, and
+ * so is a key the verifier refuses (a coordinate >= p, a point off the curve, (0, 0)): return codes never mean "invalid".
+ *   SBV_ENOTINIT before sbv_init; n == 0 is SBV_OK and writes nothing; n > 2^21 is SBV_EINVAL, refused before any array is read;
+ *   a null msg_offsets, sig_offsets, keys or accept_bitmap is SBV_EINVAL (msgs may be null when every message is empty); an offset
+ *   table that does not start at 0 or that decreases is SBV_EINVAL.  A refused call leaves the library as it was.
+ *   prep_us of sbv_last_timing includes the front-end kernel (P-256: and stage A).
+ * Measured (one MI355X, 2^20 requests over 1 024 signers, pageable host memory; tools/bench_verify_msgs.py): against SHA-256 + strict DER on 16 CPUs
+ * followed by the tuple entry, one call of these entries takes, for messages of 64 / 200 / 1 024 bytes, P-256 11.50 → 7.56 / 13.74 → 10.01 / 37.97 → 26.80 ms and secp256k1 12.40 → 9.47 / 15.19 → 12.47 / 33.11 → 29.02 ms
+ * (medians of 10 calls).  At no measured size is the entry slower than that route.  The call itself is longer than the tuple call alone (more bytes go up, and
+ * the SHA-256 loader reads byte by byte: the front-end kernel takes 0.38 / 0.66 / 2.23 ms per 2^20 messages of those sizes); what it saves is the host's pass.
+ * The sharded form overlaps the uploads with the kernels, piece by piece: 5.61 / 8.39 / 23.94 ms on one device. */
+int sbv_p256_verify_msgs(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
+                         const uint8_t* keys, size_t n, uint8_t* accept_bitmap);
+int
+sbv_secp256k1_verify_msgs(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
+                          const uint8_t* keys, size_t n, uint8_t* accept_bitmap);
+
 /* Strict DER parse of an ECDSA-Sig-Value with Go x/crypto/cryptobyte rules
  * (crypto/ecdsa.parseSignature): out = r | s, 32 bytes each, big-endian, zero padded.
  * Returns SBV_OK or SBV_EPARSE (then out is all zero, which every verify rejects). */
@@ -809,6 +833,16 @@ int sbv_p256_verify_batch_keyed_sharded(const uint8_t* rsh, const uint32_t* slot
 int sbv_p256_verify_msgs_keyed_sharded(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
                                        const uint32_t* slots, size_t n, size_t group, uint32_t quorum, uint8_t* accept_bitmap,
                                        uint8_t* quorum_bitmap, sbv_shard_info* info);
+/* The raw-messages form of sbv_p256_verify_batch_sharded: sbv_p256_verify_msgs's inputs (keys, not slots: no registry is read)
+ * through the tuple entry's plan and pieces (2^18 signatures while the key-table cache is on; SBV_SHARD_PIECE), SHA-256 and the strict
+ * DER parse on every device over its share, piece by piece beside the uploads.  No 2^21 limit; the offset tables need not start at 0;
+ * a piece whose table slice decreases or is implausible (more than 64 KiB per message or 4 KiB per signature on average) is
+ * SBV_EINVAL.  The per-device minimum comes from the same 256-key sample as sbv_shard_min_for, taken from `keys`.  Quorum bits count
+ * DISTINCT keys.  This entry ALWAYS splits contiguously, whatever sbv_shard_mode says: the key-affine split hands every device the
+ * whole batch, which here would mean every message to every device.  Verdicts as sbv_p256_verify_msgs. */
+int sbv_p256_verify_msgs_sharded(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
+                                 const uint8_t* keys, size_t n, size_t group, uint32_t quorum, uint8_t* accept_bitmap,
+                                 uint8_t* quorum_bitmap, sbv_shard_info* info);
 /* Key-affine partition (the other way to spread a batch: by signer instead of by position).  A contiguous split hands every
  * device signatures of every signer, so every device builds every key's tables — the part of a cold step that does not shrink
  * with the shard.  With sbv_shard_mode(1, parts) the sharded entry partitions by a hash of the public key: part p (on device
