@@ -546,6 +546,114 @@ def secp256k1_sign_batch_stream(d_keys_ptr: int, n_keys: int, d_index_ptr: int, 
                                                d_sigs_ptr, d_recid_ptr or None, d_ok_ptr, stream or None))
 
 
+ECDSA_SIGN_LOW_S = 1     # SBV_ECDSA_SIGN_LOW_S
+ECDSA_DER_MAX = 72       # SBV_ECDSA_DER_MAX
+
+
+def _msg_offsets(msgs, offsets=None):
+    """(blob, ctypes offset table, n) of a list of messages, or of a blob with a given offset list"""
+    if offsets is not None:
+        return (None if msgs is None else bytes(msgs)), (ctypes.c_uint64 * len(offsets))(*offsets), len(offsets) - 1
+    offs = (ctypes.c_uint64 * (len(msgs) + 1))()
+    acc = 0
+    for i, m in enumerate(msgs):
+        offs[i] = acc
+        acc += len(m)
+    offs[len(msgs)] = acc
+    return b"".join(msgs), offs, len(msgs)
+
+
+def sha256_msgs(msgs, offsets=None):
+    """sbv_sha256_msgs: SHA-256 of every message on the device (a list of messages, or a blob with `offsets`) -> a list of digests"""
+    lib = load()
+    blob, offs, n = _msg_offsets(msgs, offsets)
+    lib.sbv_sha256_msgs.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_char_p]
+    out = ctypes.create_string_buffer(max(1, 32 * n))
+    _check(lib.sbv_sha256_msgs(blob, offs, n, out))
+    return [out.raw[32 * i:32 * i + 32] for i in range(n)]
+
+
+def sha256_msgs_stream(d_msgs_ptr: int, d_offsets_ptr: int, n: int, d_digests_ptr: int, stream: int = 0) -> None:
+    """device pointers; asynchronous on `stream` under the stream contract of the _dev entries (include/sbv.h)"""
+    lib = load()
+    lib.sbv_sha256_msgs_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib.sbv_sha256_msgs_stream(d_msgs_ptr or None, d_offsets_ptr, n, d_digests_ptr, stream or None))
+
+
+def _ecdsa_sign_msgs(symbol, keys: bytes, msgs, key_index, low_s, offsets, with_recid):
+    lib = load()
+    blob, offs, n = _msg_offsets(msgs, offsets)
+    nk = len(keys) // 32
+    C, U64P = ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)
+    sigs, soff = ctypes.create_string_buffer(max(1, ECDSA_DER_MAX * n)), (ctypes.c_uint64 * (n + 1))()
+    recid, ok = ctypes.create_string_buffer(max(1, n)), ctypes.create_string_buffer(max(1, n))
+    idx = None if key_index is None else (ctypes.c_uint32 * n)(*key_index)
+    head = [C, ctypes.c_uint32, ctypes.c_void_p, C, U64P, ctypes.c_size_t, ctypes.c_uint32, C, U64P]
+    fn = getattr(lib, symbol)
+    fn.argtypes = head + ([C, C] if with_recid else [C])
+    flags = ECDSA_SIGN_LOW_S if low_s else 0
+    if with_recid:
+        _check(fn(keys, nk, idx, blob, offs, n, flags, sigs, soff, recid, ok))
+    else:
+        _check(fn(keys, nk, idx, blob, offs, n, flags, sigs, soff, ok))
+    return sigs.raw[:soff[n]], list(soff), recid.raw[:n], ok.raw[:n]
+
+
+def p256_sign_msgs(keys: bytes, msgs, key_index=None, low_s: bool = False, offsets=None):
+    """sbv_p256_sign_msgs: SHA-256, RFC 6979 ECDSA P-256 and DER on the device, one call.  keys: 32-byte private scalars (key_index[i],
+    default i % n_keys); msgs: a list of messages (or a blob with `offsets`); low_s replaces s > (n-1)/2 by n - s.  Returns
+    (sigs, sig_offsets, ok): the DER signatures packed back to back with their n + 1 offsets — the pair verify_msgs takes — and
+    ok[i] = 1 per produced signature (a refused item has an empty signature).  NOT constant-time: see include/sbv.h."""
+    sigs, soff, _, ok = _ecdsa_sign_msgs("sbv_p256_sign_msgs", keys, msgs, key_index, low_s, offsets, False)
+    return sigs, soff, ok
+
+
+def secp256k1_sign_msgs(keys: bytes, msgs, key_index=None, low_s: bool = False, offsets=None):
+    """sbv_secp256k1_sign_msgs: as p256_sign_msgs over secp256k1.  Returns (sigs, sig_offsets, recid, ok); recid[i] = the recovery id
+    0..3 (0 for a refused item).  NOT constant-time: see include/sbv.h."""
+    return _ecdsa_sign_msgs("sbv_secp256k1_sign_msgs", keys, msgs, key_index, low_s, offsets, True)
+
+
+def ecdsa_sign_msgs_workspace(n: int) -> int:
+    """sbv_ecdsa_sign_msgs_workspace: bytes of d_work for a _stream call of n messages"""
+    lib = load()
+    lib.sbv_ecdsa_sign_msgs_workspace.restype = ctypes.c_size_t
+    lib.sbv_ecdsa_sign_msgs_workspace.argtypes = [ctypes.c_size_t]
+    return lib.sbv_ecdsa_sign_msgs_workspace(n)
+
+
+def p256_sign_msgs_stream(d_keys_ptr: int, n_keys: int, d_index_ptr: int, d_msgs_ptr: int, d_offsets_ptr: int, n: int, d_records_ptr: int,
+                          d_len_ptr: int, d_ok_ptr: int, d_work_ptr: int, low_s: bool = False, stream: int = 0) -> None:
+    """device pointers; asynchronous on `stream` under the stream contract of the _dev entries (include/sbv.h)"""
+    lib = load()
+    V = ctypes.c_void_p
+    lib.sbv_p256_sign_msgs_stream.argtypes = [V, ctypes.c_uint32, V, V, V, ctypes.c_size_t, ctypes.c_uint32, V, V, V, V, V]
+    _check(lib.sbv_p256_sign_msgs_stream(d_keys_ptr, n_keys, d_index_ptr or None, d_msgs_ptr or None, d_offsets_ptr, n,
+                                         ECDSA_SIGN_LOW_S if low_s else 0, d_records_ptr, d_len_ptr, d_ok_ptr, d_work_ptr, stream or None))
+
+
+def secp256k1_sign_msgs_stream(d_keys_ptr: int, n_keys: int, d_index_ptr: int, d_msgs_ptr: int, d_offsets_ptr: int, n: int,
+                               d_records_ptr: int, d_len_ptr: int, d_recid_ptr: int, d_ok_ptr: int, d_work_ptr: int, low_s: bool = False,
+                               stream: int = 0) -> None:
+    """device pointers; asynchronous on `stream` under the stream contract of the _dev entries (include/sbv.h)"""
+    lib = load()
+    V = ctypes.c_void_p
+    lib.sbv_secp256k1_sign_msgs_stream.argtypes = [V, ctypes.c_uint32, V, V, V, ctypes.c_size_t, ctypes.c_uint32, V, V, V, V, V, V]
+    _check(lib.sbv_secp256k1_sign_msgs_stream(d_keys_ptr, n_keys, d_index_ptr or None, d_msgs_ptr or None, d_offsets_ptr, n,
+                                              ECDSA_SIGN_LOW_S if low_s else 0, d_records_ptr, d_len_ptr, d_recid_ptr or None, d_ok_ptr,
+                                              d_work_ptr, stream or None))
+
+
+def debug_ecdsa_der_op(curve: int, rs_list, low_s: bool = False):
+    """sbv_debug_ecdsa_der_op (test only): k_ecdsa_sig_finish on given 64-byte r | s -> a list of (72-byte record, length)"""
+    lib = load()
+    n = len(rs_list)
+    lib.sbv_debug_ecdsa_der_op.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+    rec, ln = ctypes.create_string_buffer(max(1, 72 * n)), ctypes.create_string_buffer(max(1, n))
+    _check(lib.sbv_debug_ecdsa_der_op(curve, ECDSA_SIGN_LOW_S if low_s else 0, b"".join(rs_list), rec, ln, n))
+    return [(rec.raw[72 * i:72 * i + 72], ln.raw[i]) for i in range(n)]
+
+
 def secp256k1_pubkeys(keys: bytes):
     """sbv_secp256k1_pubkeys: 32-byte private scalars -> (pubs, ok): m x 64 bytes Qx | Qy in one bytes object and ok[i] = 1 per key in
     [1, n-1] (otherwise 64 zero bytes).  NOT constant-time: see include/sbv.h."""

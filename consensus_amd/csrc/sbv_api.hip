@@ -41,6 +41,7 @@
 #include "k256_recover_kernels.h"
 #include "keccak_kernels.h"
 #include "msg_frontend_kernels.h"
+#include "ecdsa_sign_msgs_kernels.h"
 #include "k256_schnorr_kernels.h"
 #include "k256_schnorr_keyed_kernels.h"
 
@@ -3175,6 +3176,182 @@ extern "C" int sbv_debug_secp256k1_schnorr_keyed_op(int op, const uint8_t* in, c
     uint8_t* d_out = cb.alloc(n * 128);
     if (cb.good()) cb.launch(sbv::launch_k256_schnorr_keyed_op(d_in, d_sl, d_out, n, k256_reg_view(c), c.d_k256_gcomb, c.k256_gbits, c.stream));
     cb.download(out, d_out, n * 128);
+    return cb.finish();
+}
+
+// ---- raw-message ECDSA signing (ecdsa_sign_msgs.h, ecdsa_sign_msgs_kernels.hip) -----------------------------------------------
+// k_sha256_msgs -> the signing kernel of the curve, as sign_batch launches it -> k_ecdsa_sig_finish, on one stream.  Stateless apart
+// from the read-only combs of G: the _stream forms touch only buffers of the caller's (d_work holds the digests and r | s between the
+// kernels), so there is nothing of the library's to order and nothing to join back.
+namespace {
+constexpr uint64_t kAnyBytes = ~(uint64_t)0;        // mbytes of a _stream call: the caller vouches for the bytes behind d_msgs
+
+// c.mu held, the device current, arguments checked.  d_recid: secp256k1 only, may be null.
+int enqueue_sign_msgs(Context& c, int curve, const uint8_t* d_keys, u32 n_keys, const u32* d_idx, const uint8_t* d_msgs, const uint64_t* d_moff,
+                      uint64_t mbytes, size_t n, u32 flags, uint8_t* d_records, uint8_t* d_len, uint8_t* d_recid, uint8_t* d_ok, uint8_t* d_work,
+                      hipStream_t stream) {
+    uint8_t* d_dig = d_work;
+    uint8_t* d_rs = d_work + n * 32;
+    HIP_TRY(SBV_EDEVICE, sbv::launch_sha256_msgs(d_msgs, d_moff, n, mbytes, d_dig, d_len, stream));      // the refusal marks travel in d_len
+    if (curve == SBV_ECDSA_CURVE_P256) {
+        HIP_TRY(SBV_EDEVICE, sbv::launch_p256_sign(d_keys, n_keys, d_idx, d_dig, n, sbv::gcomb_make(c.d_g16r, c.g_bits), d_rs, d_ok, stream));
+        HIP_TRY(SBV_EDEVICE, sbv::launch_ecdsa_sig_finish(curve, d_rs, d_ok, true, n, (flags & SBV_ECDSA_SIGN_LOW_S) != 0, d_records,
+                                                          d_len, nullptr, d_ok, stream));
+    } else {
+        HIP_TRY(SBV_EDEVICE, sbv::launch_k256_sign(d_keys, n_keys, d_idx, d_dig, n, c.d_k256_gtab, flags, d_rs, d_recid, d_ok, stream));
+        HIP_TRY(SBV_EDEVICE, sbv::launch_ecdsa_sig_finish(curve, d_rs, d_ok, true, n, false, d_records, d_len, d_recid, d_ok, stream));
+    }
+    return SBV_OK;
+}
+
+int sign_msgs_stream(Context& c, int curve, const void* d_keys, uint32_t n_keys, const void* d_key_index, const void* d_msgs,
+                     const void* d_msg_offsets, size_t n, uint32_t flags, void* d_records, void* d_len, void* d_recid, void* d_ok, void* d_work,
+                     void* hip_stream) {
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (flags & ~SBV_ECDSA_SIGN_LOW_S) { g_err = "unknown flag"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!d_keys || !d_msg_offsets || !d_records || !d_len || !d_ok || !d_work || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
+    if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
+    if (misaligned(3, d_keys, d_key_index, d_records, d_work) || misaligned(7, d_msg_offsets)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    if (curve == SBV_ECDSA_CURVE_K256) {
+        const int rc = ensure_k256_table(c);
+        if (rc != SBV_OK) return rc;
+    }
+    return enqueue_sign_msgs(c, curve, static_cast<const uint8_t*>(d_keys), n_keys, static_cast<const u32*>(d_key_index),
+                             static_cast<const uint8_t*>(d_msgs), static_cast<const uint64_t*>(d_msg_offsets), kAnyBytes, n, flags,
+                             static_cast<uint8_t*>(d_records), static_cast<uint8_t*>(d_len), static_cast<uint8_t*>(d_recid),
+                             static_cast<uint8_t*>(d_ok), static_cast<uint8_t*>(d_work), static_cast<hipStream_t>(hip_stream));
+}
+
+int sign_msgs_host(Context& c, int curve, const uint8_t* keys, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs,
+                   const uint64_t* msg_offsets, size_t n, uint32_t flags, uint8_t* sigs, uint64_t* sig_offsets, uint8_t* recid, uint8_t* ok) {
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (flags & ~SBV_ECDSA_SIGN_LOW_S) { g_err = "unknown flag"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!keys || !msg_offsets || !sigs || !sig_offsets || !ok || n_keys == 0) { g_err = "null pointer or no keys"; return SBV_EINVAL; }
+    if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
+    size_t mbytes = 0;
+    int rc = check_offsets(msg_offsets, n, msgs, mbytes);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    if (curve == SBV_ECDSA_CURVE_K256 && (rc = ensure_k256_table(c)) != SBV_OK) return rc;
+    std::vector<uint8_t> rec(n * SBV_ECDSA_DER_MAX), len(n);
+    {
+        sbv::CallBuffers cb(c.stream, &g_err);
+        const uint8_t* d_keys = cb.upload(keys, (size_t)n_keys * 32, true);
+        uint8_t* d_msgs = cb.alloc(mbytes + 16);        // a buffer even when every message is empty (msgs may then be null)
+        cb.copy_in(d_msgs, msgs, mbytes);
+        const uint64_t* d_moff = cb.upload(msg_offsets, (n + 1) * sizeof(uint64_t));
+        const u32* d_idx = cb.upload(key_index, n * sizeof(u32));
+        uint8_t* d_work = cb.alloc(sbv_ecdsa_sign_msgs_workspace(n));
+        uint8_t* d_rec = cb.alloc(n * SBV_ECDSA_DER_MAX);
+        uint8_t* d_len = cb.alloc(n);
+        uint8_t* d_rid = recid ? cb.alloc(n) : nullptr;
+        uint8_t* d_ok = cb.alloc(n);
+        if (cb.good()) {
+            rc = enqueue_sign_msgs(c, curve, d_keys, n_keys, d_idx, d_msgs, d_moff, mbytes, n, flags, d_rec, d_len, d_rid, d_ok, d_work, c.stream);
+            cb.launch(hipSuccess);                      // something is in flight whatever rc says: the buffers wait for it
+            if (rc != SBV_OK) return rc;
+        }
+        cb.download(rec.data(), d_rec, rec.size());
+        cb.download(len.data(), d_len, n);
+        cb.download(recid, d_rid, n);
+        cb.download(ok, d_ok, n);
+        if ((rc = cb.finish()) != SBV_OK) return rc;
+    }
+    // the packing: a host pass over the downloaded records
+    uint64_t at = 0;
+    sig_offsets[0] = 0;
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(sigs + at, &rec[i * SBV_ECDSA_DER_MAX], len[i]);
+        at += len[i];
+        sig_offsets[i + 1] = at;
+    }
+    return SBV_OK;
+}
+}  // namespace
+
+extern "C" size_t sbv_ecdsa_sign_msgs_workspace(size_t n) { return n * 96; }       // digests n x 32, r | s n x 64
+
+extern "C" int sbv_sha256_msgs_stream(const void* d_msgs, const void* d_msg_offsets, size_t n, void* d_digests, void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!d_msg_offsets || !d_digests) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
+    if (misaligned(3, d_digests) || misaligned(7, d_msg_offsets)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, sbv::launch_sha256_msgs(static_cast<const uint8_t*>(d_msgs), static_cast<const uint64_t*>(d_msg_offsets), n, kAnyBytes,
+                                                 static_cast<uint8_t*>(d_digests), nullptr, static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+extern "C" int sbv_sha256_msgs(const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, uint8_t* digests) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (n == 0) return SBV_OK;
+    if (!msg_offsets || !digests) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }
+    size_t mbytes = 0;
+    const int rc = check_offsets(msg_offsets, n, msgs, mbytes);
+    if (rc != SBV_OK) return rc;
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    sbv::CallBuffers cb(c.stream, &g_err);
+    uint8_t* d_msgs = cb.alloc(mbytes + 16);            // a buffer even when every message is empty (msgs may then be null)
+    cb.copy_in(d_msgs, msgs, mbytes);
+    const uint64_t* d_moff = cb.upload(msg_offsets, (n + 1) * sizeof(uint64_t));
+    uint8_t* d_dig = cb.alloc(n * 32);
+    if (cb.good()) cb.launch(sbv::launch_sha256_msgs(d_msgs, d_moff, n, mbytes, d_dig, nullptr, c.stream));
+    cb.download(digests, d_dig, n * 32);
+    return cb.finish();
+}
+
+extern "C" int sbv_p256_sign_msgs_stream(const void* d_keys, uint32_t n_keys, const void* d_key_index, const void* d_msgs,
+                                         const void* d_msg_offsets, size_t n, uint32_t flags, void* d_records, void* d_len, void* d_ok,
+                                         void* d_work, void* hip_stream) {
+    SBV_ENTER(c);
+    return sign_msgs_stream(c, SBV_ECDSA_CURVE_P256, d_keys, n_keys, d_key_index, d_msgs, d_msg_offsets, n, flags, d_records, d_len, nullptr, d_ok,
+                            d_work, hip_stream);
+}
+
+extern "C" int sbv_secp256k1_sign_msgs_stream(const void* d_keys, uint32_t n_keys, const void* d_key_index, const void* d_msgs,
+                                              const void* d_msg_offsets, size_t n, uint32_t flags, void* d_records, void* d_len, void* d_recid,
+                                              void* d_ok, void* d_work, void* hip_stream) {
+    SBV_ENTER(c);
+    return sign_msgs_stream(c, SBV_ECDSA_CURVE_K256, d_keys, n_keys, d_key_index, d_msgs, d_msg_offsets, n, flags, d_records, d_len, d_recid, d_ok,
+                            d_work, hip_stream);
+}
+
+extern "C" int sbv_p256_sign_msgs(const uint8_t* keys, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs,
+                                  const uint64_t* msg_offsets, size_t n, uint32_t flags, uint8_t* sigs, uint64_t* sig_offsets, uint8_t* ok) {
+    SBV_ENTER(c);
+    return sign_msgs_host(c, SBV_ECDSA_CURVE_P256, keys, n_keys, key_index, msgs, msg_offsets, n, flags, sigs, sig_offsets, nullptr, ok);
+}
+
+extern "C" int sbv_secp256k1_sign_msgs(const uint8_t* keys, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs,
+                                       const uint64_t* msg_offsets, size_t n, uint32_t flags, uint8_t* sigs, uint64_t* sig_offsets,
+                                       uint8_t* recid, uint8_t* ok) {
+    SBV_ENTER(c);
+    return sign_msgs_host(c, SBV_ECDSA_CURVE_K256, keys, n_keys, key_index, msgs, msg_offsets, n, flags, sigs, sig_offsets, recid, ok);
+}
+
+// Test only (include/sbv.h): k_ecdsa_sig_finish on given r | s, every lane ok.
+extern "C" int sbv_debug_ecdsa_der_op(int curve, uint32_t flags, const uint8_t* rs, uint8_t* records, uint8_t* len, size_t n) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if ((curve != SBV_ECDSA_CURVE_P256 && curve != SBV_ECDSA_CURVE_K256) || (flags & ~SBV_ECDSA_SIGN_LOW_S)) { g_err = "unknown curve or flag"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!rs || !records || !len || n > kMaxChunk) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_rs = cb.upload(rs, n * 64);
+    uint8_t* d_rec = cb.alloc(n * SBV_ECDSA_DER_MAX);
+    uint8_t* d_len = cb.alloc(n);
+    if (cb.good()) cb.launch(sbv::launch_ecdsa_sig_finish(curve, d_rs, nullptr, false, n, (flags & SBV_ECDSA_SIGN_LOW_S) != 0, d_rec, d_len,
+                                                          nullptr, nullptr, c.stream));
+    cb.download(records, d_rec, n * SBV_ECDSA_DER_MAX);
+    cb.download(len, d_len, n);
     return cb.finish();
 }
 

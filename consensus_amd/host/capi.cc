@@ -288,6 +288,28 @@ size_t sbvh_sign_batch(void* s, const void* msgs, const uint64_t* offsets, size_
         if (!sigs[i].empty() && put(sigs[i], (char*)out + i * stride, stride) == sigs[i].size() && sigs[i].size() <= stride) ++done;
     return done;
 }
+// the same with Signer::SignBatch's low_s argument (the ECDSA schemes: s > (n-1)/2 is replaced by n - s)
+size_t sbvh_sign_batch_low_s(void* s, const void* msgs, const uint64_t* offsets, size_t n, int low_s, void* out, size_t stride) {
+    std::vector<bytes> in(n);
+    for (size_t i = 0; i < n; ++i) in[i] = B((const char*)msgs + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    const std::vector<bytes> sigs = ((Signer*)s)->SignBatch(in, low_s != 0);
+    size_t done = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (!sigs[i].empty() && put(sigs[i], (char*)out + i * stride, stride) == sigs[i].size() && sigs[i].size() <= stride) ++done;
+    return done;
+}
+// der_encode_sig (p256_host.cc) on its own, for tests: the encoding of r | s, at most 72 bytes; returns its length
+size_t sbvh_der_encode_sig(const uint8_t rs[64], void* out, size_t cap) { return put(der_encode_sig(rs), out, cap); }
+// ... and item by item over n signatures, as the host route behind a sign_batch call does (tools/bench_ecdsa_sign_msgs.py): packed
+// into out (72 n bytes at most) with n + 1 offsets
+void sbvh_der_encode_batch(const uint8_t* rs, size_t n, uint8_t* out, uint64_t* offsets) {
+    offsets[0] = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const bytes der = der_encode_sig(rs + 64 * i);
+        memcpy(out + offsets[i], der.data(), der.size());
+        offsets[i + 1] = offsets[i] + der.size();
+    }
+}
 void sbvh_sign_proposal(void* s, const void* payload, size_t pl, const void* header, size_t hl, const void* meta, size_t ml,
                         int64_t vseq, const void* aux, size_t al, void* msg_out, size_t msg_cap, size_t* msg_len,
                         void* val_out, size_t val_cap, size_t* val_len) {

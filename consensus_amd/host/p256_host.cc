@@ -7,6 +7,7 @@
 
 #include "../../include/sbv.h"
 #include "../csrc/p256_core.h"
+#include "../csrc/ecdsa_sign_msgs.h"
 
 namespace sbvhost {
 
@@ -154,6 +155,14 @@ bytes der_encode_sig(const uint8_t rs[64]) {
     out.push_back(0x30);
     out.push_back((char)body.size());       // <= 70 < 128: short form
     return out + body;
+}
+
+bool rs_low_s(bool k256, uint8_t rs[64]) {
+    u256 s;
+    from_be32(s, rs + 32);
+    const bool negated = ecdsa_low_s(k256 ? SBV_ECDSA_CURVE_K256 : SBV_ECDSA_CURVE_P256, s);
+    to_be32(rs + 32, s);
+    return negated;
 }
 
 }  // namespace sbvhost

@@ -23,5 +23,8 @@ bool sign_rfc6979(const uint8_t d[32], const uint8_t digest[32], uint8_t rs[64])
 bool sign_with_nonce(const uint8_t d[32], const uint8_t k[32], const uint8_t digest[32], uint8_t rs[64]);
 // minimal DER ECDSA-Sig-Value, as Go's ecdsa.SignASN1 emits
 bytes der_encode_sig(const uint8_t rs[64]);
+// low-S on r|s in place: s > (n-1)/2 becomes n - s, for the order of P-256 or (k256) secp256k1; s in [1, n-1].  The lane the device
+// runs (consensus_amd/csrc/ecdsa_sign_msgs.h: ecdsa_low_s).  Returns whether s was negated.
+bool rs_low_s(bool k256, uint8_t rs[64]);
 
 }  // namespace sbvhost

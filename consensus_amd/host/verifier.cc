@@ -1562,11 +1562,6 @@ bytes Signer::Sign(const bytes& msg) {
     if (!(scheme_ == Scheme::SECP256K1 ? k256_sign_rfc6979(d_, h, rs) : sign_rfc6979(d_, h, rs))) return bytes();
     return der_encode_sig(rs);
 }
-// The batch form.  Under Scheme::ED25519, when the process has a device initialised (a GPU backend exists: make_sbv_backend, or the
-// caller's own sbv_init), the whole batch is one sbv_ed25519_sign_msgs call under this signer's expanded record, which the device
-// derives from the seed on the first batch; byte-identical to Sign (the scheme is deterministic).  Under Scheme::SECP256K1 likewise one
-// sbv_secp256k1_sign_batch call.  Otherwise a loop over Sign.
-// A device error gives empty signatures, as a failed Sign does.  NOT constant-time on the device: see include/sbv.h.
 Status Verifier::RecoverSigners(const uint8_t* sigs65, const uint8_t* digests, size_t n, uint8_t* pubs, uint8_t* ok) {
     if (!k256()) return Status::Invalid("RecoverSigners needs Scheme::SECP256K1");
     if (n == 0) return Status::Ok();
@@ -1637,7 +1632,22 @@ Status Verifier::VerifySchnorrKeyed(const uint8_t* msgs, const uint8_t* sigs, co
     return Status::Ok();
 }
 
-std::vector<bytes> Signer::SignBatch(const std::vector<bytes>& msgs) {
+// Sign with s > (n - 1) / 2 replaced by n - s (the ECDSA schemes; Ed25519 has no such form and signs as Sign does)
+bytes Signer::SignLowS(const bytes& msg) {
+    if (scheme_ == Scheme::ED25519) return Sign(msg);
+    uint8_t h[32], rs[64];
+    sha256(msg.data(), msg.size(), h);
+    if (!(scheme_ == Scheme::SECP256K1 ? k256_sign_rfc6979(d_, h, rs) : sign_rfc6979(d_, h, rs))) return bytes();
+    (void)rs_low_s(scheme_ == Scheme::SECP256K1, rs);
+    return der_encode_sig(rs);
+}
+// The batch form.  Under Scheme::ED25519, when the process has a device initialised (a GPU backend exists: make_sbv_backend, or the
+// caller's own sbv_init), the whole batch is one sbv_ed25519_sign_msgs call under this signer's expanded record, which the device
+// derives from the seed on the first batch; byte-identical to Sign (the scheme is deterministic).  Under Scheme::P256 and
+// Scheme::SECP256K1 likewise one sbv_p256_sign_msgs / sbv_secp256k1_sign_msgs call.  Otherwise a loop over Sign.  low_s (the ECDSA
+// schemes only): s > (n - 1) / 2 is replaced by n - s, on the device and in the host loop alike.
+// A device error gives empty signatures, as a failed Sign does.  NOT constant-time on the device: see include/sbv.h.
+std::vector<bytes> Signer::SignBatch(const std::vector<bytes>& msgs, bool low_s) {
     std::vector<bytes> out(msgs.size());
     if (msgs.empty()) return out;
     if (scheme_ == Scheme::ED25519 && msgs.size() <= ((size_t)1 << 21) && sbv_initialised_devices(nullptr, 0) > 0) {
@@ -1654,17 +1664,23 @@ std::vector<bytes> Signer::SignBatch(const std::vector<bytes>& msgs) {
         }
         if (rc != SBV_ENOTINIT) return out;          // SBV_ENOTINIT: the initialised device is not the default context's: the host signs
     }
-    // Under Scheme::SECP256K1 the same offload: SHA-256 on the host, one sbv_secp256k1_sign_batch call with flags = 0 (no low-S rule:
-    // what Sign produces), then DER.  Scheme::P256 stays on the host loop.
-    if (scheme_ == Scheme::SECP256K1 && sbv_initialised_devices(nullptr, 0) > 0) {
-        std::vector<uint8_t> digests(32 * msgs.size()), sigs(64 * msgs.size()), ok(msgs.size());
-        for (size_t i = 0; i < msgs.size(); ++i) sha256(msgs[i].data(), msgs[i].size(), &digests[32 * i]);
-        const int rc = sbv_secp256k1_sign_batch(d_, 1, nullptr, digests.data(), msgs.size(), 0, sigs.data(), nullptr, ok.data());
+    // Under Scheme::P256 and Scheme::SECP256K1 likewise one device call each: sbv_p256_sign_msgs / sbv_secp256k1_sign_msgs hash the
+    // messages (SHA-256), sign and DER-encode on the device and return the signatures packed; no host hashing, no host DER.  With
+    // low_s = false that is flags = 0: what Sign produces, byte for byte.
+    if (scheme_ != Scheme::ED25519 && msgs.size() <= ((size_t)1 << 21) && sbv_initialised_devices(nullptr, 0) > 0) {
+        std::vector<uint64_t> off(msgs.size() + 1, 0), soff(msgs.size() + 1, 0);
+        for (size_t i = 0; i < msgs.size(); ++i) off[i + 1] = off[i] + msgs[i].size();
+        std::vector<uint8_t> payload((size_t)off.back() + 1), sigs(SBV_ECDSA_DER_MAX * msgs.size()), ok(msgs.size());
+        for (size_t i = 0; i < msgs.size(); ++i) memcpy(payload.data() + off[i], msgs[i].data(), msgs[i].size());
+        const uint32_t flags = low_s ? SBV_ECDSA_SIGN_LOW_S : 0u;
+        const int rc = scheme_ == Scheme::SECP256K1
+                           ? sbv_secp256k1_sign_msgs(d_, 1, nullptr, payload.data(), off.data(), msgs.size(), flags, sigs.data(), soff.data(), nullptr, ok.data())
+                           : sbv_p256_sign_msgs(d_, 1, nullptr, payload.data(), off.data(), msgs.size(), flags, sigs.data(), soff.data(), ok.data());
         for (size_t i = 0; rc == SBV_OK && i < msgs.size(); ++i)
-            if (ok[i]) out[i] = der_encode_sig(&sigs[64 * i]);
+            if (ok[i]) out[i] = bytes((const char*)&sigs[soff[i]], (size_t)(soff[i + 1] - soff[i]));
         if (rc != SBV_ENOTINIT) return out;
     }
-    for (size_t i = 0; i < msgs.size(); ++i) out[i] = Sign(msgs[i]);
+    for (size_t i = 0; i < msgs.size(); ++i) out[i] = low_s ? SignLowS(msgs[i]) : Sign(msgs[i]);
     return out;
 }
 Signature Signer::SignProposal(const Proposal& proposal, const bytes& auxiliary_input) {    // view.go:481

@@ -362,8 +362,10 @@ class Signer {
     const uint8_t* public_key() const { return q_; }                        // 64 bytes Qx|Qy, or 32 bytes A_enc (+ 32 zero bytes)
     bytes Sign(const bytes& msg);                                           // DER over SHA-256(msg), or the 64-byte Ed25519 R|S
     // one signature per message, equal to Sign of each; with a device initialised Ed25519 is one sbv_ed25519_sign_msgs call and
-    // secp256k1 one sbv_secp256k1_sign_batch call (verifier.cc)
-    std::vector<bytes> SignBatch(const std::vector<bytes>& msgs);
+    // P-256 / secp256k1 one sbv_p256_sign_msgs / sbv_secp256k1_sign_msgs call: hashing and DER on the device (verifier.cc).  low_s:
+    // the ECDSA schemes return s <= (n-1)/2
+    std::vector<bytes> SignBatch(const std::vector<bytes>& msgs, bool low_s = false);
+    bytes SignLowS(const bytes& msg);                                       // Sign with s > (n-1)/2 replaced by n - s (ECDSA schemes)
     Signature SignProposal(const Proposal& proposal, const bytes& auxiliary_input);
     ~Signer() { volatile uint8_t* p = ed_rec_; for (int i = 0; i < 96; ++i) p[i] = 0; }
 

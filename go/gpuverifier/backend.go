@@ -98,6 +98,16 @@ type K256BatchSigner interface {
 	SignBatchSecp256k1(keys [][32]byte, keyIndex []uint32, digests [][32]byte, lowS bool) (sigs [][64]byte, recid []byte, ok []bool, err error)
 }
 
+// ECDSAMsgSigner is the raw-message ECDSA signer of a backend (sbv_p256_sign_msgs / sbv_secp256k1_sign_msgs: SHA-256, the RFC 6979
+// signature and the DER encoding on the device, one call): sigs[i] = the DER signature of msgs[i] under keys[keyIndex[i]], what
+// RawMessageVerifier.VerifyMsgs takes as Item.Sig; a nil keyIndex means key i % len(keys); lowS replaces s > (n-1)/2 by n - s on
+// either curve (Fabric's BCCSP refuses the high form of P-256).  recid is nil for SchemeP256.  ok[i] = false, and an empty signature, when the key is not in [1, n-1] or the
+// index is out of range.  An optional interface beside Backend like K256BatchSigner, for the same reason; a backend without a device
+// signer returns ErrNoBatchSigner.  NOT constant-time on the device (include/sbv.h).
+type ECDSAMsgSigner interface {
+	SignMsgs(scheme Scheme, keys [][32]byte, keyIndex []uint32, msgs [][]byte, lowS bool) (sigs [][]byte, recid []byte, ok []bool, err error)
+}
+
 // K256BatchRecoverer is the secp256k1 public-key recovery of a backend (sbv_secp256k1_recover): key i = the signer's Qx|Qy of
 // signature sigs[i] (r|s, 64 bytes big-endian) with recovery id recid[i] (0..3, as K256BatchSigner emits it) over digests[i], by the
 // rules of libsecp256k1's ecdsa_recover (include/sbv.h); lowS also refuses s > (n-1)/2.  ok[i] = false, and a zero key, for a refused

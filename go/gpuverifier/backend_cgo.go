@@ -697,6 +697,63 @@ func (b *gpuBackend) SignBatchSecp256k1(keys [][32]byte, keyIndex []uint32, dige
 	return sigs, recid, ok, nil
 }
 
+// SignMsgs (ECDSAMsgSigner): sbv_p256_sign_msgs / sbv_secp256k1_sign_msgs: SHA-256, RFC 6979 signing and DER on the device, at most
+// 2^21 messages per call (not constant-time — see include/sbv.h).
+func (b *gpuBackend) SignMsgs(scheme Scheme, keys [][32]byte, keyIndex []uint32, msgs [][]byte, lowS bool) (sigs [][]byte, recid []byte, ok []bool, err error) {
+	n := len(msgs)
+	if n == 0 || n > frontEndMax || len(keys) == 0 || (keyIndex != nil && len(keyIndex) != n) {
+		return nil, nil, nil, errors.New("gpuverifier: SignMsgs needs keys, no key index or one per message, and at most 2^21 messages")
+	}
+	if scheme != SchemeP256 && scheme != SchemeSecp256k1 {
+		return nil, nil, nil, errors.New("gpuverifier: SignMsgs takes SchemeP256 or SchemeSecp256k1")
+	}
+	kb := make([]byte, 32*len(keys))
+	for i := range keys {
+		copy(kb[32*i:], keys[i][:])
+	}
+	var mode uint32
+	if lowS {
+		mode = 1 // SBV_ECDSA_SIGN_LOW_S
+	}
+	packed, moff := packMsgs(func(i int) []byte { return msgs[i] }, n)
+	out := make([]byte, 72*n) // SBV_ECDSA_DER_MAX each
+	soff := make([]uint64, n+1)
+	flags := make([]byte, n)
+	if scheme == SchemeSecp256k1 {
+		recid = make([]byte, n)
+	}
+	b.on(func() {
+		var rc C.int
+		var index *uint32 // nil: key i % len(keys), the library's rule for a NULL index
+		if keyIndex != nil {
+			index = &keyIndex[0]
+		}
+		if scheme == SchemeP256 {
+			rc = C.sbv_p256_sign_msgs(u8(kb), C.uint32_t(len(keys)), (*C.uint32_t)(unsafe.Pointer(index)), u8(packed),
+				(*C.uint64_t)(unsafe.Pointer(&moff[0])), C.size_t(n), C.uint32_t(mode), u8(out), (*C.uint64_t)(unsafe.Pointer(&soff[0])), u8(flags))
+		} else {
+			rc = C.sbv_secp256k1_sign_msgs(u8(kb), C.uint32_t(len(keys)), (*C.uint32_t)(unsafe.Pointer(index)), u8(packed),
+				(*C.uint64_t)(unsafe.Pointer(&moff[0])), C.size_t(n), C.uint32_t(mode), u8(out), (*C.uint64_t)(unsafe.Pointer(&soff[0])), u8(recid), u8(flags))
+		}
+		if rc != 0 {
+			err = lastError()
+		}
+	})
+	for i := range kb {
+		kb[i] = 0
+	}
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	sigs = make([][]byte, n)
+	ok = make([]bool, n)
+	for i := 0; i < n; i++ {
+		sigs[i] = out[soff[i]:soff[i+1]]
+		ok[i] = flags[i] != 0
+	}
+	return sigs, recid, ok, nil
+}
+
 // RecoverBatchSecp256k1: sbv_secp256k1_recover (one device call; nothing secret is involved).
 func (b *gpuBackend) RecoverBatchSecp256k1(sigs [][64]byte, recid []byte, digests [][32]byte, lowS bool) (pubs [][64]byte, ok []bool, err error) {
 	n := len(sigs)

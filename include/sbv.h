@@ -625,6 +625,57 @@ int
 sbv_secp256k1_verify_msgs(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
                           const uint8_t* keys, size_t n, uint8_t* accept_bitmap);
 
+/* Raw-message ECDSA signing: SHA-256, RFC 6979 signing and DER in one call, the signing side of the two entries above and the ECDSA
+ * form of sbv_ed25519_sign_msgs.  Signature i = DER SEQUENCE { INTEGER r, INTEGER s } of ECDSA(keys[key_index[i]],
+ * SHA-256(msgs[msg_offsets[i] .. msg_offsets[i+1]))) with the deterministic nonce of RFC 6979; with flags = 0 byte-identical to
+ * Signer::Sign of consensus_amd/host.  key_index == NULL means key i % n_keys; keys: n_keys x 32 bytes (private scalar, big-endian).
+ * Three kernels run per call: k_sha256_msgs (one lane per message), the signing kernel of sbv_p256_sign_batch /
+ * sbv_secp256k1_sign_batch as it is, and k_ecdsa_sig_finish (low-S for P-256, the minimal DER encoding as a 72-byte record);
+ * consensus_amd/csrc/ecdsa_sign_msgs.h, ecdsa_sign_msgs_kernels.hip.
+ *   flags   SBV_ECDSA_SIGN_LOW_S: s > (n-1)/2 is replaced by n - s on either curve (Fabric's BCCSP refuses the high form of P-256;
+ *           secp256k1: the flag of sbv_secp256k1_sign_batch, passed through, recid bit 0 flipped with it).  Any other bit is SBV_EINVAL.
+ * Host forms (sbv_p256_sign_msgs, sbv_secp256k1_sign_msgs): the signatures come back packed back to back in sigs (the caller provides
+ * SBV_ECDSA_DER_MAX * n bytes) with sig_offsets (n + 1 entries, the first 0): exactly the pair sbv_p256_verify_msgs /
+ * sbv_secp256k1_verify_msgs take.  The packing is a host pass over the downloaded records.  ok: n bytes; recid: n bytes or NULL.
+ * A refused item has ok[i] = 0, an empty signature (equal offsets) and recid 0: a key outside [1, n-1], an index >= n_keys, and in a
+ * `_stream` call a decreasing offset pair.
+ * `_stream` forms: device pointers, launched on `hip_stream`, no synchronisation, under the stream contract of the `_dev` entries
+ *  for every buffer they name; they own no mutable device state and may be the first call after sbv_init.
+ * They write d_records (n x 72 bytes, record i zero behind its length, all zero when refused), d_len (n bytes: 0 or 8..72), d_ok
+ * and, for secp256k1, d_recid (or NULL).  d_work: sbv_ecdsa_sign_msgs_workspace(n) bytes (the digests and r | s between the
+ * kernels), the caller's, 4-byte aligned, not shared between calls in flight.
+ * sbv_sha256_msgs: the first kernel on its own: digests = n x 32 bytes, SHA-256 of message i; in the `_stream` form a decreasing
+ * offset pair gives the digest of the empty message.
+ * SBV_ENOTINIT before sbv_init, whatever the arguments.  n == 0 is SBV_OK and writes nothing.  SBV_EINVAL, with nothing written: a null
+ * required pointer (msgs may be null when every message is empty), n_keys == 0, an unknown flag bit, n > 2^21, in a host form an
+ * offset table that does not start at 0 or that decreases, in a `_stream` form a misaligned device pointer (4 bytes for keys, key
+ * index, records, digests and workspace, 8 for the offsets).  A refused call leaves the library as it was.
+ * The host forms use device buffers of the call's own size, wait for the result and zero the device copy of the keys before they
+ * free it.  NOT constant-time, like the signers underneath (secret-indexed table lookups in HBM; low-S and the encoder branch on s and
+ * on the leading bytes of r and s): for test traffic and trusted single-tenant hosts.
+ *   sbv_debug_ecdsa_der_op   test only: k_ecdsa_sig_finish on given integers.  curve 0 = P-256, 1 = secp256k1; rs: n x 64 bytes;
+ *                            flags SBV_ECDSA_SIGN_LOW_S applies low-S (s must then be in [1, n-1]); records: n x 72, len: n bytes.
+ *                            An unknown curve or flag, a null pointer or n > 2^21 is SBV_EINVAL. */
+#define SBV_ECDSA_SIGN_LOW_S 1u        /* same bit as SBV_K256_SIGN_LOW_S */
+#define SBV_ECDSA_DER_MAX 72
+int sbv_sha256_msgs(const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, uint8_t* digests);
+int sbv_sha256_msgs_stream(const void* d_msgs, const void* d_msg_offsets, size_t n, void* d_digests, void* hip_stream);
+int sbv_p256_sign_msgs(const uint8_t* keys, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs,
+                       const uint64_t* msg_offsets, size_t n, uint32_t flags, uint8_t* sigs, uint64_t* sig_offsets, uint8_t* ok);
+int
+sbv_secp256k1_sign_msgs(const uint8_t* keys, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs,
+                        const uint64_t* msg_offsets, size_t n, uint32_t flags, uint8_t* sigs, uint64_t* sig_offsets, uint8_t* recid,
+                        uint8_t* ok);
+size_t sbv_ecdsa_sign_msgs_workspace(size_t n);
+int sbv_p256_sign_msgs_stream(const void* d_keys, uint32_t n_keys, const void* d_key_index, const void* d_msgs,
+                              const void* d_msg_offsets, size_t n, uint32_t flags, void* d_records, void* d_len, void* d_ok,
+                              void* d_work, void* hip_stream);
+int
+sbv_secp256k1_sign_msgs_stream(const void* d_keys, uint32_t n_keys, const void* d_key_index, const void* d_msgs,
+                               const void* d_msg_offsets, size_t n, uint32_t flags, void* d_records, void* d_len, void* d_recid,
+                               void* d_ok, void* d_work, void* hip_stream);
+int sbv_debug_ecdsa_der_op(int curve, uint32_t flags, const uint8_t* rs, uint8_t* records, uint8_t* len, size_t n);
+
 /* Strict DER parse of an ECDSA-Sig-Value with Go x/crypto/cryptobyte rules
  * (crypto/ecdsa.parseSignature): out = r | s, 32 bytes each, big-endian, zero padded.
  * Returns SBV_OK or SBV_EPARSE (then out is all zero, which every verify rejects). */
