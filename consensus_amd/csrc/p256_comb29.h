@@ -109,8 +109,17 @@ SBV_HD bool wave_all(bool x) {
 }
 // (j0, j1): only the windows [j0, j1) — the key-comb chunks of the grouped step; top_on_demand: the top window holds nothing but the carry of
 // the signed recoding, and is walked only when a lane of the wavefront carries (wave-uniform loop bound)
+// The two ends of a walk (pt29_madd_core):
+//   from infinity (!add_to_R) a lane's first real addition is a copy and leaves an AFFINE accumulator; its next real addition takes the
+//   affine + affine form when every lane of the wavefront that adds in that iteration is in that state (all of them, but for a zero digit:
+//   2^-16 per lane in the comb of G) — a mixed wavefront takes the general form, which is as exact on ZZ = ZZZ = 1;
+//   x_only: the caller reads X and ZZ of the result only (pt29_rx_matches), so the additions of the LAST iteration — the bound is
+//   wave-uniform — compute neither Y nor ZZZ.  A lane whose last real addition came earlier did a full one there.
+#ifndef SBV_COMB_TRIM_ENDS
+#define SBV_COMB_TRIM_ENDS 1                          // 0: every addition of a walk is the general pt29_madd (A/B builds, tools/ab_lib.sh)
+#endif
 SBV_HD void gphase29_point(xyzz& R, const u256& u1, const gcomb& gc, bool add_to_R = false, bool flip = false, int j0 = 0, int j1 = -1,
-                           bool top_on_demand = false) {
+                           bool top_on_demand = false, bool x_only = false) {
     u288 k1;
     gcomb_recode(k1, u1, gc.bits, gc.windows);
     if (!add_to_R) pt29_set_inf(R);
@@ -124,8 +133,10 @@ SBV_HD void gphase29_point(xyzz& R, const u256& u1, const gcomb& gc, bool add_to
     gcomb_digit(k1, gc.bits, j0, idx, neg, skip);
     raw_apt cur;
     raw_apt_load(cur, gc.tab + ((size_t)j0 << (gc.bits - 1)) + idx);
-    SBV_NOUNROLL
-    for (int j = j0; j < j1; ++j) {
+    bool affine = false;                              // only ever set in a walk from infinity
+    // one iteration: fetch the next window's entry, add the current one.  The x-only iteration is a copy of the body behind the loop,
+    // not a branch inside it: a flag tested in the loop cost the last Q launch spilled registers at 3 waves per SIMD.
+    auto step = [&](int j, bool xo) {
         const int jn = j + 1 < j1 ? j + 1 : j1 - 1;
         u32 idxn; bool negn, skipn;
         gcomb_digit(k1, gc.bits, jn, idxn, negn, skipn);
@@ -134,10 +145,17 @@ SBV_HD void gphase29_point(xyzz& R, const u256& u1, const gcomb& gc, bool add_to
         if (!skip) {
             apt29 q;
             raw_apt_unpack(q, cur);
-            pt29_madd(R, q, neg != flip);
+            const bool was_inf = R.inf;
+            pt29_madd_core(R, q, neg != flip, SBV_COMB_TRIM_ENDS && !add_to_R && wave_all(affine), xo);
+            affine = !add_to_R && was_inf;
         }
         cur = nxt; neg = negn; skip = skipn;
-    }
+    };
+    const bool peel = SBV_COMB_TRIM_ENDS && x_only;
+    const int jl = peel ? j1 - 1 : j1;
+    SBV_NOUNROLL
+    for (int j = j0; j < jl; ++j) step(j, false);
+    if (peel) step(j1 - 1, true);
 }
 SBV_HD void gphase29_lane(const Scratch& s, size_t i, const gcomb& gc, u32* gacc) {
     u256 u1;
@@ -188,10 +206,11 @@ SBV_HD void wide_qphase29_point(xyzz& R, const u256& u2in, const widekeys& wk, u
     (void)sub256(nmu, sc_n(), u2in);
     select256(u2, flip, nmu, u2in);
     gcomb kc = {wk.tab + (size_t)widx * wk.stride, wk.bits, wk.windows};
-    gphase29_point(R, u2, kc, true, flip);
+    gphase29_point(R, u2, kc, true, flip, 0, -1, false, true);          // every caller compares R.x with r next
 }
 
-SBV_HD void qphase29_point(xyzz& R, const u256& u2in, const apt* qtab, int j0, int j1) {
+// x_only: the caller reads X and ZZ of R only (the last chunk, in front of pt29_rx_matches)
+SBV_HD void qphase29_point(xyzz& R, const u256& u2in, const apt* qtab, int j0, int j1, bool x_only = false) {
     const bool flip = (u2in.v[7] >> 31) != 0;
     u256 u2, nmu;
     (void)sub256(nmu, sc_n(), u2in);                  // u2in < n always (stage A reduces it); garbage for an out-of-range lane, whose verdict is already false
@@ -199,7 +218,7 @@ SBV_HD void qphase29_point(xyzz& R, const u256& u2in, const apt* qtab, int j0, i
     // a key's 8-bit comb IS a comb in the layout of the comb of G (gcomb) with bits = 8 and 33 windows: the same walker (round 6 — the
     // dedicated loop of rounds 2-5 indexed the recoded scalar's register array dynamically and needed 247 VGPRs; this one fits 168)
     const gcomb kc = {qtab, 8, SBV_GTAB_WINDOWS};
-    gphase29_point(R, u2, kc, true, flip, j0, j1, true);
+    gphase29_point(R, u2, kc, true, flip, j0, j1, true, x_only);
 }
 // ---- the NARROW view of a key's comb (round 5) ------------------------------------------------------------------------------------
 // The rows step of the table builder (p256_keytab29.h) leaves, in every 128-entry window row j, the babies b * B_j (b = 1..8, entries
@@ -275,7 +294,7 @@ SBV_HD bool qphase29_lane(const Scratch& s, size_t i, u32 slot, u32 nkeys, const
     xyzz R;
     gacc29_load(R, gacc, s.cap, i);
     if (NARROW) qphase29_point_narrow(R, u2, qtab, j0, j1);
-    else qphase29_point(R, u2, qtab, j0, j1);
+    else qphase29_point(R, u2, qtab, j0, j1, last);
     if (!last) { gacc29_store(gacc, s.cap, i, R); return false; }
     u256 r;
     soa_load(r, s.r, s.cap, i);
@@ -294,7 +313,7 @@ SBV_HD bool qphase29_lane_sorted(const Scratch& s, size_t t, size_t L, u32 slot,
     xyzz R;
     gacc29_load(R, gacc, s.cap, L);
     if (NARROW) qphase29_point_narrow(R, u2, qtab, j0, j1);
-    else qphase29_point(R, u2, qtab, j0, j1);
+    else qphase29_point(R, u2, qtab, j0, j1, last);
     if (!last) {
         // The accumulator goes back where it came from.  Left alone, the compiler keeps the 36 load addresses (72 VGPRs: the planes are
         // `cap` words apart, no immediate offset reaches) alive across the whole comb loop for these stores — the difference between 168
@@ -328,7 +347,7 @@ SBV_HD bool verify29_lane_keyed(const Scratch& s, size_t i, u32 slot, u32 nkeys,
     gphase29_point(R, u1, gc);
     const u32 widx = widekeys_index(wk, slot);
     if (wave_all(widx != SBV_WIDE_NONE)) wide_qphase29_point(R, u2, wk, widx);
-    else qphase29_point(R, u2, qtab, 0, SBV_GTAB_WINDOWS);
+    else qphase29_point(R, u2, qtab, 0, SBV_GTAB_WINDOWS, true);
     return ok && pt29_rx_matches(R, r);
 }
 
@@ -359,7 +378,7 @@ SBV_HD void verify29_generic_q(xyzz& S, bool& ok, const u256& u2, const u256& qx
     // table k * Q, k = 1..8: XYZZ chain, parked raw behind the table in the lane's strip, normalised with one inversion
     {
         u32 w[16];
-        f29_store_canon(w, Q.x); f29_store_canon(w + 8, Q.y);
+        f29_store_canon32(w, Q.x); f29_store_canon32(w + 8, Q.y);       // f29_from_plain outputs: f29_mul's
         SBV_UNROLL
         for (int l = 0; l < 16; ++l) qtab[l] = w[l];
         u32* raw = qtab + 8 * 16;               // 7 records of 45 words: X, Y, ZZ, ZZZ, prefix product
@@ -395,7 +414,7 @@ SBV_HD void verify29_generic_q(xyzz& S, bool& ok, const u256& u2, const u256& qx
             apt29 a;
             f29_mul(a.x, X, w2);
             f29_mul(a.y, Y, i3);
-            f29_store_canon(w, a.x); f29_store_canon(w + 8, a.y);
+            f29_store_canon32(w, a.x); f29_store_canon32(w + 8, a.y);
             SBV_UNROLL
             for (int l = 0; l < 16; ++l) qtab[(k + 1) * 16 + l] = w[l];
         }
@@ -426,7 +445,7 @@ SBV_HD void verify29_generic_q(xyzz& S, bool& ok, const u256& u2, const u256& qx
     f29_mulx(S.ZZZ, R.Z, S.ZZ);
 }
 SBV_HD bool verify29_generic_finish(xyzz& S, const u256& r, const u256& u1, bool ok, const gcomb& gc) {
-    gphase29_point(S, u1, gc, true);
+    gphase29_point(S, u1, gc, true, false, 0, -1, false, true);
     return ok && pt29_rx_matches(S, r);
 }
 SBV_HD bool verify29_generic_core(const u256& r, const u256& u1, const u256& u2, const u256& qx, const u256& qy, bool ok,

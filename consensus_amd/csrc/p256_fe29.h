@@ -335,6 +335,47 @@ SBV_HD void f29_canon(fe29& r, const fe29& a) {
     SBV_UNROLL
     for (int i = 0; i < 9; ++i) r.v[i] = (i32)v[i];
 }
+// The same result on 32-bit limbs only, straight-line: what a table store pays per coordinate (p256_keytab29.h: apt29_store_canon).
+// f29_canon serves any |value| < 16 p on limbs up to 2^31, which forces 64-bit working limbs (half-rate shifts and adds on
+// gfx950) and two fix-up passes each way.  The coordinates a table stores are never that general: they are f29_mul / f29_sqr
+// outputs (limbs 0..7 exact, value within (-2p, 3p)) or f29_norm_red outputs (limbs within 2^25 + 8 of [0, 2^29)).
+// Contract: EVERY limb in [-2^30, 2^30)  (so |value| < 2^262 + 2^233, about 64 * 2^256)  ->  the representative in [0, p),
+// exact 29-bit limbs, limb for limb what f29_canon returns.
+// Why the carries stay inside an i32: chain 1 adds a carry in [-3, 2] to a limb in [-2^30, 2^30).  After it limbs 0..7 are exact
+// and |v[8]| <= 2^30 + 3, so q = floor(value / 2^256) = v[8] >> 24 lies in [-65, 64] and the five terms of q * p move at most
+// 65 * 2^21 < 2^28 into a limb below 2^29.  value - q p lies in [0, 2^256) + q (2^224 - 2^192 - 2^96 + 1), i.e. within
+// (-2^231, 2^256 + 2^231), strictly inside (-p, 2p): ONE conditional step settles it — add p when negative, else try
+// subtracting p — on limbs in (-2^29, 2^30), the carries of chain 3 in [-1, 1].
+#if defined(SBV_F29_CHECK) && !defined(__HIP_DEVICE_COMPILE__)
+inline void f29_check_canon32(const fe29& a) {
+    for (int i = 0; i < 9; ++i)
+        if (a.v[i] >= (1 << 30) || a.v[i] < -(1 << 30)) { fprintf(stderr, "f29_canon32: limb %d outside [-2^30, 2^30)\n", i); abort(); }
+}
+#define SBV_F29_CHECK_CANON32(a) f29_check_canon32(a)
+#else
+#define SBV_F29_CHECK_CANON32(a) ((void)0)
+#endif
+SBV_HD void f29_canon32(fe29& r, const fe29& a) {
+    SBV_F29_CHECK_CANON32(a);
+    const fe29 P = f29_p();
+    i32 v[9], t[9];
+    SBV_UNROLL
+    for (int i = 0; i < 9; ++i) v[i] = a.v[i];
+    SBV_UNROLL
+    for (int i = 0; i < 8; ++i) { v[i + 1] += v[i] >> 29; v[i] &= (i32)SBV_M29; }
+    const i32 q = v[8] >> 24;
+    v[8] -= f29_shl(q, 24); v[7] += f29_shl(q, 21); v[6] -= f29_shl(q, 18); v[3] -= f29_shl(q, 9); v[0] += q;
+    SBV_UNROLL
+    for (int i = 0; i < 8; ++i) { v[i + 1] += v[i] >> 29; v[i] &= (i32)SBV_M29; }
+    const i32 m = v[8] >> 31;                         // -1 when negative: t = v + p, else t = v - p   ((x ^ ~m) - ~m negates for m = 0)
+    SBV_UNROLL
+    for (int i = 0; i < 9; ++i) t[i] = v[i] + ((P.v[i] ^ ~m) - ~m);
+    SBV_UNROLL
+    for (int i = 0; i < 8; ++i) { t[i + 1] += t[i] >> 29; t[i] &= (i32)SBV_M29; }
+    const bool take = (m | ~(t[8] >> 31)) != 0;       // negative (v + p is the answer), or v - p >= 0
+    SBV_UNROLL
+    for (int i = 0; i < 9; ++i) r.v[i] = take ? t[i] : v[i];
+}
 // value == 0 (mod p) for |value| < 16 p.  A multiple k*p with |k| <= 16 has low limb -k mod 2^29 (limb 0 receives
 // no carry, so it IS the value mod 2^29): everything else is rejected by three instructions.
 SBV_HD bool f29_maybe_zero(const fe29& a) { return (((u32)a.v[0] + 16u) & SBV_M29) <= 32u; }
@@ -424,6 +465,16 @@ SBV_HD void f29_inv_ct(fe29& r, const fe29& a) {
 SBV_HD void f29_store_canon(u32 w[8], const fe29& a) {
     fe29 c;
     f29_canon(c, a);
+    f29_pack(w, c);
+}
+// the same for a coordinate inside f29_canon32's contract (every table store: p256_keytab29.h, p256_widetab29.h, p256_comb29.h)
+SBV_HD void f29_store_canon32(u32 w[8], const fe29& a) {
+    fe29 c;
+#if defined(SBV_F29_STORE_REF)
+    f29_canon(c, a);                            // test only: tests/test_emul_trim.py builds the tables both ways and compares the bytes
+#else
+    f29_canon32(c, a);
+#endif
     f29_pack(w, c);
 }
 

@@ -37,14 +37,30 @@ SBV_HD void f29_load_raw(fe29& a, const u32* src) {
     SBV_UNROLL
     for (int l = 0; l < 9; ++l) a.v[l] = (i32)src[l];
 }
-SBV_HD void apt29_store_canon(apt* dst, const apt29& a) {
-    u32 w[16];
-    f29_store_canon(w, a.x);
-    f29_store_canon(w + 8, a.y);
+// 16 canonical words of a point whose coordinates satisfy f29_canon32's contract (every limb in [-2^30, 2^30)): every point the table
+// builders store is a pair of f29_mul outputs (rows, chains, the one-lane kernel's table) or of f29_norm_red outputs
+// (apt29_add_with_inverse: the fills).
+SBV_HD void apt29_canon_words(u32 w[16], const apt29& a) {
+    f29_store_canon32(w, a.x);
+    f29_store_canon32(w + 8, a.y);
+}
+SBV_HD void apt_store_words(apt* dst, const u32 w[16]) {
     struct alignas(16) q4 { u32 x, y, z, w; };
     q4* d = reinterpret_cast<q4*>(dst);
     SBV_UNROLL
     for (int k = 0; k < 4; ++k) { q4 v = {w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]}; d[k] = v; }
+}
+SBV_HD void apt29_store_canon(apt* dst, const apt29& a) {
+    u32 w[16];
+    apt29_canon_words(w, a);
+    apt_store_words(dst, w);
+}
+// the same point into two places: the words are computed once
+SBV_HD void apt29_store_canon2(apt* dst, apt* dst2, const apt29& a) {
+    u32 w[16];
+    apt29_canon_words(w, a);
+    apt_store_words(dst, w);
+    if (dst2) apt_store_words(dst2, w);
 }
 
 // ---- chain -------------------------------------------------------------------------------------------------------------
@@ -303,8 +319,7 @@ SBV_HD void keytab29_rows_lane(const u32* base2, int which, bool top_window, u32
         f29_load_raw(bx, brec); f29_load_raw(by, brec + 9);
         f29_mul(a.x, bx, zi2);
         f29_mul(a.y, by, zi3);
-        apt29_store_canon(row + (which == 0 ? 0 : 15), a);
-        if (crow) apt29_store_canon(crow + (which == 0 ? 0 : 8), a);
+        apt29_store_canon2(row + (which == 0 ? 0 : 15), crow ? crow + (which == 0 ? 0 : 8) : nullptr, a);
     }
     SBV_NOUNROLL
     for (int k = n - 1; k >= 0; --k) {
@@ -321,8 +336,7 @@ SBV_HD void keytab29_rows_lane(const u32* base2, int which, bool top_window, u32
         f29_mul(a.x, X, w2);
         f29_mul(a.y, Y, i3);
         const int mult = which == 0 ? k + 2 : 16 * (k + 2);               // this point is mult * B
-        apt29_store_canon(row + mult - 1, a);
-        if (crow) apt29_store_canon(crow + (which == 0 ? k + 1 : 9 + k), a);
+        apt29_store_canon2(row + mult - 1, crow ? crow + (which == 0 ? k + 1 : 9 + k) : nullptr, a);
     }
 }
 

@@ -101,7 +101,15 @@ SBV_HD void pt29_mdbl_a(xyzz& R, const fe29& x, const fe29& y, const fe29& a4) {
 
 // R += (q.x, neg ? -q.y : q.y).  R.X, R.Y as left by this function (or pt29_mdbl / a load of stored
 // coordinates): value-reduced; ZZ, ZZZ tight with |value| < 5 p.
-SBV_HD void pt29_madd(xyzz& R, const apt29& q, bool neg) {
+// One body serves three forms, chosen by two flags that the callers keep WAVE-UNIFORM (a branch on them is a scalar branch, no lane
+// runs both sides) and that fold away where they are constants:
+//   one     the accumulator is an affine point, ZZ = ZZZ = 1 (what the first addition of a walk from infinity leaves): U2 = x2,
+//           S2 = +-y2, ZZ3 = PP, ZZZ3 = PPP — four products by one less, 4M + 2S.  R.ZZ and R.ZZZ are not read.
+//   x_only  the caller reads X and ZZ of the result only (pt29_rx_matches behind the last addition of a walk): Y3 and ZZZ3 are not
+//           computed and R.Y, R.ZZZ are left UNDEFINED.  The exceptional branches are unchanged (a doubling leaves a full point).
+// Bounds with `one`: x2 is a canonical table coordinate, so P = x2 - X1 and Rr = +-y2 - Y1 lie within +-1.02 on limbs within
+// 2^29 + 2^27, inside what the general form feeds the same products; PP, PPP within +-4.1.
+SBV_HD void pt29_madd_core(xyzz& R, const apt29& q, bool neg, bool one, bool x_only) {
     if (R.inf) {
         R.X = q.x;
         f29_cneg(R.Y, q.y, neg);
@@ -114,8 +122,13 @@ SBV_HD void pt29_madd(xyzz& R, const apt29& q, bool neg) {
     // X1, Y1 in (-0.01, 1.01) after f29_red_q; every product |A||B| <= 28, so every reduced value lies within +-4.9;
     // P, Rr within +-5.3 (the zero filter covers +-16); X3 before f29_red_q within +-19, Y3 within +-5.
     fe29 U2, S2, P, Rr, PP, PPP, Q, t, V;
-    f29_mulx(U2, q.x, R.ZZ);
-    f29_mulx(S2, q.y, R.ZZZ);
+    if (one) {
+        U2 = q.x;
+        S2 = q.y;
+    } else {
+        f29_mulx(U2, q.x, R.ZZ);
+        f29_mulx(S2, q.y, R.ZZZ);
+    }
     f29_sub(P, U2, R.X);
     f29_cneg(S2, S2, neg);
     f29_sub(Rr, S2, R.Y);
@@ -144,16 +157,31 @@ SBV_HD void pt29_madd(xyzz& R, const apt29& q, bool neg) {
     fe29 X3;
     f29_reduce_x(X3, c);                        // X3 = Rr^2 - PPP - 2 Q, one reduction
     f29_red_q(X3);
-    f29_sub(t, Q, X3);
-    f29_neg(V, R.Y);
-    f29_cols_zero(c);
-    f29_cols_mul(c, Rr, t);
-    f29_cols_mul(c, V, PPP);
-    f29_reduce_x(R.Y, c);                       // Y3 = Rr (Q - X3) - Y1 PPP, one reduction
-    f29_red_q(R.Y);
+    if (!x_only) {
+        f29_sub(t, Q, X3);
+        f29_neg(V, R.Y);
+        f29_cols_zero(c);
+        f29_cols_mul(c, Rr, t);
+        f29_cols_mul(c, V, PPP);
+        f29_reduce_x(R.Y, c);                   // Y3 = Rr (Q - X3) - Y1 PPP, one reduction
+        f29_red_q(R.Y);
+        if (one) R.ZZZ = PPP;
+        else f29_mulx(R.ZZZ, R.ZZZ, PPP);
+    }
     R.X = X3;
-    f29_mulx(R.ZZ, R.ZZ, PP);
-    f29_mulx(R.ZZZ, R.ZZZ, PPP);
+    if (one) R.ZZ = PP;
+    else f29_mulx(R.ZZ, R.ZZ, PP);
+}
+SBV_HD void pt29_madd(xyzz& R, const apt29& q, bool neg) { pt29_madd_core(R, q, neg, false, false); }
+// pt29_madd for a caller that reads X and ZZ of the sum only: 361 multiply-accumulates less.  Y and ZZZ of R are undefined afterwards
+// (unless R was infinity, or the addition was one of the exceptional cases: those leave a full point as pt29_madd does).
+SBV_HD void pt29_madd_x(xyzz& R, const apt29& q, bool neg) { pt29_madd_core(R, q, neg, false, true); }
+// R = (x1, y1) + (q.x, +-q.y): affine + affine -> XYZZ in 4M + 2S, exact like pt29_madd (equal points double, opposite points give
+// infinity).  x1, y1 value-reduced, as pt29_madd expects X and Y of its accumulator; the result is a pt29_madd accumulator.
+SBV_HD void pt29_mmadd(xyzz& R, const fe29& x1, const fe29& y1, const apt29& q, bool neg) {
+    const fe29 x = x1, y = y1;                  // x1, y1 may be R's own coordinates
+    R.X = x; R.Y = y; R.ZZ = f29_one(); R.ZZZ = f29_one(); R.inf = false;
+    pt29_madd_core(R, q, neg, true, false);
 }
 
 // ---- general XYZZ doubling and addition (the lanes-per-signature butterfly of the latency kernel) ------------------------
