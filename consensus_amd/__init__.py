@@ -478,6 +478,102 @@ def secp256k1_verify_msgs(msgs, sigs_der, keys) -> bytes:
     return _verify_msgs("sbv_secp256k1_verify_msgs", msgs, sigs_der, keys)
 
 
+def _sec1_pack(keys, offsets=None):
+    """(m, packed bytes, offset table or None) of SEC1 keys.  keys: a list of byte strings (packed back to back, with an offset table),
+    or one bytes object of 33-byte compressed keys (the fixed stride, no table); offsets: a table of m + 1 entries to pass as it is."""
+    if isinstance(keys, (bytes, bytearray)) and offsets is None:
+        if len(keys) % 33:
+            raise ValueError("a bytes object of SEC1 keys must be m x 33 bytes (compressed keys); pass a list for mixed lengths")
+        return len(keys) // 33, bytes(keys), None
+    if offsets is not None:
+        m = len(offsets) - 1
+        ko = (ctypes.c_uint64 * (m + 1))(*offsets)
+        return m, (bytes(keys) if isinstance(keys, (bytes, bytearray)) else b"".join(keys)), ko
+    m = len(keys)
+    ko = (ctypes.c_uint64 * (m + 1))()
+    a = 0
+    for i in range(m):
+        ko[i] = a
+        a += len(keys[i])
+    ko[m] = a
+    return m, b"".join(keys), ko
+
+
+def _decode_keys(symbol, keys, offsets, want_ok):
+    m, kb, ko = _sec1_pack(keys, offsets)
+    fn = getattr(load(), symbol)
+    fn.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p]
+    keys64, ok = ctypes.create_string_buffer(max(1, 64 * m)), ctypes.create_string_buffer(max(1, m))
+    _check(fn(kb, ko, m, keys64, ok if want_ok else None))
+    return keys64.raw[:64 * m], (ok.raw[:m] if want_ok else None)
+
+
+def p256_decode_keys(keys, offsets=None, want_ok: bool = True):
+    """sbv_p256_decode_keys: SEC1 public keys (65 bytes 04 | X | Y, 33 bytes 02/03 | X) -> (keys64, ok): X | Y per key in one bytes object,
+    the bytes every ECDSA entry and register_keys take, 64 zero bytes and ok 0 for a refused key.  keys: a list of byte strings, or one
+    bytes object of m x 33 compressed keys (the fixed stride)."""
+    return _decode_keys("sbv_p256_decode_keys", keys, offsets, want_ok)
+
+
+def secp256k1_decode_keys(keys, offsets=None, want_ok: bool = True):
+    """sbv_secp256k1_decode_keys: the same for secp256k1."""
+    return _decode_keys("sbv_secp256k1_decode_keys", keys, offsets, want_ok)
+
+
+_SEC1_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+
+
+def p256_decode_keys_stream(d_keys_ptr: int, d_key_offsets_ptr: int, key_bytes: int, m: int, d_keys64_ptr: int, d_ok_ptr: int = 0,
+                            stream: int = 0) -> None:
+    """sbv_p256_decode_keys_stream: device pointers, launched on `stream`, no synchronisation.  d_key_offsets_ptr 0: the 33-byte stride."""
+    lib = load()
+    lib.sbv_p256_decode_keys_stream.argtypes = _SEC1_STREAM_ARGS
+    _check(lib.sbv_p256_decode_keys_stream(d_keys_ptr or None, d_key_offsets_ptr or None, key_bytes, m, d_keys64_ptr or None, d_ok_ptr or None,
+                                           stream or None))
+
+
+def secp256k1_decode_keys_stream(d_keys_ptr: int, d_key_offsets_ptr: int, key_bytes: int, m: int, d_keys64_ptr: int, d_ok_ptr: int = 0,
+                                 stream: int = 0) -> None:
+    """sbv_secp256k1_decode_keys_stream: the same for secp256k1."""
+    lib = load()
+    lib.sbv_secp256k1_decode_keys_stream.argtypes = _SEC1_STREAM_ARGS
+    _check(lib.sbv_secp256k1_decode_keys_stream(d_keys_ptr or None, d_key_offsets_ptr or None, key_bytes, m, d_keys64_ptr or None,
+                                                d_ok_ptr or None, stream or None))
+
+
+def _verify_msgs_sec1(symbol, msgs, sigs_der, keys) -> bytes:
+    n, mo, so, _ = _msgs_tables(msgs, sigs_der, bytes(64 * len(msgs)))
+    m, kb, ko = _sec1_pack(keys)
+    if m != n:
+        raise ValueError("one SEC1 key per message")
+    out = ctypes.create_string_buffer(max(1, (n + 7) // 8))
+    fn = getattr(load(), symbol)
+    fn.argtypes = _MSGS_ARGS + [ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_void_p]
+    _check(fn(b"".join(msgs), mo, b"".join(sigs_der), so, kb, ko, n, out))
+    return out.raw[:(n + 7) // 8]
+
+
+def p256_verify_msgs_sec1(msgs, sigs_der, keys) -> bytes:
+    """sbv_p256_verify_msgs_sec1: verify_msgs with the signers' keys as SEC1 octet strings (a list, or m x 33 bytes of compressed keys),
+    decoded on the GPU in front of the front end, once per signature.  A refused key is a reject."""
+    return _verify_msgs_sec1("sbv_p256_verify_msgs_sec1", msgs, sigs_der, keys)
+
+
+def secp256k1_verify_msgs_sec1(msgs, sigs_der, keys) -> bytes:
+    """sbv_secp256k1_verify_msgs_sec1: the same in front of the generic secp256k1 step."""
+    return _verify_msgs_sec1("sbv_secp256k1_verify_msgs_sec1", msgs, sigs_der, keys)
+
+
+def debug_sec1_op(curve: int, op: int, records):
+    """sbv_debug_sec1_op (test only): one case per lane, 192-byte input records -> 128-byte output records (include/sbv.h)"""
+    lib = load()
+    n = len(records)
+    lib.sbv_debug_sec1_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+    out = ctypes.create_string_buffer(max(1, 128 * n))
+    _check(lib.sbv_debug_sec1_op(curve, op, b"".join(records), out, n))
+    return [out.raw[128 * i:128 * i + 128] for i in range(n)]
+
+
 def set_grouping(enabled: bool, min_batch: int = 0, min_count: int = 0, max_groups: int = 0) -> None:
     """In-step grouping of generic batches by public key (0 keeps a value; min_batch = GROUP_MIN_BATCH_DEFAULT restores the
     built-in thresholds); see include/sbv.h."""

@@ -44,6 +44,7 @@
 #include "ecdsa_sign_msgs_kernels.h"
 #include "k256_schnorr_kernels.h"
 #include "k256_schnorr_keyed_kernels.h"
+#include "sec1_keys_kernels.h"
 
 namespace {
 
@@ -2567,7 +2568,8 @@ namespace {
 // c.mu held.  tables(): the scheme's device tables; step(after_prep): its tuple step over c.d_tuples, which records after_prep.
 template <class Tables, class Step>
 int verify_msgs_tuples(Context& c, const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
-                       const uint8_t* keys, size_t n, uint8_t* accept_bitmap, Tables&& tables, Step&& step) {
+                       const uint8_t* keys, size_t n, uint8_t* accept_bitmap, Tables&& tables, Step&& step, int sec1_curve = -1,
+                       const uint64_t* key_offsets = nullptr) {
     if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
     if (n == 0) return SBV_OK;
     if (n > kMaxChunk) { g_err = "batch larger than 2^21: split it"; return SBV_EINVAL; }         // before any array is read
@@ -2575,25 +2577,35 @@ int verify_msgs_tuples(Context& c, const uint8_t* msgs, const uint64_t* msg_offs
     size_t mbytes = 0, sbytes = 0;
     int rc = check_offsets(msg_offsets, n, msgs, mbytes);
     if (rc == SBV_OK) rc = check_offsets(sig_offsets, n, sigs, sbytes);
+    // SEC1 keys (the _sec1 entries): the packed keys and their offsets are staged behind the n x 64 key array, which the decode kernel fills
+    const bool sec1 = sec1_curve >= 0;
+    size_t kbytes = sec1 ? n * 33 : 0;
+    if (rc == SBV_OK && sec1 && key_offsets) rc = check_offsets(key_offsets, n, keys, kbytes);
     if (rc != SBV_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
     if ((rc = tables()) != SBV_OK) return rc;
     const size_t koff = (sbytes + 15) & ~(size_t)15;
+    const size_t ooff = koff + n * 64, poff = ooff + (sec1 && key_offsets ? (n + 1) * sizeof(uint64_t) : 0);      // ooff: a multiple of 8
     if ((rc = grow(c.d_msgs, c.msgs_cap, mbytes + 16)) != SBV_OK) return rc;
-    if ((rc = grow(c.d_sigs, c.sigs_cap, koff + n * 64 + 16)) != SBV_OK) return rc;
+    if ((rc = grow(c.d_sigs, c.sigs_cap, poff + kbytes + 16)) != SBV_OK) return rc;
     if ((rc = grow(c.d_moff, c.moff_cap, n + 1)) != SBV_OK) return rc;
     if ((rc = grow(c.d_soff, c.soff_cap, n + 1)) != SBV_OK) return rc;
     return run_chunks_host(c, n, accept_bitmap, t0, true,
         [&](size_t, size_t) {
             if (mbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_msgs, msgs, mbytes, hipMemcpyHostToDevice, c.stream));
             if (sbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs, sigs, sbytes, hipMemcpyHostToDevice, c.stream));
-            HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs + koff, keys, n * 64, hipMemcpyHostToDevice, c.stream));
+            if (!sec1) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs + koff, keys, n * 64, hipMemcpyHostToDevice, c.stream));
+            if (sec1 && kbytes) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs + poff, keys, kbytes, hipMemcpyHostToDevice, c.stream));
+            if (sec1 && key_offsets) HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_sigs + ooff, key_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
             HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_moff, msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
             HIP_TRY(SBV_EDEVICE, hipMemcpyAsync(c.d_soff, sig_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
             return SBV_OK;
         },
         [&](size_t, size_t, hipEvent_t after_prep) {
+            if (sec1)
+                HIP_TRY(SBV_EDEVICE, sbv::launch_sec1_decode_keys(sec1_curve, c.d_sigs + poff, key_offsets ? reinterpret_cast<const uint64_t*>(c.d_sigs + ooff) : nullptr,
+                                                                  kbytes, n, c.d_sigs + koff, nullptr, c.stream));
             HIP_TRY(SBV_EDEVICE, sbv::launch_msg_frontend_tuples(c.d_msgs, c.d_moff, c.d_sigs, c.d_soff, c.d_sigs + koff, n,
                                                                  reinterpret_cast<u32*>(c.d_tuples), c.stream, 0, 0, mbytes, sbytes));
             return step(after_prep);
@@ -2616,6 +2628,99 @@ extern "C" int sbv_secp256k1_verify_msgs(const uint8_t* msgs, const uint64_t* ms
                                   HIP_TRY(SBV_EDEVICE, hipEventRecord(after_prep, c.stream));
                                   return enqueue_k256(c, c.d_tuples, n, c.d_bitmap, c.stream);
                               });
+}
+
+// The same with the signers' keys as SEC1 octet strings (include/sbv.h): k_sec1_decode_keys runs in front of the front end and fills
+// the key array it reads; everything behind it is the path above, untouched.  One decode per signature.
+extern "C" int sbv_p256_verify_msgs_sec1(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
+                                         const uint8_t* keys, const uint64_t* key_offsets, size_t n, uint8_t* accept_bitmap) {
+    SBV_ENTER(c);
+    return verify_msgs_tuples(c, msgs, msg_offsets, sigs, sig_offsets, keys, n, accept_bitmap, [] { return SBV_OK; },
+                              [&](hipEvent_t after_prep) { return enqueue(c, c.d_tuples, n, c.d_bitmap, c.stream, after_prep); },
+                              SBV_SEC1_P256, key_offsets);
+}
+
+extern "C" int sbv_secp256k1_verify_msgs_sec1(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
+                                              const uint8_t* keys, const uint64_t* key_offsets, size_t n, uint8_t* accept_bitmap) {
+    SBV_ENTER(c);
+    return verify_msgs_tuples(c, msgs, msg_offsets, sigs, sig_offsets, keys, n, accept_bitmap, [&] { return ensure_k256_table(c); },
+                              [&](hipEvent_t after_prep) {
+                                  HIP_TRY(SBV_EDEVICE, hipEventRecord(after_prep, c.stream));
+                                  return enqueue_k256(c, c.d_tuples, n, c.d_bitmap, c.stream);
+                              },
+                              SBV_SEC1_K256, key_offsets);
+}
+
+// ---- SEC1 public keys (sec1_keys.h, sec1_keys_kernels.hip; include/sbv.h) --------------------------------------------------------
+// Stateless: no table, nothing of the context written.  The _stream forms read and write the caller's buffers on the caller's stream
+// alone (c.busy is neither waited for nor recorded); the host forms use buffers of the call's own size.
+namespace {
+int sec1_decode_stream(int curve, const void* d_keys, const void* d_key_offsets, size_t key_bytes, size_t m, void* d_keys64, void* d_ok,
+                       void* hip_stream) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!d_keys || !d_keys64) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (misaligned(3, d_keys64) || misaligned(7, d_key_offsets)) { g_err = "misaligned device pointer"; return SBV_EINVAL; }
+    if (m > SBV_SEC1_MAX_M) { g_err = "batch larger than 2^32: split it"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    HIP_TRY(SBV_EDEVICE, sbv::launch_sec1_decode_keys(curve, static_cast<const uint8_t*>(d_keys), static_cast<const uint64_t*>(d_key_offsets), key_bytes, m,
+                                                      static_cast<uint8_t*>(d_keys64), static_cast<uint8_t*>(d_ok), static_cast<hipStream_t>(hip_stream)));
+    return SBV_OK;
+}
+
+int sec1_decode_host(int curve, const uint8_t* keys, const uint64_t* key_offsets, size_t m, uint8_t* keys64, uint8_t* ok) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if (m == 0) return SBV_OK;
+    if (!keys || !keys64) { g_err = "null pointer"; return SBV_EINVAL; }
+    if (m > SBV_SEC1_MAX_M) { g_err = "batch larger than 2^32: split it"; return SBV_EINVAL; }
+    size_t kbytes = m * 33;
+    if (key_offsets) {
+        const int rc = check_offsets(key_offsets, m, keys, kbytes);
+        if (rc != SBV_OK) return rc;
+    }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_k = kbytes ? cb.upload(keys, kbytes) : cb.alloc(16);        // every key empty: nothing of keys is read
+    const uint64_t* d_off = cb.upload(key_offsets, (m + 1) * sizeof(uint64_t));
+    uint8_t* d_keys = cb.alloc(m * 64);
+    uint8_t* d_ok = ok ? cb.alloc(m) : nullptr;
+    if (cb.good()) cb.launch(sbv::launch_sec1_decode_keys(curve, d_k, d_off, kbytes, m, d_keys, d_ok, c.stream));
+    cb.download(keys64, d_keys, m * 64);
+    cb.download(ok, d_ok, m);
+    return cb.finish();
+}
+}  // namespace
+
+extern "C" int sbv_p256_decode_keys(const uint8_t* keys, const uint64_t* key_offsets, size_t m, uint8_t* keys64, uint8_t* ok) {
+    return sec1_decode_host(SBV_SEC1_P256, keys, key_offsets, m, keys64, ok);
+}
+extern "C" int sbv_secp256k1_decode_keys(const uint8_t* keys, const uint64_t* key_offsets, size_t m, uint8_t* keys64, uint8_t* ok) {
+    return sec1_decode_host(SBV_SEC1_K256, keys, key_offsets, m, keys64, ok);
+}
+extern "C" int sbv_p256_decode_keys_stream(const void* d_keys, const void* d_key_offsets, size_t key_bytes, size_t m, void* d_keys64, void* d_ok,
+                                           void* hip_stream) {
+    return sec1_decode_stream(SBV_SEC1_P256, d_keys, d_key_offsets, key_bytes, m, d_keys64, d_ok, hip_stream);
+}
+extern "C" int sbv_secp256k1_decode_keys_stream(const void* d_keys, const void* d_key_offsets, size_t key_bytes, size_t m, void* d_keys64, void* d_ok,
+                                                void* hip_stream) {
+    return sec1_decode_stream(SBV_SEC1_K256, d_keys, d_key_offsets, key_bytes, m, d_keys64, d_ok, hip_stream);
+}
+
+extern "C" int sbv_debug_sec1_op(int curve, int op, const uint8_t* in, uint8_t* out, size_t n) {
+    SBV_ENTER(c);
+    if (!c.ready) { g_err = "sbv_init has not succeeded"; return SBV_ENOTINIT; }
+    if ((curve != SBV_SEC1_P256 && curve != SBV_SEC1_K256) || op < 0 || op >= SBV_SEC1_OPS) { g_err = "unknown curve or op"; return SBV_EINVAL; }
+    if (n == 0) return SBV_OK;
+    if (!in || !out || n > 65536) { g_err = "null pointer or too many cases"; return SBV_EINVAL; }
+    HIP_TRY(SBV_EDEVICE, hipSetDevice(c.hip_dev));
+    sbv::CallBuffers cb(c.stream, &g_err);
+    const uint8_t* d_in = cb.upload(in, n * 192);
+    uint8_t* d_out = cb.alloc(n * 128);
+    if (cb.good()) cb.launch(sbv::launch_sec1_op(curve, op, d_in, d_out, n, c.stream));
+    cb.download(out, d_out, n * 128);
+    return cb.finish();
 }
 
 // ---- batch signing (p256_sign.h) ----------------------------------------------------------------------

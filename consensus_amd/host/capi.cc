@@ -12,6 +12,7 @@
 #include "p256_host.h"
 #include "ed25519_host.h"
 #include "k256_host.h"
+#include "sec1_host.h"
 #include "chain_emul.h"
 #include "verifier.h"
 
@@ -119,6 +120,18 @@ int sbvh_sign_schnorr(void* h, const uint8_t* expanded, uint32_t n_keys, const u
 }
 void sbvh_register_consenter(void* h, uint64_t id, const uint8_t q[64]) { ((VHandle*)h)->v->RegisterConsenter(id, q); }
 void sbvh_register_client(void* h, const char* client, const uint8_t q[64]) { ((VHandle*)h)->v->RegisterClient(client, q); }
+// the same with the key as a SEC1 octet string: 0, or -1 (nothing registered) for a refused key or under Scheme::ED25519
+int sbvh_register_consenter_sec1(void* h, uint64_t id, const uint8_t* key, size_t len) { return ((VHandle*)h)->v->RegisterConsenterSec1(id, key, len) ? 0 : -1; }
+int sbvh_register_client_sec1(void* h, const char* client, const uint8_t* key, size_t len) { return ((VHandle*)h)->v->RegisterClientSec1(client, key, len) ? 0 : -1; }
+// Verifier::DecodeKeys: m SEC1 keys packed back to back + m + 1 offsets (null: the 33-byte stride) -> m x 64 bytes and ok (may be null); the status code
+int sbvh_decode_keys(void* h, const uint8_t* keys, const uint64_t* key_offsets, size_t m, uint8_t* keys64, uint8_t* ok) {
+    return ((VHandle*)h)->v->DecodeKeys(keys, key_offsets, m, keys64, ok).code;
+}
+// Verifier::VerifyMsgsSec1: raw messages + DER signatures + SEC1 keys, each with its offset table (key_offsets null: the 33-byte stride) -> bitmap
+int sbvh_verify_msgs_sec1(void* h, const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets, const uint8_t* keys,
+                          const uint64_t* key_offsets, size_t n, uint8_t* bitmap) {
+    return ((VHandle*)h)->v->VerifyMsgsSec1(msgs, msg_offsets, sigs, sig_offsets, keys, key_offsets, n, bitmap).code;
+}
 // 0: clients registered from now on get no comb slot on the device (their request signatures go as generic tuples)
 void sbvh_set_device_client_keys(void* h, int on) { ((VHandle*)h)->v->SetDeviceClientKeys(on != 0); }
 void sbvh_set_verification_sequence(void* h, uint64_t s) { ((VHandle*)h)->v->SetVerificationSequence(s); }
@@ -345,6 +358,24 @@ int sbvh_k256_schnorr_sign(const uint8_t rec[64], const uint8_t msg[32], const u
 }
 int sbvh_k256_schnorr_verify(const uint8_t pk[32], const uint8_t msg[32], const uint8_t sig[64]) { return k256_schnorr_verify(pk, msg, sig) ? 0 : -1; }
 int sbvh_k256_schnorr_lift(const uint8_t pk[32], uint8_t key[64]) { return k256_schnorr_lift(pk, key) ? 0 : -1; }
+// the SEC1 key decoders on their own (sec1_host.cc): 0, or -1 and 64 zero bytes for a refused key; only key[0 .. len) is read
+int sbvh_p256_sec1_decode(const uint8_t* key, size_t len, uint8_t key64[64]) { return p256_sec1_decode(key, len, key64) ? 0 : -1; }
+int sbvh_k256_sec1_decode(const uint8_t* key, size_t len, uint8_t key64[64]) { return k256_sec1_decode(key, len, key64) ? 0 : -1; }
+// m keys on `threads` threads (tools/bench_sec1.py: what a host pays for decoding on its own): curve 0 = P-256, 1 = secp256k1; key i =
+// keys[koff[i] .. koff[i+1]), or the 33-byte stride when koff is null; ok may be null
+void sbvh_sec1_decode_batch(int curve, const uint8_t* keys, const uint64_t* koff, size_t m, uint8_t* keys64, uint8_t* ok, int threads) {
+    if (threads < 1) threads = 1;
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; ++t)
+        th.emplace_back([=] {
+            for (size_t i = (size_t)t; i < m; i += (size_t)threads) {
+                const size_t k0 = koff ? (size_t)koff[i] : 33 * i, k1 = koff ? (size_t)koff[i + 1] : 33 * i + 33;
+                const bool good = curve == 1 ? k256_sec1_decode(keys + k0, k1 - k0, keys64 + 64 * i) : p256_sec1_decode(keys + k0, k1 - k0, keys64 + 64 * i);
+                if (ok) ok[i] = good ? 1 : 0;
+            }
+        });
+    for (auto& x : th) x.join();
+}
 
 // ---- formats ---------------------------------------------------------------------------------------
 void sbvh_proposal_digest(const void* payload, size_t pl, const void* header, size_t hl, const void* meta, size_t ml,

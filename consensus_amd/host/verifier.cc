@@ -15,6 +15,7 @@
 #include "ed25519_host.h"
 #include "k256_host.h"
 #include "p256_host.h"
+#include "sec1_host.h"
 
 namespace sbvhost {
 
@@ -142,6 +143,23 @@ int Backend::keccak256_msgs(const uint8_t* msgs, const uint64_t* moff, size_t n,
     });
     return 0;
 }
+int Backend::decode_keys(bool k256, const uint8_t* keys, const uint64_t* koff, size_t m, uint8_t* keys64, uint8_t* ok) {
+    parallel_chunks(m, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) {
+            const size_t k0 = koff ? (size_t)koff[i] : 33 * i, k1 = koff ? (size_t)koff[i + 1] : 33 * i + 33;
+            const bool good = k256 ? k256_sec1_decode(keys + k0, k1 - k0, keys64 + 64 * i) : p256_sec1_decode(keys + k0, k1 - k0, keys64 + 64 * i);
+            if (ok) ok[i] = good ? 1 : 0;
+        }
+    });
+    return 0;
+}
+int Backend::verify_msgs_sec1(bool k256, const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys,
+                              const uint64_t* koff, size_t n, uint8_t* bitmap) {
+    std::vector<uint8_t> keys64(n * 64);
+    const int rc = decode_keys(k256, keys, koff, n, keys64.data(), nullptr);
+    if (rc != 0) return rc;
+    return k256 ? verify_msgs_k256(msgs, moff, sigs, soff, keys64.data(), n, bitmap) : verify_msgs(msgs, moff, sigs, soff, keys64.data(), n, bitmap);
+}
 int Backend::schnorr_sign_k256(const uint8_t* expanded, uint32_t n_keys, const uint32_t* key_index, const uint8_t* msgs, const uint8_t* aux,
                                size_t n, uint8_t* sigs, uint8_t* ok) {
     if (n == 0) return 0;
@@ -262,6 +280,17 @@ class SbvBackend : public Backend {
     int schnorr_verify_keyed_k256(const uint8_t* msgs, const uint8_t* sigs, const uint32_t* slots, size_t n, uint8_t* ok) override {
         if (rc_ != SBV_OK) return rc_;
         return sbv_secp256k1_schnorr_verify_keyed(msgs, sigs, slots, n, ok);
+    }
+    int decode_keys(bool k256, const uint8_t* keys, const uint64_t* koff, size_t m, uint8_t* keys64, uint8_t* ok) override {
+        if (rc_ != SBV_OK) return rc_;
+        return k256 ? sbv_secp256k1_decode_keys(keys, koff, m, keys64, ok) : sbv_p256_decode_keys(keys, koff, m, keys64, ok);
+    }
+    int verify_msgs_sec1(bool k256, const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys,
+                         const uint64_t* koff, size_t n, uint8_t* bitmap) override {
+        if (rc_ != SBV_OK) return rc_;
+        ++msgs_batches_;
+        return k256 ? sbv_secp256k1_verify_msgs_sec1(msgs, moff, sigs, soff, keys, koff, n, bitmap)
+                    : sbv_p256_verify_msgs_sec1(msgs, moff, sigs, soff, keys, koff, n, bitmap);
     }
     void* host_alloc(size_t bytes) override { return rc_ == SBV_OK ? sbv_host_alloc(bytes) : nullptr; }
     void host_free(void* p) override { sbv_host_free(p); }
@@ -1620,6 +1649,52 @@ long Verifier::RegisterSchnorrKey(const uint8_t pk[32]) {
     uint8_t key[64];
     (void)k256_schnorr_lift(pk, key);              // a key off the curve: x | 0^32, which registers as an invalid slot
     return co_.backend().register_key_k256(key);
+}
+
+Status Verifier::DecodeKeys(const uint8_t* keys, const uint64_t* key_offsets, size_t m, uint8_t* keys64, uint8_t* ok) {
+    if (ed()) return Status::Invalid("DecodeKeys needs an ECDSA scheme");
+    if (m == 0) return Status::Ok();
+    if (!keys || !keys64) return Status::Invalid("DecodeKeys: null pointer");
+    if (key_offsets) {
+        if (key_offsets[0] != 0) return Status::Invalid("DecodeKeys: the offset table must start at 0");
+        for (size_t i = 0; i < m; ++i)
+            if (key_offsets[i + 1] < key_offsets[i]) return Status::Invalid("DecodeKeys: the offset table decreases");
+    }
+    const int rc = co_.backend().decode_keys(k256(), keys, key_offsets, m, keys64, ok);
+    if (rc != 0) return Status::Unavailable("decoding SEC1 keys failed on the backend");
+    return Status::Ok();
+}
+
+Status Verifier::VerifyMsgsSec1(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets, const uint8_t* keys,
+                                const uint64_t* key_offsets, size_t n, uint8_t* bitmap) {
+    if (ed()) return Status::Invalid("VerifyMsgsSec1 needs an ECDSA scheme");
+    if (n == 0) return Status::Ok();
+    if (n > ((size_t)1 << 21)) return Status::Invalid("VerifyMsgsSec1: more than 2^21 requests: split the batch");
+    if (!msg_offsets || !sig_offsets || !keys || !bitmap) return Status::Invalid("VerifyMsgsSec1: null pointer");
+    for (const uint64_t* t : {msg_offsets, sig_offsets, key_offsets}) {
+        if (!t) continue;
+        if (t[0] != 0) return Status::Invalid("VerifyMsgsSec1: an offset table must start at 0");
+        for (size_t i = 0; i < n; ++i)
+            if (t[i + 1] < t[i]) return Status::Invalid("VerifyMsgsSec1: an offset table decreases");
+    }
+    if ((msg_offsets[n] != 0 && !msgs) || (sig_offsets[n] != 0 && !sigs)) return Status::Invalid("VerifyMsgsSec1: null pointer");
+    const int rc = co_.backend().verify_msgs_sec1(k256(), msgs, msg_offsets, sigs, sig_offsets, keys, key_offsets, n, bitmap);
+    if (rc != 0) return Status::Unavailable("raw-message verification with SEC1 keys failed on the backend");
+    return Status::Ok();
+}
+
+// One key at registration: the host form (a device call for one square root would cost more than the root).
+bool Verifier::RegisterConsenterSec1(uint64_t id, const uint8_t* key, size_t len) {
+    uint8_t q[64];
+    if (ed() || !(k256() ? k256_sec1_decode(key, len, q) : p256_sec1_decode(key, len, q))) return false;
+    RegisterConsenter(id, q);
+    return true;
+}
+bool Verifier::RegisterClientSec1(const std::string& client_id, const uint8_t* key, size_t len) {
+    uint8_t q[64];
+    if (ed() || !(k256() ? k256_sec1_decode(key, len, q) : p256_sec1_decode(key, len, q))) return false;
+    RegisterClient(client_id, q);
+    return true;
 }
 
 Status Verifier::VerifySchnorrKeyed(const uint8_t* msgs, const uint8_t* sigs, const uint32_t* slots, size_t n, uint8_t* ok) {

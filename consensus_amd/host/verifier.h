@@ -140,6 +140,17 @@ class Backend {
         (void)sigs; (void)pks; (void)msgs; (void)moff; (void)n; (void)bitmap; return -2;
     }
     virtual uint64_t msgs_batches() { return 0; }       // test hook: how many batches the three forms above ran
+    // SEC1 public keys -> 64 bytes X | Y each (include/sbv.h: sbv_p256_decode_keys, sbv_secp256k1_decode_keys): key i is
+    // keys[koff[i] .. koff[i+1]), koff starts at 0 and never decreases, or null for the 33-byte stride; keys64 m x 64, ok m bytes or
+    // null; a refused key is 64 zero bytes.  The default is a CPU loop over the host forms (sec1_host.cc, one square root per
+    // compressed key); the GPU backend makes one device call.  0, or the backend's error code.
+    virtual int decode_keys(bool k256, const uint8_t* keys, const uint64_t* koff, size_t m, uint8_t* keys64, uint8_t* ok);
+    // verify_msgs / verify_msgs_k256 with the signers' keys as SEC1 octet strings (include/sbv.h: sbv_p256_verify_msgs_sec1,
+    // sbv_secp256k1_verify_msgs_sec1): bit i = the verdict under the 64 bytes decode_keys gives for key i, a refused key is a reject.
+    // The default is decode_keys followed by verify_msgs / verify_msgs_k256 (-2 when those are unsupported); the GPU backend makes one
+    // device call, the keys decoded in front of the front end.
+    virtual int verify_msgs_sec1(bool k256, const uint8_t* msgs, const uint64_t* moff, const uint8_t* sigs, const uint64_t* soff, const uint8_t* keys,
+                                 const uint64_t* koff, size_t n, uint8_t* bitmap);
 };
 // The host route of a batch of ECDSA requests (what VerifyProposal's workers build when no front end takes the batch): tuple i = strict
 // DER parse of signature i (zeros when refused) | SHA-256(message i) | keys[64 i ..), n x 160 bytes, over the worker pool.
@@ -304,6 +315,23 @@ class Verifier {
     // (sbv_secp256k1_schnorr_verify_keyed on the device).  INVALID under another scheme, UNAVAILABLE without a registry or on an error.
     long RegisterSchnorrKey(const uint8_t pk[32]);
     Status VerifySchnorrKeyed(const uint8_t* msgs, const uint8_t* sigs, const uint32_t* slots, size_t n, uint8_t* ok);
+    // The ECDSA schemes only: public keys as SEC1 octet strings (65 bytes 04 | X | Y or 33 bytes 02/03 | X: what an X.509
+    // SubjectPublicKeyInfo, Go's elliptic.Marshal / MarshalCompressed and secp256k1 traffic carry).  DecodeKeys: m keys packed back to
+    // back with m + 1 offsets (null: the 33-byte stride) -> keys64 m x 64 bytes X | Y and ok[i] (may be null), one backend call
+    // (sbv_p256_decode_keys / sbv_secp256k1_decode_keys on the device, a CPU loop otherwise).  INVALID under Scheme::ED25519 or for a
+    // bad offset table, UNAVAILABLE on a backend error.  RegisterConsenterSec1 / RegisterClientSec1: decode, then RegisterConsenter /
+    // RegisterClient on the 64 bytes — the key is decoded once, at registration, and every later signature of that signer goes through
+    // the scheme's registered-key entries; false, and nothing registered, for a refused key.
+    Status DecodeKeys(const uint8_t* keys, const uint64_t* key_offsets, size_t m, uint8_t* keys64, uint8_t* ok);
+    // The unregistered raw-message route for a caller that holds SEC1 keys: n messages, DER signatures and SEC1 keys, each packed back to
+    // back with n + 1 offsets (key_offsets null: the 33-byte stride) -> bitmap, bit i = signature i verifies over SHA-256(message i)
+    // under key i; a key that does not decode is a reject.  One backend call (the _sec1 entries on the device: the keys are decoded
+    // once per signature there; for signers that repeat, register them instead).  n <= 2^21.  INVALID under Scheme::ED25519, for a bad
+    // offset table or a larger n; UNAVAILABLE on a backend error.
+    Status VerifyMsgsSec1(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets, const uint8_t* keys,
+                          const uint64_t* key_offsets, size_t n, uint8_t* bitmap);
+    bool RegisterConsenterSec1(uint64_t id, const uint8_t* key, size_t len);
+    bool RegisterClientSec1(const std::string& client_id, const uint8_t* key, size_t len);
     CoalescerStats stats() { return co_.stats(); }
     Scheme scheme() const { return opt_.scheme; }
 

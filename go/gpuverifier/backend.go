@@ -160,6 +160,16 @@ type RawMessageVerifier interface {
 	VerifyMsgs(scheme Scheme, items []Item) (ok []bool, err error)
 }
 
+// SEC1KeyDecoder decodes public keys from their SEC1 octet strings (sbv_p256_decode_keys / sbv_secp256k1_decode_keys): keys[i] is 65
+// bytes 04|X|Y or 33 bytes 02/03|X, what elliptic.Marshal / elliptic.MarshalCompressed, an X.509 SubjectPublicKeyInfo and secp256k1
+// traffic carry; pubs[i] = X|Y, the 64 bytes Item.Key, the key registries and RawMessageVerifier take.  ok[i] = false, and a zero key,
+// for anything elliptic.Unmarshal / UnmarshalCompressed refuse: another length or prefix (the hybrid forms 06 / 07 too), a coordinate
+// >= p, a point off the curve, an X without a point.  SchemeP256 and SchemeSecp256k1 only.  The compressed form costs a square root
+// per key, which is why it runs on the device.  An optional interface beside Backend like K256SchnorrKeyed: callers type-assert.
+type SEC1KeyDecoder interface {
+	DecodeKeysSEC1(scheme Scheme, keys [][]byte) (pubs [][64]byte, ok []bool, err error)
+}
+
 // ErrNoBatchSigner: the backend has no batch signing entry (the pure-Go backend).
 var ErrNoBatchSigner = errors.New("gpuverifier: backend has no batch signer")
 

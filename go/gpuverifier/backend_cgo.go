@@ -984,3 +984,43 @@ func (b *gpuBackend) SignBatchSchnorr(keys [][32]byte, keyIndex []uint32, msgs [
 }
 
 func (b *gpuBackend) Close() { close(b.jobs) }
+
+// DecodeKeysSEC1: sbv_p256_decode_keys / sbv_secp256k1_decode_keys on the keys packed back to back (one device call; nothing secret
+// is involved).
+func (b *gpuBackend) DecodeKeysSEC1(scheme Scheme, keys [][]byte) (pubs [][64]byte, ok []bool, err error) {
+	m := len(keys)
+	if m == 0 || (scheme != SchemeP256 && scheme != SchemeSecp256k1) {
+		return nil, nil, errors.New("gpuverifier: DecodeKeysSEC1 needs a key and an ECDSA scheme")
+	}
+	offs := make([]uint64, m+1)
+	for i := range keys {
+		offs[i+1] = offs[i] + uint64(len(keys[i]))
+	}
+	kb := make([]byte, offs[m]+1) // never empty: the entry refuses a null key array
+	for i := range keys {
+		copy(kb[offs[i]:], keys[i])
+	}
+	out := make([]byte, 64*m)
+	flags := make([]byte, m)
+	b.on(func() {
+		var rc C.int
+		if scheme == SchemeSecp256k1 {
+			rc = C.sbv_secp256k1_decode_keys(u8(kb), (*C.uint64_t)(unsafe.Pointer(&offs[0])), C.size_t(m), u8(out), u8(flags))
+		} else {
+			rc = C.sbv_p256_decode_keys(u8(kb), (*C.uint64_t)(unsafe.Pointer(&offs[0])), C.size_t(m), u8(out), u8(flags))
+		}
+		if rc != 0 {
+			err = lastError()
+		}
+	})
+	if err != nil {
+		return nil, nil, err
+	}
+	pubs = make([][64]byte, m)
+	ok = make([]bool, m)
+	for i := 0; i < m; i++ {
+		copy(pubs[i][:], out[64*i:64*i+64])
+		ok[i] = flags[i] != 0
+	}
+	return pubs, ok, nil
+}

@@ -676,6 +676,63 @@ sbv_secp256k1_sign_msgs_stream(const void* d_keys, uint32_t n_keys, const void* 
                                void* d_ok, void* d_work, void* hip_stream);
 int sbv_debug_ecdsa_der_op(int curve, uint32_t flags, const uint8_t* rs, uint8_t* records, uint8_t* len, size_t n);
 
+/* SEC1 public keys.  Every ECDSA entry above takes a key as 64 raw bytes Qx | Qy; keys travel as SEC1 octet strings (SEC1 2.3.3: 65
+ * bytes 04 | X | Y, or 33 bytes 02/03 | X — the content of an X.509 SubjectPublicKeyInfo, Go's elliptic.Marshal /
+ * MarshalCompressed, every secp256k1 key on a wire).  These entries decode them on the device, one key per lane
+ * (consensus_amd/csrc/sec1_keys.h, sec1_keys_kernels.hip): the compressed form costs a square root mod p per key, a^((p+1)/4) on either
+ * curve (253 squarings).  The rules are SEC1 2.3.4 as Go applies them (elliptic.Unmarshal, elliptic.UnmarshalCompressed):
+ *   length 65, first byte 04        accepted iff X < p, Y < p and the point is on the curve
+ *   length 33, first byte 02 / 03   accepted iff X < p and X^3 + aX + b is a square; Y is the root whose low bit is the prefix's
+ *   everything else                 refused: any other length (0 and 1 included, so the one-byte point at infinity too) and the hybrid
+ *                                   prefixes 06 / 07 (Go and Bitcoin's strict-encoding rule refuse them; libsecp256k1 and OpenSSL
+ *                                   would accept them)
+ * A refused key is 64 zero bytes and ok[i] = 0; an accepted one is X | Y and ok[i] = 1.  (0, 0) is on neither curve, so every
+ * verifier of the library rejects against a refused key.  Only the bytes of key i are read, at any alignment.
+ *   sbv_*_decode_keys          keys: the m keys packed back to back; key i = keys[key_offsets[i] .. key_offsets[i+1]).  key_offsets ==
+ *                              NULL means the fixed 33-byte stride, key i = keys[33 i .. 33 i + 33) (compressed keys only).
+ *                              Otherwise m + 1 offsets, the first 0, never decreasing, else SBV_EINVAL.  keys64: m x 64 bytes;
+ *                              ok: m bytes or NULL.  The buffers are of the call's own size; the call waits for the result.
+ *   sbv_*_decode_keys_stream   device pointers, launched on `hip_stream`, no synchronisation, under the stream contract of the `_dev`
+ *                              entries for every buffer they name.  They own no mutable device state and
+ *                              may be the first call of a process after sbv_init.  key_bytes: the size of d_keys; each lane holds
+ *                              its own offset pair against it (monotone, inside it), and a pair that fails is a refused key, not
+ *                              a read outside the buffer.  With d_key_offsets == NULL a key behind key_bytes is refused likewise.
+ *                              d_keys64 must be 4-byte aligned and d_key_offsets 8-byte aligned, else SBV_EINVAL; d_keys and d_ok may
+ *                              be at any address.
+ * SBV_ENOTINIT before sbv_init, whatever the arguments; m == 0 is SBV_OK and writes nothing; a null keys with m > 0, a null keys64 or
+ * m > 2^32 is SBV_EINVAL with nothing written.  A refused call leaves the library as it was.
+ * Registering a compressed key is decode_keys followed by sbv_p256_register_keys / sbv_secp256k1_register_keys on keys64, as
+ * sbv_secp256k1_schnorr_lift_keys followed by register_keys registers an x-only key.
+ *   sbv_*_verify_msgs_sec1     sbv_p256_verify_msgs / sbv_secp256k1_verify_msgs with the signers' keys as a packed SEC1 array: key i =
+ *                              keys[key_offsets[i] .. key_offsets[i+1]) (NULL: the 33-byte stride).  The packed keys and their offsets
+ *                              go up, the decode kernel fills the n x 64 key array the front end reads, and the existing path runs
+ *                              untouched.  Bit i is by definition what the verify_msgs entry of the curve returns when keys[i] is the
+ *                              64 bytes decode_keys writes for key i: a refused key is a reject, never an error.  Limits (n <= 2^21),
+ *                              return codes and prep_us accounting (the decode kernel counts as prep) as verify_msgs; a key offset
+ *                              table that does not start at 0 or that decreases is SBV_EINVAL.  Keys are decoded once per SIGNATURE,
+ *                              not once per distinct signer.  For signers that repeat: decode once, register the keys, and use the
+ *                              keyed entries (sbv_p256_verify_msgs_keyed, sbv_secp256k1_verify_msgs_keyed).  No sharded form.
+ *   sbv_debug_sec1_op          test only: one case per lane, n <= 65 536, curve 0 = P-256, 1 = secp256k1; in: n x 192 bytes, out: n x
+ *                              128 bytes, byte 127 = ok, all zero when not ok (the records of sbv_debug_secp256k1_recover_op).
+ *                                op 0  a (32 bytes, taken mod p) -> a^((p+1)/4) mod p (32 bytes); ok = a is a square
+ *                                op 1  x (32 bytes), parity (byte 63: 0 / 1) -> x | y of the point with that x and parity; ok = 0
+ *                                      for x >= p, no point with that x, or a parity byte above 1
+ *                              Any other op or curve, a null pointer or n > 65 536 is SBV_EINVAL. */
+int sbv_p256_decode_keys(const uint8_t* keys, const uint64_t* key_offsets, size_t m, uint8_t* keys64, uint8_t* ok);
+int
+sbv_secp256k1_decode_keys(const uint8_t* keys, const uint64_t* key_offsets, size_t m, uint8_t* keys64, uint8_t* ok);
+int sbv_p256_decode_keys_stream(const void* d_keys, const void* d_key_offsets, size_t key_bytes, size_t m, void* d_keys64,
+                                void* d_ok, void* hip_stream);
+int
+sbv_secp256k1_decode_keys_stream(const void* d_keys, const void* d_key_offsets, size_t key_bytes, size_t m, void* d_keys64,
+                                 void* d_ok, void* hip_stream);
+int sbv_p256_verify_msgs_sec1(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
+                              const uint8_t* keys, const uint64_t* key_offsets, size_t n, uint8_t* accept_bitmap);
+int
+sbv_secp256k1_verify_msgs_sec1(const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* sigs, const uint64_t* sig_offsets,
+                               const uint8_t* keys, const uint64_t* key_offsets, size_t n, uint8_t* accept_bitmap);
+int sbv_debug_sec1_op(int curve, int op, const uint8_t* in, uint8_t* out, size_t n);
+
 /* Strict DER parse of an ECDSA-Sig-Value with Go x/crypto/cryptobyte rules
  * (crypto/ecdsa.parseSignature): out = r | s, 32 bytes each, big-endian, zero padded.
  * Returns SBV_OK or SBV_EPARSE (then out is all zero, which every verify rejects). */
